@@ -11,6 +11,11 @@ for this path (timing/timeSFMBAL.h:64-95: GeneralSFMFactor<SfmCamera,Point3>, Un
 SetCeresDefaults, points-first Schur ordering).  Data are synthetic (the BAL file is not in the image):
 gtsam_amd/datasets.py::ladybug_1723, seed 42, values resident in HBM before the timed region.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times exactly `--steps` iterations in the Python mirror of the host and prints the headline
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`); `--dump-outputs DIR` also writes the last timed step's
+results as .npy files.  `--full` adds everything else: the C++ host leg (the headline when its program is built), the reference's
+CPU baseline and parity, rooflines, time-to-converged, the other workloads and, for N > 1, the other parallel modes.
 """
 import argparse
 import json
@@ -209,6 +214,16 @@ def workload_record(workload, desc, cpp):
     return rec
 
 
+def dump_outputs(out_dir, opt):
+    """--dump-outputs: what the last timed step left for a caller of iterate() -- the packed values, the step (delta) of its last lambda
+    try, the error and lambda -- as float64 .npy files (about 8 MB on the L1723 shape)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"values": opt.values_packed(), "delta": opt.dev.delta(),
+              "error": np.array([opt.error()]), "lambda": np.array([opt.lambda_()])}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -228,9 +243,17 @@ def main():
     ap.add_argument("--workloads", default="auto",
                     help="N = 1, headline workload: the same line also carries `workloads` -- north_star's second headline (sphere2500, with the reference's own "
                          "optimizer as its cpu_baseline) and the Venice-1778 shape, each timed in its C++ host program.  auto = sphere2500,venice1778; off; or a comma list")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: C++ host leg, CPU baseline and parity against the reference, rooflines (dense schedule, in-run PMC "
+                         "traffic), time-to-converged, device memory, other workloads, N > 1 extra modes.  Without it the run sets up, warms up, times "
+                         "--steps iterations of the Python mirror and prints the headline line; the options above only act with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (values, delta, error, lambda) as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     extra_workloads = []
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.workload == "ladybug1723" and args.host == "auto" and args.workloads != "off":
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.workload == "ladybug1723" and args.host == "auto" and args.workloads != "off":
         extra_workloads = ["sphere2500", "venice1778"] if args.workloads == "auto" else [w for w in args.workloads.split(",") if w]
     # (input files of the slow generators are written by child processes from the start, CPU only)
     prepared = {w: start_workload_file(w) for w in extra_workloads if w in ("venice1778",)}
@@ -281,13 +304,15 @@ def main():
         return DeviceLevenbergMarquardt(problem_, values_, params_, device=local_rank, shard=rank, n_shards=world,
                                         allreduce=allreduce if world > 1 else None)
 
-    torch.cuda.synchronize()
-    mem_free0 = torch.cuda.mem_get_info()[0]     # (the first handle of the process: nothing is in the library's block cache yet)
+    if args.full:
+        torch.cuda.synchronize()
+        mem_free0 = torch.cuda.mem_get_info()[0]     # (the first handle of the process: nothing is in the library's block cache yet)
     opt = fresh()
-    torch.cuda.synchronize()
-    handle_bytes = mem_free0 - torch.cuda.mem_get_info()[0]      # device memory the first handle of the process takes from the driver ...
-    from gtsam_amd.lib import load as _load_lib
-    cached_bytes = int(_load_lib().gtg_cached_memory_bytes())   # ... of which the library keeps this much released set-up scratch for the next handle
+    if args.full:
+        torch.cuda.synchronize()
+        handle_bytes = mem_free0 - torch.cuda.mem_get_info()[0]      # device memory the first handle of the process takes from the driver ...
+        from gtsam_amd.lib import load as _load_lib
+        cached_bytes = int(_load_lib().gtg_cached_memory_bytes())   # ... of which the library keeps this much released set-up scratch for the next handle
     n_red = opt.dev.reduced_dim
 
     def run_iterations(o, k, values_=None, params_=None):
@@ -345,7 +370,8 @@ def main():
         return rec
 
     run_iterations(opt, args.warmup)
-    opt.dev.enable_timing(True); opt.dev.reset_timing()
+    if args.full:
+        opt.dev.enable_timing(True); opt.dev.reset_timing()
     inner0 = opt.getInnerIterations()
     barrier()
     t0 = time.perf_counter()
@@ -353,6 +379,24 @@ def main():
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
     tries = opt.getInnerIterations() - inner0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, opt)
+    parallelism = ((f"speculative-lambda x{world} (replicas; replica r tries the r-th lambda of the rejection sequence, decisions replayed in order: the sequential trajectory)"
+                    if speculative else f"landmark-shard x{world}") if world > 1 else "single GPU")
+    if not args.full:
+        if rank == 0:
+            print(json.dumps({
+                "metric": "LM iterations/sec", "value": args.steps / elapsed, "unit": "iterations/s", "higher_is_better": True, "dtype": "f64",
+                "ms_per_step": 1e3 * elapsed / args.steps, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "scaling": "strong", "data": "synthetic",
+                "value_source": "Python mirror of the host (gtsam_amd/optimizer.py over the C ABI): exactly `steps` iterate() calls of one optimizer constructed "
+                                "before the timed region; a run that converges restarts from the initial values inside the timed region (bench.py --full adds the C++ host leg)",
+                "lambda_tries": int(tries), "tries_per_iteration": tries / args.steps,
+                "config": {"workload": desc, "reduced_dim": int(n_red), "parallelism": parallelism}}), flush=True)
+        if world > 1:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+        return
     phases = opt.dev.phase_ms()
     chol_ms, chol_calls = phases["cholesky"]
     chol_flops = opt.dev.cholesky_flops()
@@ -491,8 +535,7 @@ def main():
                        "cameras": int((problem.var_type == 1).sum()), "points": int((problem.var_type == 2).sum()),
                        "poses": int(((problem.var_type == 0) | (problem.var_type == 3)).sum()), "between_factors": int(problem.n_between),
                        "observations": int(problem.n_sfm), "reduced_dim": int(n_red),
-                       "parallelism": (f"speculative-lambda x{world} (replicas; replica r tries the r-th lambda of the rejection sequence, decisions replayed in order: the sequential trajectory)"
-                                       if speculative else f"landmark-shard x{world}") if world > 1 else "single GPU",
+                       "parallelism": parallelism,
                        "exchange": (("RCCL" if getattr(comm, "device_backend", False) else "gloo through the host (dry run)") + (": gather of 5 doubles + broadcast of the accepted values per iteration" if speculative else ": all-reduce of the reduced camera system [S | g] at block granularity + landmark part of delta per try, Hessian diagonal per linearisation")) if world > 1 else None},
             "extra_modes": extra,
             # the cross-checks a reader needs, at the top level: tries per iteration of the timed loop and the device time per iteration

@@ -1,4 +1,4 @@
-"""pytest configuration: `gpu` marker, golden-fixture loader, optional live reference."""
+"""pytest configuration: `gpu` marker, golden-fixture loader, example datasets, optional live reference."""
 import os
 import sys
 
@@ -41,6 +41,28 @@ def pytest_collection_modifyitems(session, config, items):
 
 def load_golden(name):
     return dict(np.load(os.path.join(GOLDEN_DIR, name + ".npz"), allow_pickle=False))
+
+
+_DATA_DIR = None
+
+
+def data_dir():
+    """The reference's example datasets the tests read (tests/golden/data/*.gz: gzipped, otherwise unchanged copies), unpacked once per
+    process into a temporary directory that is removed at exit.  Returns its path with a trailing separator."""
+    global _DATA_DIR
+    if _DATA_DIR is None:
+        import atexit
+        import gzip
+        import shutil
+        import tempfile
+        d = tempfile.mkdtemp(prefix="gtsam_amd_data_")
+        atexit.register(shutil.rmtree, d, True)
+        src = os.path.join(GOLDEN_DIR, "data")
+        for f in os.listdir(src):
+            with gzip.open(os.path.join(src, f), "rb") as i, open(os.path.join(d, f[:-3]), "wb") as o:
+                shutil.copyfileobj(i, o)
+        _DATA_DIR = d + os.sep
+    return _DATA_DIR
 
 
 @pytest.fixture(scope="session")

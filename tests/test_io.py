@@ -1,22 +1,19 @@
 """Dataset readers (gtsam_amd/io.py) against the reference's own loaders: the golden fixtures hold what
-SfmData::FromBalFile / readG2o returned for the reference's shipped files; when /root/reference and oracle/_ref are
-present (build container) the live loaders are compared as well."""
-import os
+SfmData::FromBalFile / readG2o returned for the reference's shipped files (copies under tests/golden/data); when oracle/_ref
+is present the live loaders are compared as well."""
 
 import numpy as np
 import pytest
 
 from gtsam_amd import io
 from gtsam_amd.problem import NOISE_GAUSSIAN, NOISE_ISOTROPIC, NOISE_UNIT
-from tests.conftest import load_golden
+from tests.conftest import data_dir, load_golden
 
-DATA = "/root/reference/examples/Data/"
+DATA = data_dir()
 
 
 def test_bal_reader_matches_reference_loader():
     path = DATA + "dubrovnik-3-7-pre.txt"
-    if not os.path.exists(path):
-        pytest.skip("reference data not present on this machine")
     g = load_golden("dubrovnik_3_7")
     cams, pts, oc, op, oz = io.read_bal(path)
     assert np.array_equal(oc, g["obs_cam"]) and np.array_equal(op, g["obs_pt"])
@@ -26,8 +23,6 @@ def test_bal_reader_matches_reference_loader():
 
 def test_toro_reader_matches_reference_loader():
     path = DATA + "sphere2500.txt"
-    if not os.path.exists(path):
-        pytest.skip("reference data not present on this machine")
     g = load_golden("sphere2500")
     d = io.read_g2o3d(path)
     assert np.array_equal(d["v1"], g["v1"]) and np.array_equal(d["v2"], g["v2"])
@@ -40,7 +35,7 @@ def test_toro_reader_matches_reference_loader():
 @pytest.mark.parametrize("name", ["pose3example.txt", "pose3example-offdiagonal.txt", "pose3example-grid.txt"])
 def test_g2o_quat_reader_matches_live_reference(name, live_ref):
     path = DATA + name
-    if live_ref is None or not os.path.exists(path):
+    if live_ref is None:
         pytest.skip("live reference not present")
     r = live_ref.load_g2o3d(path)
     d = io.read_g2o3d(path)
@@ -82,8 +77,6 @@ def test_bal_reader_on_a_written_file(tmp_path):
 def test_load2d_reader_matches_reference_loader(fn, name):
     """io.read_2d against what the reference's load2D returned for its shipped 2-D files (golden fixtures)."""
     path = DATA + fn
-    if not os.path.exists(path):
-        pytest.skip("reference data not present on this machine")
     g = load_golden(name)
     d = io.read_2d(path)
     assert np.array_equal(d["v1"], g["v1"]) and np.array_equal(d["v2"], g["v2"])
@@ -132,8 +125,6 @@ def _same_tokens(a, b, rtol):
 
 def test_native_bal_reader_matches_restatement_and_reference():
     path = DATA + "dubrovnik-3-7-pre.txt"
-    if not os.path.exists(path):
-        pytest.skip("reference data not present on this machine")
     nat = io.read_bal(path); py = io.read_bal_py(path)
     for a, b in zip(nat, py):
         assert a.shape == b.shape and a.dtype == b.dtype
@@ -168,7 +159,7 @@ def test_native_bal_roundtrip_and_errors(tmp_path):
 
 def test_bal_writer_matches_reference_writer(tmp_path, live_ref):
     path = DATA + "dubrovnik-3-7-pre.txt"
-    if live_ref is None or not os.path.exists(path):
+    if live_ref is None:
         pytest.skip("live reference not present")
     ref_out = str(tmp_path / "ref.txt"); my_out = str(tmp_path / "mine.txt")
     assert live_ref.rewrite_bal(path, ref_out) == 0
@@ -184,7 +175,7 @@ def test_bal_writer_matches_reference_writer(tmp_path, live_ref):
                                        ("noisyToyGraph.txt", False), ("w100.graph", False)])
 def test_g2o_writer_matches_reference_writer(tmp_path, live_ref, name, is3d):
     path = DATA + name
-    if live_ref is None or not os.path.exists(path):
+    if live_ref is None:
         pytest.skip("live reference not present")
     ref_out = str(tmp_path / "ref.g2o"); my_out = str(tmp_path / "mine.g2o")
     live_ref.rewrite_g2o(path, ref_out, is3d)
@@ -202,8 +193,6 @@ def test_sfmdata_tests_of_the_reference_restated(tmp_path):
     has 3 measurements starting with camera 0, its point projects within 12 px of the measurement), writeBAL_Dubrovnik
     (what is written reads back to the same cameras, points and measurements)."""
     path = DATA + "dubrovnik-3-7-pre.txt"
-    if not os.path.exists(path):
-        pytest.skip("reference data not present on this machine")
     from oracle import gtsam_oracle as O
     cams, pts, oc, op, oz = io.read_bal(path)
     assert cams.shape == (3, 17) and pts.shape == (7, 3)
@@ -234,8 +223,6 @@ def test_dataset_tests_of_the_reference_restated():
     factor BetweenFactor(1, 0, Pose2(-0.99879, 0.0417574, -0.00818381), Unit)); readG2o3D on pose3example (:147-218: six
     relative poses and five vertex poses as quaternion / translation literals, Isotropic precision 10000, 1e-5);
     readG2o3DNonDiagonalNoise (:221-256: information matrix with 10000 on the diagonal and i+1 off it, 1e-2)."""
-    if not os.path.exists(DATA + "w100.graph"):
-        pytest.skip("reference data not present on this machine")
     d = io.read_2d(DATA + "w100.graph")
     assert d["v1"].size == 300 and d["vertex_keys"].size == 100
     assert (int(d["v1"][0]), int(d["v2"][0])) == (1, 0) and int(d["noise_kind"][0]) == NOISE_UNIT
@@ -298,8 +285,6 @@ def test_read_g2o_2d_reads_information_matrices_and_round_trips(tmp_path):
                                        ("sphere2500.txt", True), ("noisyToyGraph.txt", False), ("w100.graph", False), ("w20000.txt", False)])
 def test_native_g2o_reader_and_writer_match_the_restatement(tmp_path, name, is3d):
     path = DATA + name
-    if not os.path.exists(path):
-        pytest.skip("reference data not present on this machine")
     nat = io.read_g2o3d(path) if is3d else io.read_2d(path)
     py = io.read_g2o3d_py(path) if is3d else io.read_2d_py(path)
     for k in ("v1", "v2", "noise_kind", "vertex_keys"):

@@ -13,8 +13,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tools import host_profile as HP  # noqa: E402
+from tests.conftest import data_dir  # noqa: E402
 
-DATA = "/root/reference/examples/Data/"
+DATA = data_dir()
 EXE = os.path.join(ROOT, "tests", "_build", "test_shim_extractor")
 
 _CHILD = r'''
@@ -50,8 +51,8 @@ print("RESULT " + json.dumps(res))
 
 
 def test_cpp_and_python_extractors_hand_the_library_identical_tables():
-    if not (os.path.exists(EXE) and os.path.isdir(DATA) and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libgtsam_ref.so"))):
-        pytest.skip("shim extractor test / reference data / oracle/_ref not present on this machine")
+    if not (os.path.exists(EXE) and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libgtsam_ref.so"))):
+        pytest.skip("shim extractor test / oracle/_ref not built")
     stub = HP.build_stub()
     env = dict(os.environ); env["LD_PRELOAD"] = stub
     r = subprocess.run([EXE, DATA], env=env, capture_output=True, text=True, timeout=300)

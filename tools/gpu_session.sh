@@ -6,7 +6,7 @@
 out=gpurun_out/${1:-session}; mkdir -p $out
 timeout 1200 python -m pytest tests -x -q -m gpu 2>&1 | tail -15 > $out/gpu_tests.log
 tail -3 $out/gpu_tests.log
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err
 timeout 300 python tools/df_trace.py > $out/df_trace_summary.txt 2> $out/df_trace.err
 GTG_DEBUG_TIMING=1 timeout 600 python tools/time_sfm_bal.py ladybug1723 > $out/time_sfm_bal_cpp.json 2> $out/cpp_host_setup_breakdown.txt
 timeout 300 python tools/df_stress.py 120 3 > $out/stress.txt 2> $out/stress.err

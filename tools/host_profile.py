@@ -25,7 +25,10 @@ STUB = os.path.join(ROOT, "tools", "hipstub", "libhipstub.so")
 def build_stub():
     src = os.path.join(ROOT, "tools", "hipstub", "hipstub.c")
     if not os.path.exists(STUB) or os.path.getmtime(STUB) < os.path.getmtime(src):
-        subprocess.run(["gcc", "-O2", "-fPIC", "-shared", "-o", STUB, src], check=True)
+        # (written under a name of this process and renamed into place: a test running in parallel never preloads a half-written file)
+        tmp = f"{STUB}.{os.getpid()}.tmp"
+        subprocess.run(["gcc", "-O2", "-fPIC", "-shared", "-o", tmp, src], check=True)
+        os.replace(tmp, STUB)
     return STUB
 
 

@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 600 python $REPO/bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.log
+timeout 600 python $REPO/bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.log
 tail -c 600 $OUT/${TAG}_bench.json
 rm -rf /tmp/prof_s /tmp/prof_f /tmp/prof_w
 # (kernel tracing does not serialise dispatches: the two cooperating kernels of the dataflow Cholesky run as in production; should a
