@@ -29,18 +29,9 @@
 
 namespace gt {
 
-static std::vector<std::pair<gtg_context*, HostIndex*>> g_index;  // tiny registry (handles are few)
-static std::mutex g_index_mutex;                                   // handles may be created / destroyed from several host threads
 HostIndex& host_index(gtg_context* c) {
-  std::lock_guard<std::mutex> lock(g_index_mutex);
-  for (auto& kv : g_index) if (kv.first == c) return *kv.second;
-  g_index.emplace_back(c, new HostIndex);
-  return *g_index.back().second;
-}
-void drop_index(gtg_context* c) {
-  std::lock_guard<std::mutex> lock(g_index_mutex);
-  for (size_t i = 0; i < g_index.size(); i++)
-    if (g_index[i].first == c) { delete g_index[i].second; g_index.erase(g_index.begin() + i); return; }
+  if (!c->index) c->index.reset(new HostIndex);
+  return *c->index;
 }
 
 // Large scratch arrays of the analysis (tens of MB, first touched by many threads at once): 2 MB aligned and advised to
@@ -815,7 +806,7 @@ void analyze(gtg_context& c) {
       // default schedule: the dataflow pass (chol_dataflow.hip), symbolic fill at 128-tile granularity.  GTG_CHOL=streams
       // selects the per-column launch sequence of cholesky.hip; the elimination-tree schedule only exists there.
       c.use_df = dataflow_schedule_selected();
-      free_df_plan(c.df);
+      c.df = DfPlan();
       std::vector<int32_t> tile_part;                      // nested dissection: the part of every block column (parts are aligned to column pairs)
       if (!pair_part.empty()) { tile_part.resize(nt); for (int t = 0; t < nt; t++) tile_part[t] = pair_part[t / 2]; }
       // The two tile schedules are built side by side: the task lists of the dataflow pass on a thread of their own (pure host code),

@@ -1,10 +1,10 @@
 // api.hip -- the C ABI (include/gtsam_amd.h): handle life cycle, upload of the factor tables (shard filter, noise table),
 // the per-iteration entry points (linearize / try_lambda / accept) that issue the HIP kernels, getters and test hooks.
-// The one-time symbolic analysis of a graph is analysis.hip.  All arithmetic of the hot path runs in the HIP kernels.
+// The one-time symbolic analysis of a graph is analysis.hip, what a handle owns on its device and how it is released
+// device_memory.hip.  All arithmetic of the hot path runs in the HIP kernels.
 #include <algorithm>
 #include <atomic>
 #include <exception>
-#include <functional>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -15,8 +15,6 @@
 #include <map>
 #include <set>
 #include <memory>
-#include <new>
-#include <sys/mman.h>
 #include <mutex>
 #include <stdexcept>
 
@@ -36,104 +34,6 @@ static std::vector<void (*)(int)>& prewarm_units() { static std::vector<void (*)
 PrewarmUnit::PrewarmUnit(void (*fn)(int device)) { prewarm_units().push_back(fn); }
 
 static thread_local std::string g_last_error;
-
-void check_hip(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-// The big buffers of a handle (>= 16 MB: the E slots, the term lists, the stored tiles of the reduced system) are kept for the next
-// handle of the process when one is released instead of going back to the driver, at most GTG_ALLOC_CACHE_MB per DEVICE (default
-// 2048 = about one handle of the headline size, 0.7 % of the device's memory; 0 switches it off); a kept block serves a request of
-// 80 - 100 % of its size on the same device.  On boxes where the driver clears device memory as it hands it out a fresh hipMalloc costs
-// ~30 ms per GB -- 10.9 of the 33 ms of a warm set-up of the L1723 shape in round 4, when the default was 0 -- and programs construct
-// optimizers one after the other (GncOptimizer: one per outer iteration; the reference's own timing programs).  History of the
-// default: 8192 in round 3 (the reduced system was a dense 1.9 GB - 31 GB array then), 0 in round 4, 2048 since round 5.  When an
-// allocation fails, every kept block of that device is released and the allocation is tried once more;
-// gtg_release_cached_memory() releases them at any time.  Every such buffer is fully written by the kernels before it is read, so
-// recycled contents are never observed (GTG_ALLOC_POISON=1 fills a recycled block with NaNs first: a debug mode the parity suite
-// can be run under).
-namespace {
-struct KeptBlock { void* p; size_t bytes; int device; };
-std::mutex g_kept_mu;
-std::vector<KeptBlock> g_kept;
-constexpr size_t kKeepMin = (size_t)16 << 20;
-size_t keep_limit() {
-  static const size_t lim = [] { const char* e = std::getenv("GTG_ALLOC_CACHE_MB"); return (size_t)(e ? std::max(0L, std::atol(e)) : 2048L) << 20; }();
-  return lim;
-}
-size_t kept_bytes_on(int dev) { size_t b = 0; for (const auto& k : g_kept) if (k.device == dev) b += k.bytes; return b; }   // (g_kept_mu held)
-void* take_kept(size_t bytes, size_t* got) {
-  if (bytes < kKeepMin || keep_limit() == 0) return nullptr;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  std::lock_guard<std::mutex> lk(g_kept_mu);
-  int best = -1;
-  for (int i = 0; i < (int)g_kept.size(); i++)
-    if (g_kept[i].device == dev && g_kept[i].bytes >= bytes && g_kept[i].bytes - bytes <= g_kept[i].bytes / 5 &&
-        (best < 0 || g_kept[i].bytes < g_kept[best].bytes)) best = i;
-  if (best < 0) return nullptr;
-  void* q = g_kept[best].p;
-  *got = g_kept[best].bytes;
-  g_kept.erase(g_kept.begin() + best);
-  static const bool poison = std::getenv("GTG_ALLOC_POISON") != nullptr;
-  if (poison) (void)hipMemset(q, 0xFF, *got);   // all-ones bytes = a NaN in every double, -1 in every index
-  return q;
-}
-bool keep_block(void* q, size_t bytes) {        // (hipFree synchronises the device; a kept block must be idle as well)
-  if (bytes < kKeepMin || keep_limit() == 0) return false;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return false;
-  std::lock_guard<std::mutex> lk(g_kept_mu);
-  if (kept_bytes_on(dev) + bytes > keep_limit()) return false;
-  if (hipDeviceSynchronize() != hipSuccess) return false;
-  g_kept.push_back(KeptBlock{q, bytes, dev});
-  return true;
-}
-size_t release_kept(int dev) {                  // dev < 0: every device
-  std::lock_guard<std::mutex> lk(g_kept_mu);
-  size_t freed = 0;
-  for (size_t i = 0; i < g_kept.size();) {
-    if (dev < 0 || g_kept[i].device == dev) {
-      int cur = 0;
-      const bool sw = hipGetDevice(&cur) == hipSuccess && cur != g_kept[i].device && hipSetDevice(g_kept[i].device) == hipSuccess;
-      (void)hipFree(g_kept[i].p);
-      if (sw) (void)hipSetDevice(cur);
-      freed += g_kept[i].bytes;
-      g_kept.erase(g_kept.begin() + (long)i);
-    } else i++;
-  }
-  return freed;
-}
-}  // namespace
-
-template <class T> void DevBuf<T>::alloc(size_t count) {
-  free();
-  n = count;
-  if (!count) return;
-  if (void* q = take_kept(sizeof(T) * count, &cap)) { p = static_cast<T*>(q); return; }
-  hipError_t e = hipMalloc(&p, sizeof(T) * count);
-  if (e != hipSuccess) {   // out of memory with blocks kept aside: give them back to the driver and try once more
-    (void)hipGetLastError();
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && release_kept(dev) > 0) e = hipMalloc(&p, sizeof(T) * count);
-  }
-  if (e != hipSuccess) { p = nullptr; n = 0; }
-  check_hip(e, "hipMalloc");
-  cap = sizeof(T) * count;
-}
-template <class T> void DevBuf<T>::upload(const T* host, size_t count, hipStream_t s) {
-  if (count != n || (count && !p)) alloc(count);
-  if (count) check_hip(hipMemcpyAsync(p, host, sizeof(T) * count, hipMemcpyHostToDevice, s), "H2D");
-}
-template <class T> void DevBuf<T>::free() {
-  if (p && !keep_block(p, cap ? cap : sizeof(T) * n)) (void)hipFree(p);
-  p = nullptr; n = 0; cap = 0;
-}
-template struct DevBuf<double>;
-template struct DevBuf<int32_t>;
-template struct DevBuf<int64_t>;
-template struct DevBuf<long long>;
-template struct DevBuf<unsigned char>;
 
 static void exchange(gtg_context& c, double* ptr, int64_t n);
 void exchange_sum(gtg_context& c, double* ptr, int64_t n) { exchange(c, ptr, n); }
@@ -160,17 +60,6 @@ static std::mutex& df_device_lock(int device) {
   if (!p) p.reset(new std::mutex);
   return *p;
 }
-
-// Every entry point runs on the handle's device and leaves the caller's current device as it found it (a torch or multi-GPU host
-// keeps its own notion of "current device").
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) check_hip(hipSetDevice(dev), "hipSetDevice"); else prev = -1;
-  }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 // Sharded: the scalars are partial sums and get all-reduced -- a COPY of them (second half of the buffer), so that slots a call
 // does not rewrite are not multiplied by the number of shards on every call (they would overflow to inf after a few hundred).
@@ -217,47 +106,6 @@ static void ensure_events(gtg_context& c) {   // the handle's own events, on its
   if (!c.phase_events.empty()) return;
   c.phase_events.resize(2 * GTG_PH_COUNT, nullptr);
   for (auto& e : c.phase_events) check_hip(hipEventCreate(&e), "event");
-}
-// A handle's stream and events outlive it: gtg_destroy parks them (idle) per device and the next gtg_create of the process takes them from
-// there -- creating a stream and 18 events cost 1.7 ms of every construction of an optimizer (tools/cpp/cold_start_probe.cpp), a third of
-// what the whole symbolic analysis of the L1723 shape takes now.  At most kParkedMax sets per device are kept; gtg_release_cached_memory()
-// destroys them with the cached device memory.
-struct ParkedQueue { int device; hipStream_t stream; hipStream_t copy_stream; std::vector<hipEvent_t> events; };
-static std::mutex g_parked_mu;
-static std::vector<ParkedQueue> g_parked;
-constexpr size_t kParkedMax = 4;
-static bool take_parked(gtg_context& c) {
-  if (std::getenv("GTG_NO_PARKED_STREAMS")) return false;   // (A/B: every handle creates its own stream and events)
-  std::lock_guard<std::mutex> lk(g_parked_mu);
-  for (size_t i = 0; i < g_parked.size(); i++)
-    if (g_parked[i].device == c.device) {
-      c.stream = g_parked[i].stream; c.copy_stream = g_parked[i].copy_stream; c.phase_events = std::move(g_parked[i].events);
-      g_parked.erase(g_parked.begin() + (long)i);
-      return true;
-    }
-  return false;
-}
-static bool park_queue(gtg_context& c) {   // (the caller has synchronised the streams)
-  if (std::getenv("GTG_NO_PARKED_STREAMS")) return false;
-  std::lock_guard<std::mutex> lk(g_parked_mu);
-  size_t n = 0;
-  for (const auto& q : g_parked) n += q.device == c.device;
-  if (n >= kParkedMax) return false;
-  g_parked.push_back(ParkedQueue{c.device, c.stream, c.copy_stream, std::move(c.phase_events)});
-  c.stream = nullptr; c.copy_stream = nullptr; c.phase_events.clear();
-  return true;
-}
-static void destroy_parked() {
-  std::lock_guard<std::mutex> lk(g_parked_mu);
-  int cur = 0; (void)hipGetDevice(&cur);
-  for (auto& q : g_parked) {
-    (void)hipSetDevice(q.device);
-    for (hipEvent_t e : q.events) if (e) (void)hipEventDestroy(e);
-    if (q.stream) (void)hipStreamDestroy(q.stream);
-    if (q.copy_stream) (void)hipStreamDestroy(q.copy_stream);
-  }
-  g_parked.clear();
-  (void)hipSetDevice(cur);
 }
 static void collect(gtg_context& c, std::initializer_list<int> phases) {
   if (!c.timing) return;
@@ -346,36 +194,17 @@ int gtg_destroy(gtg_handle c) {
   // profiles/r06_stress_240s.txt).  GTG_DESTROY_UNLOCKED=1: the A/B.
   std::unique_lock<std::mutex> no_factorisation_in_flight;
   if (!std::getenv("GTG_DESTROY_UNLOCKED")) no_factorisation_in_flight = std::unique_lock<std::mutex>(df_device_lock(c->device));
-  auto& f = c->f;
-  DevBuf<double>* dbl[] = {&c->values, &c->trial, &c->delta, &c->noise_data, &f.sfm_z, &f.sfm_J, &f.proj_z, &f.proj_J,
-                           &f.calib, &f.sensor, &f.between_z, &f.between_J, &f.prior_data, &f.prior_J, &c->Hd, &c->gred0,
-                           &c->hdiag_red, &c->V, &c->gp, &c->Hoff, &c->Linv, &c->ylm, &c->E, &c->vobs, &c->wobs, &c->cam_part, &c->cam_pack, &c->pcg_vec, &c->pcg_bj, &c->pcg_y, &c->delta_lm, &c->S,
-                           &c->Dinv, &c->xred, &c->partials, &c->scalars, &c->noise_rk};
-  for (auto* b : dbl) b->free();
-  DevBuf<int32_t>* i32[] = {&c->var_type, &c->lm_var, &c->red_var, &c->red_dim, &c->lm_index, &c->red_index, &c->lm_owned,
-                            &c->noise_kind, &c->noise_rkind, &f.sfm_cam, &f.sfm_point, &f.sfm_noise, &f.sfm_cam_at, &f.sfm_point_at, &c->obs_wpos, &f.proj_pose, &f.proj_point,
-                            &f.proj_noise, &f.proj_calib, &f.proj_sensor, &f.between_v1, &f.between_v2, &f.between_noise,
-                            &f.prior_var, &f.prior_noise, &c->obs_red, &c->obs_lm, &c->lm_obs, &c->lm_pri,
-                            &c->red_inc_kind, &c->red_inc_idx, &c->hoff_row, &c->hoff_col, &c->hoff_fac, &c->pair_row,
-                            &c->pair_col, &c->pair_oa, &c->pair_ob, &c->smart_status, &c->smart_lin_status, &c->smart_cache_state, &c->sfm_smart, &c->lm_smart};
-  for (auto* b : i32) b->free();
-  c->plan.rows.free(); c->plan.pairs.free(); c->plan.bcols.free(); c->plan.bwd_col_off.free(); c->plan.bwd_col_rows.free(); c->plan.stored.free(); c->plan.slot.free(); c->yred.free(); c->plan.exch.free(); c->xbuf.free();
-  DevBuf<int64_t>* i64[] = {&c->val_off, &c->dim_off, &c->red_off, &c->noise_off, &f.prior_off, &c->lm_obs_ptr,
-                            &c->lm_pri_ptr, &c->red_inc_ptr, &c->hoff_ptr, &c->pair_ptr, &c->smart_ptr, &c->pad_index};
-  for (auto* b : i64) b->free();
-  c->smart_params.free(); c->smart_cache_pose.free(); c->smart_cache_point.free();
-  c->chol_epoch_dev.free(); c->layout_probe.free(); c->xb_row_off.free(); c->xb_col_off.free(); c->xb_dim.free();
-  free_df_plan(c->df);
-  c->pivot_kind.free(); c->tile_exp.free();
-  destroy_chol_streams(*c);
-  if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-  if (!park_queue(*c)) {
-    for (hipEvent_t e : c->phase_events) if (e) (void)hipEventDestroy(e);
-    (void)hipStreamDestroy(c->stream);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-  }
-  drop_index(c);
+  // What outlives the handle -- its stream, copy stream and phase events -- is taken out of it; everything else it owns (all its device
+  // memory, the schedule's streams and events, the host index) goes with the context: here, under the lock, on the handle's device,
+  // before the streams are parked.
+  ParkedQueue q{c->device, c->stream, c->copy_stream, std::move(c->phase_events)};
   delete c;
+  if (q.copy_stream) (void)hipStreamSynchronize(q.copy_stream);
+  if (!park_queue(q)) {
+    for (hipEvent_t e : q.events) if (e) (void)hipEventDestroy(e);
+    (void)hipStreamDestroy(q.stream);
+    if (q.copy_stream) (void)hipStreamDestroy(q.copy_stream);
+  }
   return GTG_OK;
 }
 
@@ -897,7 +726,7 @@ int gtg_accept(gtg_handle c) {
   GTG_TRY
   if (!c || !c->have_trial) throw std::invalid_argument("gtg_accept: no trial values (call gtg_try_lambda)");
   DeviceGuard on_device(c->device);
-  std::swap(c->values.p, c->trial.p);
+  std::swap(c->values, c->trial);
   c->linearized = false; c->have_trial = false;
   return GTG_OK;
   GTG_CATCH
@@ -971,7 +800,6 @@ int gtg_get_jacobians(gtg_handle c, int type, double* out, int64_t n) {
   }
   if (n != cnt) throw std::invalid_argument("gtg_get_jacobians: wrong output size");
   DevBuf<double> recomputed;
-  struct Release { DevBuf<double>& b; ~Release() { b.free(); } } release{recomputed};   // (declared before the allocation: a throwing launch / sync frees it too)
   if (type == GTG_FAC_GENERAL_SFM && c->fused_sfm && cnt) {   // debug path: these records are not stored (fused.h) -- recomputed at the current values
     recomputed.alloc((size_t)cnt);
     launch_sfm_records(*c, recomputed.p);
@@ -1051,9 +879,7 @@ double gtg_debug_syrk_ms(gtg_handle c, int m, int abl, int reps) {
     for (int q = 0; q < nt * nt; q++) hs[(size_t)q] = q;
     DevBuf<int32_t> slot; slot.upload(hs.data(), hs.size(), c->stream);
     check_hip(hipMemset(S.p, 0, sizeof(double) * S.n), "memset");
-    const double ms = debug_time_syrk(*c, SMat{S.p, slot.p, nt}, m, abl, reps);
-    S.free(); slot.free();
-    return ms;
+    return debug_time_syrk(*c, SMat{S.p, slot.p, nt}, m, abl, reps);
   } catch (const std::exception& e) { g_last_error = e.what(); return -1.0; }
 }
 
@@ -1066,7 +892,6 @@ int gtg_debug_potrf_stamps(gtg_handle c, double* A128, long long* out15) {
   const int rc = gtg_dense_cholesky_host(c, A128, 128, nullptr);
   g_potrf_dbg_set(nullptr);
   check_hip(hipMemcpy(out15, dbg.p, 15 * sizeof(long long), hipMemcpyDeviceToHost), "D2H");
-  dbg.free();
   return rc;
   GTG_CATCH
 }
@@ -1187,6 +1012,7 @@ int gtg_dense_cholesky_host(gtg_handle c, double* A, int32_t n, double* rhs) {
   DeviceGuard on_device(c->device);
   const int NP = (n + kTile - 1) / kTile * kTile;
   const int nt = NP / kTile;
+  std::unique_lock<std::mutex> one_at_a_time;      // (declared before the buffers: they are released while it is held, on a throw as well)
   CholPlan plan;
   build_chol_plan(plan, nt, nullptr, c->stream);   // dense: every lower tile + the rhs row has a slot
   DevBuf<double> S, Dinv, x, fail;
@@ -1211,7 +1037,6 @@ int gtg_dense_cholesky_host(gtg_handle c, double* A, int32_t n, double* rhs) {
   pk[n - 1] = n >= 2 ? 1 : 2;
   DevBuf<unsigned char> dpk; dpk.upload(pk.data(), pk.size(), c->stream);
   DevBuf<double> dexp; dexp.alloc(NP / kTile + 1);
-  std::unique_lock<std::mutex> one_at_a_time;
   if (use_df) one_at_a_time = std::unique_lock<std::mutex>(df_device_lock(c->device));
   if (use_df) launch_cholesky_df(*c, Sm, NP, df, Dinv.p, fail.p, dpk.p, dexp.p);
   else launch_cholesky(*c, Sm, NP, plan, Dinv.p, fail.p, dpk.p, dexp.p);
@@ -1223,15 +1048,12 @@ int gtg_dense_cholesky_host(gtg_handle c, double* A, int32_t n, double* rhs) {
   check_hip(hipStreamSynchronize(c->stream), "sync");
   for (int64_t i = 0; i < n; i++)       // the factor: lower triangle (and what the diagonal tiles hold above it, as before)
     for (int64_t j = 0; j < std::min<int64_t>(n, (i / kTile + 1) * kTile); j++) A[i * n + j] = *hs.at(i, j);
-  dpk.free(); dexp.free();
-  S.free(); Dinv.free(); x.free(); fail.free(); plan.rows.free(); plan.pairs.free(); plan.bcols.free(); plan.stored.free(); plan.slot.free(); plan.bwd_col_off.free(); plan.bwd_col_rows.free();
-  free_df_plan(df);
   if (hf2[1] != 0.0) throw std::runtime_error("gtg_dense_cholesky_host: a dependency wait of the factorisation ran into its bound");
   return hf2[0] != 0.0 ? GTG_INDETERMINATE : GTG_OK;
   GTG_CATCH
 }
 
 int64_t gtg_release_cached_memory(void) { destroy_parked(); return (int64_t)release_kept(-1); }
-int64_t gtg_cached_memory_bytes(void) { std::lock_guard<std::mutex> lk(g_kept_mu); size_t b = 0; for (const auto& k : g_kept) b += k.bytes; return (int64_t)b; }
+int64_t gtg_cached_memory_bytes(void) { return (int64_t)kept_bytes(); }
 
 }  // extern "C"

@@ -1046,7 +1046,6 @@ void upload_df_plan(DfPlan& df, hipStream_t stream, const std::vector<int32_t>& 
       auto al = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
       const size_t b_t6 = al(4 * df.h_tasks.size()), b_kl = al(4 * df.h_klist.size()), b_lane = al(4 * lane_tab.size()), b_sub = sub16 ? al(8 * sub16->size()) : 0;
       DevBuf<unsigned char> ws; ws.alloc(b_t6 + b_kl + b_lane + b_sub + 256);
-      struct Release { DevBuf<unsigned char>& b; ~Release() { b.free(); } } release{ws};
       int32_t* d_t6 = reinterpret_cast<int32_t*>(ws.p); int32_t* d_kl = reinterpret_cast<int32_t*>(ws.p + b_t6);
       int32_t* d_lane = reinterpret_cast<int32_t*>(ws.p + b_t6 + b_kl);
       unsigned long long* d_sub = sub16 ? reinterpret_cast<unsigned long long*>(ws.p + b_t6 + b_kl + b_lane) : nullptr;
@@ -1117,11 +1116,6 @@ void upload_df_plan(DfPlan& df, hipStream_t stream, const std::vector<int32_t>& 
   check_hip(hipMemsetAsync(df.part_flag.p, 0, sizeof(long long) * df.part_flag.n, stream), "memset");
   check_hip(hipMemsetAsync(df.ctrl.p, 0, sizeof(int32_t) * 32, stream), "memset");
   check_hip(hipStreamSynchronize(stream), "df plan upload");
-}
-
-void free_df_plan(DfPlan& df) {
-  df.tasks.free(); df.klist.free(); df.tile_flag.free(); df.part_flag.free(); df.pd_flag.free(); df.ctrl.free(); df.trace.free(); df.has_sub.free();
-  df.chain_off.free(); df.chain_tiles.free();
 }
 
 // GTG_CHOL=streams selects the per-column launch sequence of cholesky.hip instead of the dataflow pass (the A/B of the tests; read per

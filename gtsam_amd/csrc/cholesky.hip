@@ -616,7 +616,6 @@ float debug_time_syrk(gtg_context& c, SMat S, int m, int abl, int reps) {
   float ms = 0;
   check_hip(hipEventElapsedTime(&ms, e0, e1), "elapsed");
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  dl.free();
   return ms / reps;
 }
 
@@ -872,15 +871,6 @@ __global__ __launch_bounds__(kSweepThreads) void k_bwd_sweep(SMat S, int NP, int
     __hip_atomic_store(x + j * T + tid, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // write-through: what the waiting workgroups poll
     __hip_atomic_store(x + NP + j * T + tid, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // and its shadow copy
   }
-}
-
-// gtg_destroy: the handle's schedule streams and events
-void destroy_chol_streams(gtg_context& c) {
-  CholStreams& cs = c.cs;
-  if (cs.panel) (void)hipStreamDestroy(cs.panel);
-  if (cs.start) (void)hipEventDestroy(cs.start);
-  for (auto* v : {&cs.P, &cs.N}) { for (hipEvent_t e : *v) (void)hipEventDestroy(e); v->clear(); }
-  cs = CholStreams();
 }
 
 // y = L^-1 g sits in row 0 of the rhs tiles after the factorisation: gathered into a contiguous vector for the backward solve

@@ -15,6 +15,7 @@
 
 #include <string>
 #include <exception>
+#include <memory>
 #include <thread>
 #include <vector>
 
@@ -56,11 +57,23 @@ struct SMat {
 constexpr double kUnsupportedCheirality = 1024.0;
 enum { SC_ERROR = 0, SC_LIN0 = 1, SC_LIN1 = 2, SC_TRIAL_ERROR = 3, SC_DELTA_SQ = 4, SC_FAIL = 5, SC_TIMEOUT = 6, SC_UNSUPPORTED = 7, SC_COUNT = 8 };
 
+// One block of device memory, owned: released by the destructor (to the runtime, or to the process' cache of big blocks:
+// device_memory.hip), movable, not copyable.  free() releases early on purpose.  Never declare one at namespace scope or as
+// `static` / `thread_local`: its destructor would call the runtime during process teardown, when the runtime may be gone.
 template <class T>
 struct DevBuf {
   T* p = nullptr;
   size_t n = 0;
-  size_t cap = 0;                               // bytes of the allocation behind p (>= n elements: api.hip keeps and re-issues big blocks)
+  size_t cap = 0;                               // bytes of the allocation behind p (>= n elements: device_memory.hip keeps and re-issues big blocks)
+  DevBuf() = default;
+  ~DevBuf() { free(); }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n), cap(o.cap) { o.p = nullptr; o.n = 0; o.cap = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) { free(); p = o.p; n = o.n; cap = o.cap; o.p = nullptr; o.n = 0; o.cap = 0; }
+    return *this;
+  }
   void alloc(size_t count);
   void upload(const T* host, size_t count, hipStream_t s);
   void free();
@@ -153,10 +166,22 @@ struct CholStreams {
   hipStream_t panel = nullptr;    // high-priority stream of the serial panel chain (the bulk updates run on the handle's stream)
   hipEvent_t start = nullptr;
   std::vector<hipEvent_t> P, N;   // per column pair: rest(p) finished / chain of pair p finished
+  CholStreams() = default;
+  CholStreams(const CholStreams&) = delete;
+  CholStreams& operator=(const CholStreams&) = delete;
+  ~CholStreams() {
+    if (panel) (void)hipStreamDestroy(panel);
+    if (start) (void)hipEventDestroy(start);
+    for (auto* v : {&P, &N}) for (hipEvent_t e : *v) (void)hipEventDestroy(e);
+  }
 };
+struct HostIndex;   // analysis.h: host copy of the factor index arrays the symbolic analysis reads
 }  // namespace gt
 
+// Everything a handle owns is released by its destructor; gtg_destroy (api.hip) decides WHEN and on which device that runs.
 struct gtg_context {
+  gtg_context();
+  ~gtg_context();   // joins block_level_thread first (its closure writes into this object); both in device_memory.hip, where HostIndex is complete
   int device = 0;
   hipStream_t stream = nullptr;
   gt::CholStreams cs;
@@ -280,6 +305,7 @@ struct gtg_context {
   double chol_flops = 0, chol_flops_block = 0, lin_bytes = 0;
   std::thread block_level_thread;               // computes chol_flops_block beside / after analyze() (analysis.hip::join_block_level)
   std::exception_ptr block_level_err;
+  std::unique_ptr<gt::HostIndex> index;         // created on first use (analysis.hip::host_index)
 };
 
 namespace gt {

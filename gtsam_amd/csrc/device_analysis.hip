@@ -232,7 +232,7 @@ void device_schur_terms(gtg_context& c, DevBuf<int32_t>& d_pos, int nrv, const s
   c.n_pair_terms = total;
   c.pair_oa.alloc((size_t)std::max<int64_t>(total, 1)); c.pair_ob.alloc((size_t)std::max<int64_t>(total, 1));
   block_row.clear(); block_col.clear(); block_ptr.assign(1, 0);
-  if (total == 0) { d_pos.free(); d_cnt.free(); d_off.free(); d_dup.free(); scan_tmp.free(); c.pair_ptr.upload(block_ptr.data(), 1, s); c.pair_row.alloc(1); c.pair_col.alloc(1); return; }
+  if (total == 0) { d_pos.free(); c.pair_ptr.upload(block_ptr.data(), 1, s); c.pair_row.alloc(1); c.pair_col.alloc(1); return; }
   // one scratch allocation for everything that does not outlive the call (a dozen separate hipMalloc / hipFree of tens of
   // megabytes cost more than the kernels)
   const size_t N = (size_t)total;
@@ -243,7 +243,7 @@ void device_schur_terms(gtg_context& c, DevBuf<int32_t>& d_pos, int nrv, const s
   // summation order of the Schur complement --, then the runs of the sorted keys: primitives.hip)
   const size_t need_tmp = std::max(prim::sort_scratch_bytes(N), prim::runs_scratch_bytes(N));
   const size_t bytes = 3 * al(8 * N) + 4 * al(4 * N) + al(8 * (N + 1)) + al(16) + al(need_tmp) + al(4 * (size_t)nrv);
-  DevBuf<unsigned char> pool_buf; pool_buf.alloc(bytes);     // (through DevBuf: a block of this size is kept for the next handle, api.hip)
+  DevBuf<unsigned char> pool_buf; pool_buf.alloc(bytes);     // (through DevBuf: a block of this size is kept for the next handle, device_memory.hip)
   char* pool = reinterpret_cast<char*>(pool_buf.p);
   size_t at = 0;
   auto take = [&](size_t nbytes) { char* q = pool + at; at += al(nbytes); return q; };
@@ -280,8 +280,7 @@ void device_schur_terms(gtg_context& c, DevBuf<int32_t>& d_pos, int nrv, const s
   c.pair_ptr.alloc((size_t)nruns + 1);
   hc(hipMemcpyAsync(c.pair_ptr.p, pp, sizeof(int64_t) * ((size_t)nruns + 1), hipMemcpyDeviceToDevice, s), "D2D");
   hc(hipStreamSynchronize(s), "sync");
-  d_pos.free(); d_cnt.free(); d_off.free(); d_dup.free(); scan_tmp.free();
-  pool_buf.free();
+  d_pos.free();   // (the caller's: consumed here)
 }
 
 // The incidence lists of the analysis, on the device (see the file header).  In: the factor tables (c.f.*), c.var_type; up: the
@@ -332,15 +331,10 @@ void device_incidence_lists(gtg_context& c, const std::vector<int32_t>& red_pos,
   int64_t n_inc = 0;
   hc(hipMemcpyAsync(&n_inc, c.red_inc_ptr.p + nrv, sizeof(int64_t), hipMemcpyDeviceToHost, s), "D2H");
   hc(hipStreamSynchronize(s), "sync");
-  if (h_bad) {
-    pool_buf.free(); d_red_pos.free();
-    throw std::invalid_argument(h_bad == 1 ? "GeneralSFMFactor keys must be (SFM_CAMERA, POINT3)" : "GenericProjectionFactor keys must be (POSE3, POINT3)");
-  }
+  if (h_bad) throw std::invalid_argument(h_bad == 1 ? "GeneralSFMFactor keys must be (SFM_CAMERA, POINT3)" : "GenericProjectionFactor keys must be (POSE3, POINT3)");
   c.red_inc_kind.alloc((size_t)std::max<int64_t>(n_inc, 1)); c.red_inc_idx.alloc((size_t)std::max<int64_t>(n_inc, 1));
   hipLaunchKernelGGL(k_da_inc_decode, grid(n_inc), dim3(256), 0, s, n_inc, n_sfm, n_proj, n_btw, val2, c.red_inc_kind.p, c.red_inc_idx.p);
   hc(hipStreamSynchronize(s), "sync");
-  pool_buf.free();
-  d_red_pos.free();
 }
 
 // After the ordering: blocks whose row variable is now placed EARLIER than their column variable change orientation (c.pair_row / c.pair_col
@@ -351,7 +345,6 @@ void device_orient_blocks(gtg_context& c, int64_t n_blocks, const std::vector<in
   hipLaunchKernelGGL(k_da_orient, dim3((unsigned)((n_blocks + 3) / 4)), dim3(256), 0, c.stream, n_blocks, d_pos.p, c.pair_row.p, c.pair_col.p, c.pair_ptr.p,
                      c.pair_oa.p, c.pair_ob.p);
   check_hip(hipStreamSynchronize(c.stream), "sync");
-  d_pos.free();
 }
 
 // ---- the marks of the Schur blocks in the tile / strip structure of the reduced system (after the ordering) ---------------------------
@@ -395,7 +388,6 @@ void device_tile_marks(gtg_context& c, int64_t n_blocks, const std::vector<RedLa
   hipStream_t s = c.stream;
   const size_t b_t1 = ((size_t)nt * nt + 255) & ~(size_t)255, b_m16 = (size_t)n16 * w16 * 8, b_lay = (layout.size() * sizeof(RedLayout) + 255) & ~(size_t)255;
   DevBuf<unsigned char> ws; ws.alloc(b_t1 + b_m16 + 256 + b_lay);
-  struct Release { DevBuf<unsigned char>& b; ~Release() { b.free(); } } release{ws};
   unsigned char* d_t1 = ws.p;
   unsigned long long* d_m16 = reinterpret_cast<unsigned long long*>(ws.p + b_t1);
   unsigned long long* d_sum = reinterpret_cast<unsigned long long*>(ws.p + b_t1 + b_m16);

@@ -216,7 +216,6 @@ bool device_rcm(gtg_context& c, int n, const std::vector<int32_t>& ea, const std
   // (the workspace is released on every path; a HIP error inside -- an illegal key, a failed allocation, a driver error -- makes this
   // function return false, as its contract says: the caller then runs the host ordering instead of failing the upload)
   DevBuf<unsigned char> ws;
-  struct Release { DevBuf<unsigned char>& b; ~Release() { b.free(); } } release{ws};
   int32_t status = 1;
   try {
   ws.alloc(off);

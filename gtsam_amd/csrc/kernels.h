@@ -59,7 +59,6 @@ void launch_smart_hdiag(gtg_context& c);
 void launch_smart_lin1(gtg_context& c);
 void exchange_sum(gtg_context& c, double* ptr, int64_t n);   // api.hip: all-reduce (sum) over the shards on the handle's stream; no-op on one shard
 void launch_backward_solve(gtg_context& c, SMat S, int NP, const CholPlan& plan, const double* Xinv, double* x, double* fail);
-void destroy_chol_streams(gtg_context& c);
 
 // chol_dataflow.hip -----------------------------------------------------------------------------------
 // The same factorisation as one dataflow pass of two persistent kernels (default schedule).  tile_struct = lower-triangular
@@ -71,7 +70,6 @@ void build_df_plan_host(DfPlan& df, int nt, const std::vector<uint8_t>* tile_str
                         const std::vector<int32_t>* tile_part = nullptr, const std::vector<int32_t>* part_parent = nullptr);
 void upload_df_plan(DfPlan& df, hipStream_t s, const std::vector<int32_t>& slot, int64_t n_slots, const std::vector<uint64_t>* sub16 = nullptr,
                     const int32_t* d_slot = nullptr);   // the device half (d_slot: the device copy of `slot` -- the tables are resolved by a kernel then)
-void free_df_plan(DfPlan& df);
 void df_prepare_streams_async(int device, int n_chain);   // the masked stream pair of a plan with n_chain chain workgroups, created on a helper thread ahead of the first factorisation
 void df_join_prepared();                                       // (joined by the first factorisation and by gtg_destroy)
 bool dataflow_schedule_selected();   // false: GTG_CHOL=streams (the stream / event schedule of cholesky.hip, the A/B of the dataflow pass)
@@ -83,7 +81,20 @@ void launch_cholesky_df(gtg_context& c, SMat S, int NP, DfPlan& df, double* Xinv
 int launch_pcg(gtg_context& c, double lambda, int diag, double dmin, double dmax, int max_iterations, int min_iterations,
                double epsilon_rel, double epsilon_abs, double* gamma0, double* gamma_end);
 
+// device_memory.hip --------------------------------------------------------------------------------
 void check_hip(hipError_t e, const char* what);
+struct DeviceGuard {     // an entry point's scope on the handle's device; the caller's current device is restored behind it
+  int prev = -1;
+  explicit DeviceGuard(int dev);
+  ~DeviceGuard();
+};
+size_t release_kept(int dev);   // the cache of big device blocks behind DevBuf: hands the kept blocks of a device (< 0: of every device) back, returns their bytes
+size_t kept_bytes();
+// a handle's stream, copy stream and phase events, which outlive it (parked per device for the next gtg_create)
+struct ParkedQueue { int device; hipStream_t stream; hipStream_t copy_stream; std::vector<hipEvent_t> events; };
+bool take_parked(gtg_context& c);
+bool park_queue(ParkedQueue& q);   // false: not kept (the caller destroys the streams and events)
+void destroy_parked();
 
 // gtg_prewarm (api.hip): every translation unit with kernels registers a function that makes the runtime load the unit's code object and
 // create the function objects of its kernels (hipFuncGetAttributes does both, without a launch) -- the work a kernel's FIRST launch

@@ -115,6 +115,18 @@ def test_three_shards_and_pose_graph_layouts(stub):
     assert all(r["ok"] and r["structure_hash"] == single["structure_hash"] for r in recs)
 
 
+# content the upload must reject (the reference's exceptions): each changes a good problem `q` in place
+_REJECTED = r'''
+def wrong_dim(q): q.noise_dim = q.noise_dim.copy(); q.noise_dim[q.sfm_noise[0]] = 3
+def bad_key(q): q.sfm_point = q.sfm_point.copy(); q.sfm_point[0] = 10 ** 6
+def cam_as_point(q): q.sfm_point = q.sfm_point.copy(); q.sfm_point[0] = q.sfm_cam[0]
+def bad_type(q): q.var_type = q.var_type.copy(); q.var_type[0] = 17
+def bad_noise(q): q.noise_kind = q.noise_kind.copy(); q.noise_kind[0] = 9
+def bad_estimator(q): q.noise_robust = np.full(q.noise_kind.size, 2, np.int32); q.noise_robust_param = np.zeros(q.noise_kind.size)
+REJECTED = [("wrong_dim", wrong_dim), ("bad_key", bad_key), ("cam_as_point", cam_as_point), ("bad_type", bad_type),
+            ("bad_noise", bad_noise), ("bad_estimator", bad_estimator)]
+'''
+
 _PROTOCOL = r'''
 import ctypes as C, json
 import numpy as np
@@ -150,14 +162,8 @@ out["values_size_null"] = int(lib.gtg_values_size(None))
 # --- content the upload must reject (the reference's exceptions) --------------------------------------
 def variant(fn):
     q, _ = bal_problem(*D.synthetic_bal(6, 40, seed=1)); fn(q); hh, rc, e = upload(q); lib.gtg_destroy(hh); return [rc, e]
-def wrong_dim(q): q.noise_dim = q.noise_dim.copy(); q.noise_dim[q.sfm_noise[0]] = 3
-def bad_key(q): q.sfm_point = q.sfm_point.copy(); q.sfm_point[0] = 10 ** 6
-def cam_as_point(q): q.sfm_point = q.sfm_point.copy(); q.sfm_point[0] = q.sfm_cam[0]
-def bad_type(q): q.var_type = q.var_type.copy(); q.var_type[0] = 17
-def bad_noise(q): q.noise_kind = q.noise_kind.copy(); q.noise_kind[0] = 9
-def bad_estimator(q): q.noise_robust = np.full(q.noise_kind.size, 2, np.int32); q.noise_robust_param = np.zeros(q.noise_kind.size)
-for name, fn in [("wrong_dim", wrong_dim), ("bad_key", bad_key), ("cam_as_point", cam_as_point), ("bad_type", bad_type),
-                 ("bad_noise", bad_noise), ("bad_estimator", bad_estimator)]:
+''' + _REJECTED + r'''
+for name, fn in REJECTED:
     out[name] = variant(fn)
 hh, rc, e = upload(good, shard=2, n=2); out["bad_shard"] = [rc, e]; lib.gtg_destroy(hh)
 hh, rc, e = upload(good, shard=0, n=2); lib.gtg_set_values(hh, v0.ctypes.data, v0.size)
@@ -246,7 +252,7 @@ print("RESULT " + json.dumps(out))
 
 
 def test_big_device_blocks_are_kept_for_the_next_handle(stub):
-    """api.hip keeps released device blocks of >= 16 MB for the next handle of the process (GTG_ALLOC_CACHE_MB per device, default
+    """device_memory.hip keeps released device blocks of >= 16 MB for the next handle of the process (GTG_ALLOC_CACHE_MB per device, default
     2048, 0 = off): with it the second construction of the same problem asks the runtime for less memory, a block is only re-issued
     for a request of 80 - 100 % of its size, and gtg_release_cached_memory() gives everything back; switched off, every
     construction allocates the same."""
@@ -276,3 +282,86 @@ print("RESULT " + json.dumps({"reduced_dim": np_, "marks": marks, "released": re
     assert second <= first - (16 << 20) and again <= first - (16 << 20)   # with the cache the big blocks are re-issued ...
     assert small == m0                                          # ... but not to a much smaller problem
     assert on["released"] >= 16 << 20                           # and the release call hands them back
+
+
+_LIFECYCLE = r'''
+import ctypes as C, json
+import numpy as np
+from gtsam_amd import lib as L
+from gtsam_amd.problem import bal_problem
+from gtsam_amd import datasets as D
+from tools import host_profile as HP
+from tests import problems as PB
+stub = C.CDLL(HP.STUB); stub.hipstub_live_bytes.restype = C.c_longlong; stub.hipstub_live_blocks.restype = C.c_longlong
+lib = L.load()
+lib.gtg_debug_syrk_ms.restype = C.c_double; lib.gtg_debug_syrk_ms.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+lib.gtg_debug_potrf_stamps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+start = (int(stub.hipstub_live_bytes()), int(stub.hipstub_live_blocks()))
+left = {}
+def scenario(fn):
+    fn()
+    lib.gtg_release_cached_memory()
+    left[fn.__name__] = [int(stub.hipstub_live_bytes()) - start[0], int(stub.hipstub_live_blocks()) - start[1]]
+def iterate(g, v0, pcg=True):
+    g.set_values(v0); g.linearize(); g.try_lambda(1e-3, True)
+    if pcg: g.try_lambda_pcg(1e-3, True, max_iterations=5)
+bal, bal_v0 = bal_problem(*D.synthetic_bal(20, 600, seed=4))
+pose, pose_v0 = HP.problem_for("sphere2500")
+def bal_iteration():
+    g = L.DeviceGraph(bal); iterate(g, bal_v0); g.accept(); g.close()
+def pose_graph_iteration():
+    g = L.DeviceGraph(pose); iterate(g, pose_v0); g.close()
+def smart_iteration():
+    p, v0 = PB.SMART["smart_far_infinity"](); g = L.DeviceGraph(p); iterate(g, v0); g.close()
+def reupload_smart_then_plain():
+    p, v0 = PB.SMART["smart_orbit"](); g = L.DeviceGraph(p); iterate(g, v0, pcg=False)
+    cp = bal.to_ctypes(); assert lib.gtg_upload_problem(g.h, C.byref(cp), 0, 1) == 0
+    assert lib.gtg_set_values(g.h, bal_v0.ctypes.data, bal_v0.size) == 0 and lib.gtg_linearize(g.h) == 0
+    g.close()
+def reordering_analyses_again():
+    g = L.DeviceGraph(bal)
+    order = np.arange(20, dtype=np.int32)[::-1].copy()
+    assert lib.gtg_set_reduced_ordering(g.h, order.ctypes.data, order.size) == 0
+    iterate(g, bal_v0); g.close()
+''' + _REJECTED + r'''
+def rejected_uploads():
+    for name, fn in REJECTED:
+        q, _ = bal_problem(*D.synthetic_bal(6, 40, seed=1)); fn(q)
+        h = C.c_void_p(); assert lib.gtg_create(C.byref(h), 0) == 0
+        cp = q.to_ctypes(); assert lib.gtg_upload_problem(h, C.byref(cp), 0, 1) == -1, name
+        assert lib.gtg_destroy(h) == 0
+def two_shards_in_one_process():
+    def lockstep(ptr, n, stream):
+        buf = np.frombuffer((C.c_double * n).from_address(ptr), dtype=np.float64); buf *= 2
+    gs = [L.DeviceGraph(bal, shard=k, n_shards=2, allreduce=lockstep) for k in range(2)]
+    for g in gs: iterate(g, bal_v0, pcg=False)
+    for g in gs: g.close()
+def dense_cholesky_with_and_without_rhs():
+    g = L.DeviceGraph(bal)
+    for n, with_rhs in [(100, False), (300, True), (128, True)]:
+        A = np.eye(n) * 4.0; rhs = np.ones(n)
+        assert lib.gtg_dense_cholesky_host(g.h, A.ctypes.data, n, rhs.ctypes.data if with_rhs else None) == 0
+    g.close()
+def allocating_debug_getters():
+    g = L.DeviceGraph(bal); g.set_values(bal_v0); g.linearize()
+    g.jacobians(0)                               # the GeneralSFM records of a fused graph are recomputed into a buffer of the call
+    A = np.eye(128) * 4.0; stamps = np.zeros(16, np.int64)
+    assert lib.gtg_debug_potrf_stamps(g.h, A.ctypes.data, stamps.ctypes.data) == 0
+    assert lib.gtg_debug_syrk_ms(g.h, 2, 0, 1) >= 0.0
+    g.close()
+for fn in [bal_iteration, pose_graph_iteration, smart_iteration, reupload_smart_then_plain, reordering_analyses_again, rejected_uploads,
+           two_shards_in_one_process, dense_cholesky_with_and_without_rhs, allocating_debug_getters]:
+    scenario(fn)
+print("RESULT " + json.dumps({"start": start, "left": left}))
+'''
+
+
+def test_handle_lifecycle_leaves_no_device_memory(stub):
+    """Every byte of device memory a handle (or a call) took is back with the runtime once the handle is destroyed and the cache of
+    big blocks is released: the stub counts live bytes and live blocks, and after each scenario -- iterations on a BAL problem, a
+    pose graph and a smart-factor problem, a second upload on one handle, a second analysis after gtg_set_reduced_ordering, every
+    rejected upload of the protocol test, two shards in one process, gtg_dense_cholesky_host with and without a right-hand side,
+    the debug getters that allocate -- both are exactly what they were before the first handle."""
+    r = HP.run_snippet(_LIFECYCLE)
+    assert len(r["left"]) == 9
+    assert r["left"] == {name: [0, 0] for name in r["left"]}, r

@@ -7,7 +7,8 @@
  * only counts), so nothing numeric comes out of a process that runs under it -- it is not a CPU fallback.
  *
  * The entry points are the ones `nm -D --undefined-only gtsam_amd/lib/libgtsam_amd.so | grep hip` lists.
- * Counters: hipstub_launches(), hipstub_bytes_h2d(), hipstub_allocated() (plain C, read through ctypes).
+ * Counters: hipstub_launches(), hipstub_bytes_h2d(), hipstub_allocated() (cumulative), hipstub_live_bytes() / hipstub_live_blocks()
+ * (allocated and not yet freed) (plain C, read through ctypes).
  */
 #include <stddef.h>
 #include <stdint.h>
@@ -20,7 +21,7 @@ typedef void* hipStream_t;
 typedef void* hipEvent_t;
 typedef struct { unsigned x, y, z; } dim3s;
 
-static long long g_launches, g_h2d, g_alloc, g_streams, g_events;
+static long long g_launches, g_h2d, g_alloc, g_live_bytes, g_live_blocks, g_streams, g_events;
 
 /* every host-to-device copy is recorded as (bytes, FNV-1a hash of the bytes): two builds of the library that produce the same
  * multiset of records for the same problem have uploaded identical tables (tests/test_host_analysis.py) */
@@ -68,6 +69,8 @@ static hipstub_op* trace(int type, void* stream, const void* obj) {
 long long hipstub_launches(void) { return g_launches; }
 long long hipstub_bytes_h2d(void) { return g_h2d; }
 long long hipstub_allocated(void) { return g_alloc; }
+long long hipstub_live_bytes(void) { return __atomic_load_n(&g_live_bytes, __ATOMIC_RELAXED); }
+long long hipstub_live_blocks(void) { return __atomic_load_n(&g_live_blocks, __ATOMIC_RELAXED); }
 void hipstub_reset(void) { g_launches = 0; g_h2d = 0; g_nrec = 0; }
 
 static double now_ms(void) {
@@ -131,13 +134,27 @@ hipError_t hipGetDevicePropertiesR0600(void* prop, int dev) {
 }
 
 /* ---- memory ---- */
+/* every block carries its size in a header in front of it (HIPSTUB_HDR bytes: the block keeps malloc's alignment), for the live counters */
+#define HIPSTUB_HDR 16
 hipError_t hipMalloc(void** p, size_t n) {
-  *p = calloc(n ? n : 1, 1);
+  char* q = (char*)calloc(HIPSTUB_HDR + (n ? n : 1), 1);
+  if (!q) { *p = NULL; return 2; }
+  *(size_t*)q = n;
+  *p = q + HIPSTUB_HDR;
   __atomic_add_fetch(&g_alloc, (long long)n, __ATOMIC_RELAXED);
-  return *p ? 0 : 2;
+  __atomic_add_fetch(&g_live_bytes, (long long)n, __ATOMIC_RELAXED);
+  __atomic_add_fetch(&g_live_blocks, 1, __ATOMIC_RELAXED);
+  return 0;
 }
 hipError_t hipExtMallocWithFlags(void** p, size_t n, unsigned flags) { (void)flags; return hipMalloc(p, n); }
-hipError_t hipFree(void* p) { free(p); return 0; }
+hipError_t hipFree(void* p) {
+  if (!p) return 0;
+  char* q = (char*)p - HIPSTUB_HDR;
+  __atomic_sub_fetch(&g_live_bytes, (long long)*(size_t*)q, __ATOMIC_RELAXED);
+  __atomic_sub_fetch(&g_live_blocks, 1, __ATOMIC_RELAXED);
+  free(q);
+  return 0;
+}
 hipError_t hipMemcpy(void* d, const void* s, size_t n, int kind) {
   memcpy(d, s, n);
   if (kind == 1) { __atomic_add_fetch(&g_h2d, (long long)n, __ATOMIC_RELAXED); record_h2d(s, n); }

@@ -8,16 +8,20 @@
 set -e
 ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 RT=$(dirname "$(/opt/rocm/lib/llvm/bin/clang -print-file-name=libclang_rt.asan-x86_64.so)")
-WORK=${WORK:-edge bal:60:6000:7 bal:300:20000:3 sphere2500 ladybug1723}
+WORK=${WORK:-edge threads bal:60:6000:7 bal:300:20000:3 sphere2500 ladybug1723}
 [ $# -gt 0 ] && WORK="$*"
 gcc -O2 -fPIC -shared -o "$ROOT/tools/hipstub/libhipstub.so" "$ROOT/tools/hipstub/hipstub.c"
 for SAN in address thread; do
   OUT=/tmp/gtsam_amd_$SAN; mkdir -p $OUT
-  for f in api cholesky assemble factors pcg; do
+  rm -f $OUT/*.o
+  for src in "$ROOT"/gtsam_amd/csrc/*.hip; do
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -Xarch_host -fsanitize=$SAN -Xarch_host -fno-omit-frame-pointer \
-        -c "$ROOT/gtsam_amd/csrc/$f.hip" -o $OUT/$f.o 2>/dev/null
+        -c "$src" -o $OUT/$(basename "$src" .hip).o 2>/dev/null &
   done
-  /opt/rocm/bin/hipcc -O1 -g -std=c++17 -fPIC -fsanitize=$SAN -c "$ROOT/gtsam_amd/csrc/io.cpp" -o $OUT/io.o 2>/dev/null
+  for src in "$ROOT"/gtsam_amd/csrc/*.cpp; do
+    /opt/rocm/bin/hipcc -O1 -g -std=c++17 -fPIC -fsanitize=$SAN -c "$src" -o $OUT/$(basename "$src" .cpp).o 2>/dev/null &
+  done
+  wait
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Xarch_host -fsanitize=$SAN -o $OUT/libgtsam_amd.so $OUT/*.o 2>/dev/null
   if [ $SAN = address ]; then LIBRT=$RT/libclang_rt.asan-x86_64.so; else LIBRT=$RT/libclang_rt.tsan-x86_64.so; fi
   for ND in "" 2; do

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Drives the HOST code of the library (upload + symbolic analysis, one linearize / try_lambda / PCG issue sequence, plan
-getters; single handle and two shards) under tools/hipstub with a sanitizer-instrumented build: tools/sanitize/host_sanitizers.sh.
+getters; single handle and two shards; handles created and destroyed from several threads at once) under tools/hipstub with a sanitizer-instrumented build: tools/sanitize/host_sanitizers.sh.
 Development tool; nothing numeric is computed (kernels do not run under the stub)."""
 import ctypes, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -35,9 +35,27 @@ def edge_cases():
         p, v0 = bal_problem(*D.synthetic_bal(nc, 200, seed=nc)); run(f"bal {nc} cameras", p, v0)
 
 
+def threads():
+    """Handles created, used and destroyed from four host threads at once: the cache of big blocks, the parked streams and the
+    per-device lock of gtg_destroy are shared by all of them (bal:300:20000:3 has blocks above the cache's 16 MB threshold)."""
+    import threading
+    problems = [HP.problem_for(w) for w in ("bal:300:20000:3", "bal:20:600:4")]
+    def work(k):
+        for rep in range(3):
+            p, v0 = problems[(k + rep) % 2]
+            g = L.DeviceGraph(p); g.set_values(v0); g.linearize(); g.try_lambda(1e-3, True); g.accept(); g.close()
+    ts = [threading.Thread(target=work, args=(k,)) for k in range(4)]
+    for t in ts: t.start()
+    for t in ts: t.join()
+    L.load().gtg_release_cached_memory()
+    print("ok threads", flush=True)
+
+
 for w in sys.argv[1:]:
     if w == "edge":
         edge_cases(); continue
+    if w == "threads":
+        threads(); continue
     nd = None
     problem, v0 = HP.problem_for(w)
     for shards in (1, 2):
