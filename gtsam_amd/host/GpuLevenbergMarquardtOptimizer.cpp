@@ -52,11 +52,12 @@
 #include <iomanip>
 #include <iostream>
 #include <limits>
-#include <algorithm>
 #include <map>
 #include <new>
 #include <stdexcept>
 #include <thread>
+#include <type_traits>
+#include <typeinfo>
 
 using namespace gtsam;
 
@@ -99,37 +100,14 @@ struct GpuState : State {
   }
 };
 
-struct GpuLevenbergMarquardtOptimizer::Impl {
-  gtg_handle h = nullptr;
-  std::vector<Key> keys;                 // variable id -> Key (Values order: sorted)
-  int32_t idOf(Key k) const {            // Key -> variable id: binary search over the sorted, contiguous keys
-    auto it = std::lower_bound(keys.begin(), keys.end(), k);
-    if (it == keys.end() || *it != k) throw ValuesKeyDoesNotExist("GpuLevenbergMarquardtOptimizer", k);
-    return (int32_t)(it - keys.begin());
-  }
-  std::vector<int32_t> var_type;
-  std::vector<int64_t> val_off;
-  std::vector<double> packed;            // host copy of the packed values
-  Values scratch;                        // the deep copy of the caller's Values (made beside the extraction); swapped into the State at the end of init
-  std::vector<Value*> slots;             // variable id -> the GenericValue object of that variable inside the State's Values (heap objects
-                                         // owned by the map's nodes: they stay where they are when the map is swapped into the next State)
-  const Values* published = nullptr;     // the Values object (inside the State THIS class published last) whose nodes `slots` point into:
-                                         // checked before every write through `slots` (adoptStateIfForeign)
-  std::vector<std::pair<int32_t, int64_t>> fac_map;   // factor of graph_ -> (GTG_FAC_*, index in that type's table); (-1, 0): null
-  std::vector<int64_t> dim_off;          // variable id -> offset in the tangent vector (delta)
-  bool keep_linearization = false;       // iterate(): download the records right after gtg_linearize
-  GaussianFactorGraph::shared_ptr linearization;
-  bool host_values_stale = false;
-  // device-side copies of the LM state while optimize() keeps Values on the GPU
-  double error = 0, lambda = 0, factor = 0;
-  size_t iterations = 0; int inner = 0;
-  std::chrono::high_resolution_clock::time_point start = std::chrono::high_resolution_clock::now();   // logFile's seconds column
-  ~Impl() { if (h) gtg_destroy(h); }
-};
-
 namespace {
-void check(int rc, const char* what) {
-  if (rc < 0) throw std::runtime_error(std::string(what) + ": " + gtg_last_error());
+void check(int rc, const char* what) { if (rc < 0) throw std::runtime_error(std::string(what) + ": " + gtg_last_error()); }
+// Key -> variable id: the keys are sorted, so a binary search over the contiguous array (a std::map of 158 000 keys cost 0.2 s of
+// pointer chasing for the 1.35 M lookups of the L1723 shape)
+int32_t idOf(const std::vector<Key>& keys, Key k) {
+  auto it = std::lower_bound(keys.begin(), keys.end(), k);
+  if (it == keys.end() || *it != k) throw ValuesKeyDoesNotExist("GpuLevenbergMarquardtOptimizer", k);
+  return (int32_t)(it - keys.begin());
 }
 void packPose(const Pose3& T, double* p) {
   const Matrix3 R = T.rotation().matrix();
@@ -146,7 +124,131 @@ void packCamera(const SfmCamera& c, double* p) {
   p[12] = c.calibration().fx(); p[13] = c.calibration().k1(); p[14] = c.calibration().k2();
   p[15] = c.calibration().px(); p[16] = c.calibration().py();
 }
+// ---- variable types (GTG_VAR_*), each fact once: which Values are of one, its storage size and tangent dimension, to doubles and back
+int32_t classify(const Value* v) {   // -1: a type outside the GPU path
+  return dynamic_cast<const GenericValue<Point3>*>(v) ? GTG_VAR_POINT3 : dynamic_cast<const GenericValue<SfmCamera>*>(v) ? GTG_VAR_SFM_CAMERA :
+         dynamic_cast<const GenericValue<Pose3>*>(v) ? GTG_VAR_POSE3 : dynamic_cast<const GenericValue<Pose2>*>(v) ? GTG_VAR_POSE2 : -1;
+}
+template <class T> struct VarTypeOf;
+template <> struct VarTypeOf<Pose3> { static constexpr int32_t value = GTG_VAR_POSE3; };
+template <> struct VarTypeOf<SfmCamera> { static constexpr int32_t value = GTG_VAR_SFM_CAMERA; };
+template <> struct VarTypeOf<Point3> { static constexpr int32_t value = GTG_VAR_POINT3; };
+template <> struct VarTypeOf<Pose2> { static constexpr int32_t value = GTG_VAR_POSE2; };
+constexpr int storageSize(int32_t t) { return t == GTG_VAR_POSE3 ? 12 : t == GTG_VAR_SFM_CAMERA ? 17 : 3; }
+constexpr int tangentDim(int32_t t) { return t == GTG_VAR_POSE3 ? 6 : t == GTG_VAR_SFM_CAMERA ? 9 : 3; }
+// an object of a variable's type (a value, a prior, a measurement) as storageSize() doubles; payload(): of a Value whose type the caller knows, no check
+void packAs(const Point3& q, double* p) { p[0] = q.x(); p[1] = q.y(); p[2] = q.z(); }
+void packAs(const Pose2& q, double* p) { p[0] = q.x(); p[1] = q.y(); p[2] = q.theta(); }
+void packAs(const Pose3& q, double* p) { packPose(q, p); }
+void packAs(const SfmCamera& q, double* p) { packCamera(q, p); }
+template <class T> const T& payload(const Value& v) { return static_cast<const GenericValue<T>&>(v).value(); }
+template <class T> T& payload(Value& v) { return static_cast<GenericValue<T>&>(v).value(); }
+void pack(int32_t t, const Value& v, double* p) {
+  if (t == GTG_VAR_POINT3) packAs(payload<Point3>(v), p);
+  else if (t == GTG_VAR_SFM_CAMERA) packAs(payload<SfmCamera>(v), p);
+  else if (t == GTG_VAR_POSE3) packAs(payload<Pose3>(v), p);
+  else packAs(payload<Pose2>(v), p);
+}
+void unpack(int32_t t, const double* p, Value& v) {
+  if (t == GTG_VAR_POINT3) payload<Point3>(v) = Point3(p[0], p[1], p[2]);
+  else if (t == GTG_VAR_SFM_CAMERA) payload<SfmCamera>(v) = SfmCamera(unpackPose(p), Cal3Bundler(p[12], p[13], p[14], p[15], p[16]));
+  else if (t == GTG_VAR_POSE3) payload<Pose3>(v) = unpackPose(p);
+  else payload<Pose2>(v) = Pose2(p[0], p[1], p[2]);
+}
+// ---- Jacobian records (gtg_get_jacobians): one whitened [A1 | A2 | b] per factor, row-major blocks at fixed offsets; the record's width follows
+// the factor type, the block sizes the factor's first variable (Pose2: 3x3 blocks inside the record of the Pose3 factor)
+const int64_t kRecordWidth[4] = {26, 20, 78, 90};   // by GTG_FAC_*
+struct RecordLayout { int rows, nblk, boff[2], bcols[2], rhs; int64_t width; };
+template <class F> RecordLayout recordLayout(int32_t fac, F&& firstVarType) {   // firstVarType(): GTG_VAR_* of the factor's first variable, asked only where the layout depends on it
+  const int64_t w = kRecordWidth[fac];
+  if (fac == GTG_FAC_GENERAL_SFM) return {2, 2, {0, 18}, {tangentDim(GTG_VAR_SFM_CAMERA), 3}, 24, w};
+  if (fac == GTG_FAC_PROJECTION) return {2, 2, {0, 12}, {tangentDim(GTG_VAR_POSE3), 3}, 18, w};
+  const int d = tangentDim(firstVarType());
+  if (fac == GTG_FAC_BETWEEN_POSE3) return {d, 2, {0, 36}, {d, d}, 72, w};
+  return {d, 1, {0, 0}, {d, 0}, 81, w};
+}
+typedef std::vector<std::pair<int32_t, int64_t>> FactorMap;   // factor of graph_ -> (GTG_FAC_*, index in that type's table); (-1, 0): null; (-2, i): smart factor i
+// The device's current records, one buffer per GTG_FAC_* (null and smart factors have none: a smart factor's linearisation is a Hessian factor the device never forms)
+struct Records {
+  std::vector<double> rec[4];
+  const double* of(const std::pair<int32_t, int64_t>& tf) const { return rec[tf.first].data() + tf.second * kRecordWidth[tf.first]; }
+};
+Records fetchRecords(gtg_handle h, const FactorMap& fac_map) {
+  Records out;
+  int64_t count[4] = {0, 0, 0, 0};
+  for (const auto& tf : fac_map) if (tf.first >= 0) count[tf.first]++;
+  for (int t = 0; t < 4; t++) {
+    if (!count[t]) continue;
+    out.rec[t].resize((size_t)(count[t] * kRecordWidth[t]));
+    check(gtg_get_jacobians(h, t, out.rec[t].data(), (int64_t)out.rec[t].size()), "gtg_get_jacobians");
+  }
+  return out;
+}
+// params.iterativeParams as the cg[4] of gtg_try_lambda_pcg (PCGSolverParameters only); `who` opens the text of the exception
+std::shared_ptr<PCGSolverParameters> pcgParameters(const NonlinearOptimizerParams& params, const char* who, double cg[4]) {
+  auto pcg = std::dynamic_pointer_cast<PCGSolverParameters>(params.iterativeParams);
+  if (!pcg) throw std::runtime_error(std::string(who) + ": only PCGSolverParameters are handled by the GPU path");
+  cg[0] = (double)pcg->maxIterations; cg[1] = (double)pcg->minIterations; cg[2] = pcg->epsilon_rel; cg[3] = pcg->epsilon_abs;
+  return pcg;
+}
+// ---- host threads.  Range t of nthreads over [0, n) is [cut(t), cut(t + 1)).
+size_t cut(size_t n, size_t nthreads, size_t t) { return n * t / nthreads; }
+struct Join { std::thread& t; ~Join() { if (t.joinable()) t.join(); } };
+struct JoinAll { std::vector<std::thread>& v; ~JoinAll() { for (auto& t : v) if (t.joinable()) t.join(); } };
+// starts fn(t, begin, end) on a thread of its own for the ranges t = first .. nthreads - 1; the caller owns (and joins) `pool`
+template <class F> void startRanges(std::vector<std::thread>& pool, size_t n, size_t nthreads, size_t first, F fn) {
+  for (size_t t = first; t < nthreads; t++) pool.emplace_back(fn, t, cut(n, nthreads, t), cut(n, nthreads, t + 1));
+}
+// fn(t, begin, end) for every range: range 0 on the calling thread, the others on threads that are joined on every way out
+template <class F> void parallelRanges(size_t n, size_t nthreads, F fn) {
+  std::vector<std::thread> pool;
+  JoinAll join{pool};
+  startRanges(pool, n, nthreads, 1, fn);
+  fn((size_t)0, cut(n, nthreads, 0), cut(n, nthreads, 1));
+}
+// GTG_HOST_THREADS, or the hardware's threads up to `cap` (every site has its own, measured)
+size_t hostThreads(unsigned cap) {
+  const char* env = std::getenv("GTG_HOST_THREADS");
+  return (size_t)(env ? std::max(1, std::atoi(env)) : (int)std::min(std::max(1u, std::thread::hardware_concurrency()), cap));
+}
+// GTG_DEBUG_TIMING: host-side breakdown of the construction on stderr, one line per lap
+struct Lap {
+  const bool on = std::getenv("GTG_DEBUG_TIMING") != nullptr;
+  std::chrono::high_resolution_clock::time_point prev = std::chrono::high_resolution_clock::now();
+  void operator()(const char* what) {
+    const auto now = std::chrono::high_resolution_clock::now();
+    if (on) std::fprintf(stderr, "[gtsam_amd shim ] %-46s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - prev).count());
+    prev = now;
+  }
+};
+}  // namespace
 
+struct GpuLevenbergMarquardtOptimizer::Impl {
+  gtg_handle h = nullptr;
+  std::vector<Key> keys;                 // variable id -> Key (Values order: sorted)
+  std::vector<int32_t> var_type;
+  std::vector<int64_t> val_off;
+  std::vector<double> packed;            // host copy of the packed values
+  Values scratch;                        // the deep copy of the caller's Values (made beside the extraction); swapped into the State at the end of init
+  std::vector<Value*> slots;             // variable id -> the GenericValue object of that variable inside the State's Values (heap objects
+                                         // owned by the map's nodes: they stay where they are when the map is swapped into the next State)
+  const Values* published = nullptr;     // the Values object (inside the State THIS class published last) whose nodes `slots` point into:
+                                         // checked before every write through `slots` (adoptStateIfForeign)
+  FactorMap fac_map;                     // by factor of graph_
+  std::vector<int64_t> dim_off;          // variable id -> offset in the tangent vector (delta)
+  bool keep_linearization = false;       // iterate(): download the records right after gtg_linearize
+  GaussianFactorGraph::shared_ptr linearization;
+  bool host_values_stale = false;
+  // device-side copies of the LM state while optimize() keeps Values on the GPU
+  double error = 0, lambda = 0, factor = 0;
+  size_t iterations = 0; int inner = 0;
+  std::chrono::high_resolution_clock::time_point start = std::chrono::high_resolution_clock::now();   // logFile's seconds column
+  ~Impl() { if (h) gtg_destroy(h); }
+  void takeScalars(const State& s) { error = s.error; lambda = s.lambda; factor = s.currentFactor; iterations = s.iterations; inner = s.totalNumberInnerIterations; }
+  RecordLayout layoutOf(const std::pair<int32_t, int64_t>& tf, Key first) const { return recordLayout(tf.first, [&] { return var_type[idOf(keys, first)]; }); }
+};
+
+namespace {
 struct NoiseTable {
   std::vector<int32_t> kind, dim, rkind; std::vector<int64_t> off; std::vector<double> data, rparam;
   std::map<const noiseModel::Base*, int32_t> seen;        // by object: the usual case of one shared_ptr on many factors
@@ -247,26 +349,276 @@ struct Extract {
   std::vector<int32_t> sfm_cam, sfm_pt, pj_pose, pj_pt, pj_sen, bt_1, bt_2, pr_var, sm_cam;
   std::vector<double> sfm_z, pj_z, sensor, bt_z, pr_data, sm_z, sm_prm;
   std::vector<int64_t> pr_off, sm_ptr;
-  std::vector<std::pair<int32_t, int64_t>> fac_map;                       // (type, index in THIS chunk's table of that type)
+  FactorMap fac_map;                                                        // (type, index in THIS chunk's table of that type)
   typedef std::vector<std::pair<int64_t, SharedNoiseModel>> Runs;
   Runs sfm_nz, pj_nz, bt_nz, pr_nz, sm_nz;
   std::vector<int32_t> bt_dim, pr_dim;                                      // expected noise dimension per between / prior factor
   std::vector<std::pair<const void*, int>> pj_cal;                          // calibration object per projection factor, 1 = Cal3DS2
-  std::exception_ptr err; size_t err_at = 0;
+  std::exception_ptr err;                                                   // what the chunk's first offending factor threw
   static void run(Runs& r, const SharedNoiseModel& nm) { if (!r.empty() && r.back().second.get() == nm.get()) r.back().first++; else r.emplace_back(1, nm); }
+  static double* grow(std::vector<double>& v, size_t n) { v.resize(v.size() + n); return v.data() + v.size() - n; }   // n more doubles, zero-filled
 };
+void addSfm(Extract& x, const SfmFactor& s, const std::vector<Key>& keys) {
+  x.fac_map.emplace_back(GTG_FAC_GENERAL_SFM, (int64_t)x.sfm_cam.size());
+  x.sfm_cam.push_back(idOf(keys, s.key1())); x.sfm_pt.push_back(idOf(keys, s.key2()));
+  x.sfm_z.push_back(s.measured().x()); x.sfm_z.push_back(s.measured().y());
+  Extract::run(x.sfm_nz, s.noiseModel());
+}
+// GenericProjectionFactor<Pose3, Point3, Cal3_S2>, or the same factor with a Cal3DS2 calibration (section 8(f) #3)
+template <class CAL> void addProjection(Extract& x, const GenericProjectionFactor<Pose3, Point3, CAL>& p, const std::vector<Key>& keys) {
+  x.fac_map.emplace_back(GTG_FAC_PROJECTION, (int64_t)x.pj_pose.size());
+  if (p.throwCheirality()) throw std::invalid_argument("GenericProjectionFactor with throwCheirality is not supported");
+  x.pj_pose.push_back(idOf(keys, p.key1())); x.pj_pt.push_back(idOf(keys, p.key2()));
+  x.pj_z.push_back(p.measured().x()); x.pj_z.push_back(p.measured().y());
+  Extract::run(x.pj_nz, p.noiseModel());
+  x.pj_cal.emplace_back(p.calibration().get(), std::is_same<CAL, Cal3DS2>::value ? 1 : 0);
+  if (p.body_P_sensor()) { x.pj_sen.push_back((int32_t)(x.sensor.size() / 12)); packPose(*p.body_P_sensor(), Extract::grow(x.sensor, 12)); }
+  else x.pj_sen.push_back(-1);
+}
+void addSmart(Extract& x, const SmartFactor& sf, const std::vector<Key>& keys) {
+  x.fac_map.emplace_back(-2, (int64_t)x.sm_prm.size() / 8);   // (no Jacobian record: its linearisation is a Hessian factor)
+  const SmartProjectionParams& sp = sf.*SmartAccess::params();
+  const TriangulationParameters& tp = sp.triangulation;
+  // HESSIAN, JACOBIAN_Q and JACOBIAN_SVD are the same normal equations (the device never forms the factor itself); an
+  // IMPLICIT_SCHUR factor cannot be eliminated by the reference's direct solvers either.  (throwCheirality / verboseCheirality
+  // are read by the pose-only smart factors, not by SmartProjectionFactor<CAMERA>.)
+  if (sp.linearizationMode == IMPLICIT_SCHUR) throw std::invalid_argument("SmartProjectionFactor: the IMPLICIT_SCHUR linearisation is not supported");
+  if (tp.useLOST) throw std::invalid_argument("SmartProjectionFactor: useLOST is not supported");
+  if (tp.enableEPI && tp.noiseModel) throw std::invalid_argument("SmartProjectionFactor: enableEPI with a noise model in the triangulation parameters is not supported");
+  const SharedIsotropic& iso = sf.*SmartAccess::noise();
+  Extract::run(x.sm_nz, iso);
+  const auto& zs = sf.measured();
+  if (zs.size() != sf.keys().size() || zs.empty()) throw std::invalid_argument("SmartProjectionFactor: measurements and keys do not match");
+  for (size_t k = 0; k < zs.size(); k++) { x.sm_cam.push_back(idOf(keys, sf.keys()[k])); x.sm_z.push_back(zs[k].x()); x.sm_z.push_back(zs[k].y()); }
+  x.sm_ptr.push_back((int64_t)x.sm_cam.size());
+  x.sm_prm.insert(x.sm_prm.end(), {tp.rankTolerance, tp.landmarkDistanceThreshold, tp.dynamicOutlierRejectionThreshold, sp.retriangulationThreshold,
+                                   sp.degeneracyMode == ZERO_ON_DEGENERACY ? 1.0 : (sp.degeneracyMode == HANDLE_INFINITY ? 2.0 : 0.0),
+                                   sp.linearizationMode == JACOBIAN_Q ? 2.0 : (sp.linearizationMode == JACOBIAN_SVD ? 3.0 : 0.0), tp.enableEPI ? 1.0 : 0.0, 0.0});
+}
+// BetweenFactor<Pose3>, and <Pose2> in the same table: the factor's type follows from its variables', (x, y, theta) in the first 3 of the 12 doubles
+template <class T> void addBetween(Extract& x, const BetweenFactor<T>& b, const std::vector<Key>& keys) {
+  x.fac_map.emplace_back(GTG_FAC_BETWEEN_POSE3, (int64_t)x.bt_1.size());
+  x.bt_1.push_back(idOf(keys, b.key1())); x.bt_2.push_back(idOf(keys, b.key2()));
+  packAs(b.measured(), Extract::grow(x.bt_z, 12));
+  Extract::run(x.bt_nz, b.noiseModel()); x.bt_dim.push_back(tangentDim(VarTypeOf<T>::value));
+}
+template <class T> void addPrior(Extract& x, const PriorFactor<T>& q, const std::vector<Key>& keys) {
+  x.fac_map.emplace_back(GTG_FAC_PRIOR, (int64_t)x.pr_var.size());
+  x.pr_var.push_back(idOf(keys, q.key())); x.pr_off.push_back((int64_t)x.pr_data.size());
+  packAs(q.prior(), Extract::grow(x.pr_data, storageSize(VarTypeOf<T>::value)));
+  Extract::run(x.pr_nz, q.noiseModel()); x.pr_dim.push_back(tangentDim(VarTypeOf<T>::value));
+}
+void addFactor(Extract& x, const NonlinearFactor* f, const std::vector<Key>& keys) {
+  if (auto s = dynamic_cast<const SfmFactor*>(f)) addSfm(x, *s, keys);
+  else if (auto p = dynamic_cast<const ProjFactor*>(f)) addProjection(x, *p, keys);
+  else if (auto pd = dynamic_cast<const ProjFactorDS2*>(f)) addProjection(x, *pd, keys);
+  else if (auto sf = dynamic_cast<const SmartFactor*>(f)) addSmart(x, *sf, keys);
+  else if (auto bb = dynamic_cast<const BetweenFactor<Pose3>*>(f)) addBetween(x, *bb, keys);
+  else if (auto b2 = dynamic_cast<const BetweenFactor<Pose2>*>(f)) addBetween(x, *b2, keys);
+  else if (auto q2 = dynamic_cast<const PriorFactor<Pose2>*>(f)) addPrior(x, *q2, keys);
+  else if (auto pp = dynamic_cast<const PriorFactor<Pose3>*>(f)) addPrior(x, *pp, keys);
+  else if (auto pc = dynamic_cast<const PriorFactor<SfmCamera>*>(f)) addPrior(x, *pc, keys);
+  else if (auto p3 = dynamic_cast<const PriorFactor<Point3>*>(f)) addPrior(x, *p3, keys);
+  else throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: factor type outside the GPU hot path "   // (anything else is a hard error)
+                                   "(supported: GeneralSFMFactor<SfmCamera,Point3>, GenericProjectionFactor<Pose3,Point3,Cal3_S2|Cal3DS2>, "
+                                   "SmartProjectionFactor<SfmCamera>, BetweenFactor<Pose3|Pose2>, PriorFactor<Pose3|Pose2|SfmCamera|Point3>)");
+}
+// The factors [b, e) of `graph` into x, each pointer also copied into `graphCopy`; the chunk stops at its first offending factor and keeps what that threw.
+void extractChunk(Extract& x, const NonlinearFactorGraph& graph, NonlinearFactorGraph& graphCopy, const std::vector<Key>& keys, size_t b, size_t e) {
+  x.fac_map.reserve(e - b);
+  x.sm_ptr.push_back(0);
+  // (a chunk is nearly always one kind of factor: room for that kind up front -- vectors that grow by doubling go through mmap / munmap
+  // above 128 KB, and 16 threads doing that held up the thread that deep-copies the Values: it was the last thing the constructor
+  // waited for, 7 ms with 32 extraction threads, 0.3 ms with 16 -- round 6, L1723 shape)
+  if (b < e && graph.begin()[b]) {
+    const NonlinearFactor* f0 = graph.begin()[b].get();
+    if (dynamic_cast<const SfmFactor*>(f0)) { x.sfm_cam.reserve(e - b); x.sfm_pt.reserve(e - b); x.sfm_z.reserve(2 * (e - b)); }
+    else if (dynamic_cast<const ProjFactor*>(f0) || dynamic_cast<const ProjFactorDS2*>(f0)) { x.pj_pose.reserve(e - b); x.pj_pt.reserve(e - b); x.pj_sen.reserve(e - b); x.pj_z.reserve(2 * (e - b)); x.pj_cal.reserve(e - b); }
+    else if (dynamic_cast<const BetweenFactor<Pose3>*>(f0) || dynamic_cast<const BetweenFactor<Pose2>*>(f0)) { x.bt_1.reserve(e - b); x.bt_2.reserve(e - b); x.bt_z.reserve(12 * (e - b)); x.bt_dim.reserve(e - b); }
+  }
+  try {
+    for (size_t i = b; i < e; i++) {
+      const auto& f = (graphCopy.at(i) = graph.begin()[i]);   // (graph[i] returns a COPY of the pointer: two more atomic operations per factor)
+      if (f) addFactor(x, f.get(), keys); else x.fac_map.emplace_back(-1, 0);
+    }
+  } catch (...) { x.err = std::current_exception(); }
+}
+// ---- the merged tables.  The GeneralSFM tables -- 30 MB on the L1723 shape -- are plain buffers, not value-initialised: threads fill them (mergeTables)
+template <class T> struct Raw {
+  std::unique_ptr<T[]> p; size_t n = 0;
+  void alloc(size_t k) { p.reset(new T[k ? k : 1]); n = k; }
+  T* data() const { return p.get(); } size_t size() const { return n; }
+};
+typedef Raw<int32_t> RawI; typedef Raw<double> RawD;
+struct Place { int64_t o_sfm, o_pj, o_bt, o_pr, o_sm; std::vector<std::pair<int64_t, int32_t>> sfm_rows; };   // per chunk: offsets of its tables, (count, noise row) of its GeneralSFM runs
+struct HostProblem {
+  NoiseTable nt;
+  RawI sfm_cam, sfm_pt, sfm_nz;
+  RawD sfm_z;
+  std::vector<int32_t> pj_pose, pj_pt, pj_nz, pj_cal, pj_sen, bt_1, bt_2, bt_nz, pr_var, pr_nz, sm_cam, sm_nz;
+  std::vector<double> pj_z, calib, sensor, bt_z, pr_data, sm_z, sm_prm;
+  std::vector<int64_t> pr_off, sm_ptr{0};    // (smart factors: one track each)
+  std::map<const void*, int32_t> calib_id;   // shared calibration objects (Cal3_S2 or Cal3DS2) -> row of the calibration table
+  std::vector<double> calib_dist;            // k1 k2 p1 p2 per row (zero for a Cal3_S2)
+  bool any_distortion = false;
+  template <class CAL> void pinhole(const CAL* K) { calib.insert(calib.end(), {K->fx(), K->fy(), K->skew(), K->px(), K->py()}); }
+  int32_t calibRow(const void* object, int distorted) {
+    auto it = calib_id.find(object);
+    if (it != calib_id.end()) return it->second;
+    it = calib_id.emplace(object, (int32_t)(calib.size() / 5)).first;
+    const Cal3DS2* D = distorted ? static_cast<const Cal3DS2*>(object) : nullptr;
+    if (D) { pinhole(D); calib_dist.insert(calib_dist.end(), {D->k1(), D->k2(), D->p1(), D->p2()}); any_distortion = true; }
+    else { pinhole(static_cast<const Cal3_S2*>(object)); calib_dist.insert(calib_dist.end(), {0.0, 0.0, 0.0, 0.0}); }
+    return it->second;
+  }
+  gtg_problem view(const std::vector<int32_t>& var_type) const {   // (pointers into this object and into var_type: both outlive the upload)
+    gtg_problem pb{};
+    pb.n_vars = (int32_t)var_type.size(); pb.var_type = var_type.data();
+    pb.n_noise = (int32_t)nt.kind.size(); pb.noise_kind = nt.kind.data(); pb.noise_dim = nt.dim.data();
+    pb.noise_off = nt.off.data(); pb.noise_data = nt.data.data();
+    pb.noise_robust = nt.rkind.data(); pb.noise_robust_param = nt.rparam.data();
+    pb.n_sfm = (int64_t)sfm_cam.size(); pb.sfm_cam = sfm_cam.data(); pb.sfm_point = sfm_pt.data(); pb.sfm_z = sfm_z.data(); pb.sfm_noise = sfm_nz.data();
+    pb.n_proj = (int64_t)pj_pose.size(); pb.proj_pose = pj_pose.data(); pb.proj_point = pj_pt.data(); pb.proj_z = pj_z.data();
+    pb.proj_noise = pj_nz.data(); pb.proj_calib = pj_cal.data(); pb.proj_sensor = pj_sen.data();
+    pb.n_calib = (int32_t)(calib.size() / 5); pb.calib = calib.data(); pb.calib_distortion = any_distortion ? calib_dist.data() : nullptr;
+    pb.n_sensor = (int32_t)(sensor.size() / 12); pb.sensor = sensor.data();
+    pb.n_between = (int64_t)bt_1.size(); pb.between_v1 = bt_1.data(); pb.between_v2 = bt_2.data(); pb.between_z = bt_z.data(); pb.between_noise = bt_nz.data();
+    pb.n_smart = (int64_t)sm_nz.size(); pb.smart_ptr = sm_ptr.data(); pb.smart_cam = sm_cam.data(); pb.smart_z = sm_z.data();
+    pb.smart_noise = sm_nz.data(); pb.smart_params = sm_prm.data();
+    pb.n_prior = (int64_t)pr_var.size(); pb.prior_var = pr_var.data(); pb.prior_off = pr_off.data(); pb.prior_data = pr_data.data(); pb.prior_noise = pr_nz.data();
+    return pb;
+  }
+};
+// Variables in Values order (sorted by Key, Values.h:74-79): `keys` and a pointer to every Value.  The walk over the map is pointer
+// chasing (1.5 - 5 ms for the 158 000 variables of the L1723 shape, beside the two copier threads); it is cut into key ranges walked
+// side by side: the range boundaries are lower_bound()s of keys interpolated inside every symbol's index range (Symbol keys: character
+// in the top byte, Key.h / Symbol.h; plain integer keys are one such range), so the pieces are equal where the indices are dense and
+// merely unequal where they are not.  Classification (a chain of dynamic_casts) runs on the extraction's threads, each thread its
+// range; the values are packed on threads while the factor tables are merged.
+void walkValues(const Values& initial, std::vector<Key>* keys, std::vector<const Value*>* vptr, Lap& lap) {
+  const size_t nvars = initial.size();
+  keys->reserve(nvars); vptr->reserve(nvars);
+  const char* walk_env = std::getenv("GTG_VALUES_WALKERS");   // (tests: the split walk on small graphs)
+  const size_t walkers = nvars < 2 ? 1 : walk_env ? (size_t)std::max(1, std::atoi(walk_env)) : nvars >= 32768 ? 4 : 1;
+  std::vector<Values::deref_iterator> cuts;           // walker t takes [cuts[t], cuts[t + 1])
+  cuts.push_back(initial.begin());
+  if (walkers > 1) {
+    struct Seg { Key first, last; };
+    std::vector<Seg> segs;                            // the keys of one symbol character each
+    for (auto it = initial.begin(); it != initial.end();) {
+      const Key first = (*it).key, top = first >> 56;
+      auto next = top == 0xFF ? initial.end() : initial.lower_bound((top + 1) << 56);
+      auto last = next; --last.it_;
+      segs.push_back(Seg{first, (*last).key});
+      it = next;
+    }
+    long double total = 0;
+    for (const Seg& g : segs) total += (long double)(g.last - g.first) + 1;
+    size_t gi = 0; long double before = 0;
+    for (size_t t = 1; t < walkers; t++) {
+      const long double want = total * t / walkers;
+      while (gi + 1 < segs.size() && before + (long double)(segs[gi].last - segs[gi].first) + 1 <= want) { before += (long double)(segs[gi].last - segs[gi].first) + 1; gi++; }
+      const Key k = segs[gi].first + (Key)std::min<long double>(want - before, (long double)(segs[gi].last - segs[gi].first));
+      cuts.push_back(initial.lower_bound(k));
+    }
+  }
+  cuts.push_back(initial.end());
+  lap("(variables: key ranges)");
+  const size_t pieces = cuts.size() - 1;
+  std::vector<std::vector<Key>> pk(pieces);
+  std::vector<std::vector<const Value*>> pv(pieces);
+  parallelRanges(pieces, pieces, [&](size_t t, size_t, size_t) {
+    pk[t].reserve(nvars / pieces + 16); pv[t].reserve(nvars / pieces + 16);
+    for (auto it = cuts[t]; it != cuts[t + 1]; ++it) { const auto kv = *it; pk[t].push_back(kv.key); pv[t].push_back(&kv.value); }
+  });
+  lap("(variables: walk)");
+  for (size_t t = 0; t < pieces; t++) { keys->insert(keys->end(), pk[t].begin(), pk[t].end()); vptr->insert(vptr->end(), pv[t].begin(), pv[t].end()); }
+  if (keys->size() != nvars) throw std::logic_error("GpuLevenbergMarquardtOptimizer: the walk over the Values lost variables");
+}
+// Host threads, a range each: every factor into the Extract of its chunk (and its pointer into graphCopy, sized by the caller), every variable's
+// type into var_type.  Throws for a variable of an unsupported type, else what the first offending factor in graph order threw.
+std::vector<Extract> extractFactors(const NonlinearFactorGraph& graph, NonlinearFactorGraph& graphCopy, const std::vector<const Value*>& vptr,
+                                    const std::vector<Key>& keys, std::vector<int32_t>* var_type) {
+  const size_t nfac = graph.size(), nvars = vptr.size();
+  const size_t grain = std::getenv("GTG_EXTRACT_GRAIN") ? std::max(1, std::atoi(std::getenv("GTG_EXTRACT_GRAIN"))) : 4096;   // factors per thread at least (tests: 1)
+  const size_t nthreads = std::max<size_t>(1, std::min<size_t>(hostThreads(16), nfac / grain + 1));
+  var_type->assign(nvars, -1);
+  std::vector<Extract> part(nthreads);
+  parallelRanges(nfac, nthreads, [&](size_t ti, size_t b, size_t e) {
+    for (size_t v = cut(nvars, nthreads, ti); v < cut(nvars, nthreads, ti + 1); v++) (*var_type)[v] = classify(vptr[v]);   // (-1: unsupported, reported below)
+    extractChunk(part[ti], graph, graphCopy, keys, b, e);
+  });
+  for (size_t v = 0; v < nvars; v++)
+    if ((*var_type)[v] < 0) throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: unsupported value type for key " + DefaultKeyFormatter(keys[v]));
+  for (const Extract& x : part) if (x.err) std::rethrow_exception(x.err);   // the first offending factor in graph order
+  return part;
+}
+// offsets of the packed values / of the tangent vector
+void layoutValues(const std::vector<int32_t>& var_type, std::vector<int64_t>* val_off, std::vector<int64_t>* dim_off) {
+  const size_t nvars = var_type.size();
+  val_off->assign(nvars + 1, 0); dim_off->assign(nvars + 1, 0);
+  for (size_t v = 0; v < nvars; v++) { (*val_off)[v + 1] = (*val_off)[v] + storageSize(var_type[v]); (*dim_off)[v + 1] = (*dim_off)[v] + tangentDim(var_type[v]); }
+}
+// Merge in graph order: the chunks' tables concatenated, noise / calibration rows in first-occurrence order; fac_map: (type, index in the merged table)
+HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap* fac_map) {
+  HostProblem hp;
+  auto cat = [](auto& dst, const auto& src) { dst.insert(dst.end(), src.begin(), src.end()); };
+  auto rows = [&hp](std::vector<int32_t>& dst, const Extract::Runs& runs, const std::vector<int32_t>* expect_dim) {
+    size_t at = 0;
+    for (const auto& r : runs) { dst.insert(dst.end(), (size_t)r.first, hp.nt.add(r.second, expect_dim ? (size_t)(*expect_dim)[at] : 2)); at += (size_t)r.first; }
+  };
+  size_t n_sfm = 0, n_pj = 0, n_bt = 0;
+  for (const Extract& x : part) { n_sfm += x.sfm_cam.size(); n_pj += x.pj_pose.size(); n_bt += x.bt_1.size(); }
+  hp.sfm_cam.alloc(n_sfm); hp.sfm_pt.alloc(n_sfm); hp.sfm_nz.alloc(n_sfm); hp.sfm_z.alloc(2 * n_sfm);
+  hp.pj_pose.reserve(n_pj); hp.pj_pt.reserve(n_pj); hp.pj_nz.reserve(n_pj); hp.pj_cal.reserve(n_pj); hp.pj_sen.reserve(n_pj); hp.pj_z.reserve(2 * n_pj);
+  hp.bt_1.reserve(n_bt); hp.bt_2.reserve(n_bt); hp.bt_nz.reserve(n_bt); hp.bt_z.reserve(12 * n_bt);
+  fac_map->clear(); fac_map->resize(nfac);
+  std::vector<Place> place(part.size());
+  int64_t o_sfm_next = 0;
+  for (size_t pi = 0; pi < part.size(); pi++) {
+    const Extract& x = part[pi];
+    const int64_t o_sen = (int64_t)(hp.sensor.size() / 12), o_prd = (int64_t)hp.pr_data.size(), o_smc = (int64_t)hp.sm_cam.size();
+    place[pi].o_sfm = o_sfm_next; place[pi].o_pj = (int64_t)hp.pj_pose.size(); place[pi].o_bt = (int64_t)hp.bt_1.size();
+    place[pi].o_pr = (int64_t)hp.pr_var.size(); place[pi].o_sm = (int64_t)hp.sm_nz.size();
+    o_sfm_next += (int64_t)x.sfm_cam.size();
+    for (const auto& r : x.sfm_nz) place[pi].sfm_rows.emplace_back(r.first, hp.nt.add(r.second, 2));
+    cat(hp.pj_pose, x.pj_pose); cat(hp.pj_pt, x.pj_pt); cat(hp.pj_z, x.pj_z);
+    rows(hp.pj_nz, x.pj_nz, nullptr);
+    for (int32_t sidx : x.pj_sen) hp.pj_sen.push_back(sidx < 0 ? -1 : (int32_t)(sidx + o_sen));
+    cat(hp.sensor, x.sensor);
+    for (const auto& kc : x.pj_cal) hp.pj_cal.push_back(hp.calibRow(kc.first, kc.second));
+    cat(hp.bt_1, x.bt_1); cat(hp.bt_2, x.bt_2); cat(hp.bt_z, x.bt_z);
+    rows(hp.bt_nz, x.bt_nz, &x.bt_dim);
+    cat(hp.pr_var, x.pr_var); cat(hp.pr_data, x.pr_data);
+    for (int64_t o : x.pr_off) hp.pr_off.push_back(o + o_prd);
+    rows(hp.pr_nz, x.pr_nz, &x.pr_dim);
+    cat(hp.sm_cam, x.sm_cam); cat(hp.sm_z, x.sm_z); cat(hp.sm_prm, x.sm_prm);
+    for (size_t k = 1; k < x.sm_ptr.size(); k++) hp.sm_ptr.push_back(x.sm_ptr[k] + o_smc);
+    rows(hp.sm_nz, x.sm_nz, nullptr);
+  }
+  // the big tables, by threads, one chunk each, now that the offsets and the noise rows are handed out in graph order
+  parallelRanges(part.size(), part.size(), [&](size_t pi, size_t, size_t) {
+    const Extract& x = part[pi];
+    const Place& pl = place[pi];
+    const size_t k = x.sfm_cam.size();
+    if (k) {
+      std::memcpy(hp.sfm_cam.data() + pl.o_sfm, x.sfm_cam.data(), 4 * k); std::memcpy(hp.sfm_pt.data() + pl.o_sfm, x.sfm_pt.data(), 4 * k);
+      std::memcpy(hp.sfm_z.data() + 2 * pl.o_sfm, x.sfm_z.data(), 16 * k);
+      int32_t* nz = hp.sfm_nz.data() + pl.o_sfm;
+      for (const auto& r : pl.sfm_rows) { std::fill(nz, nz + r.first, r.second); nz += r.first; }
+    }
+    auto* fm_out = fac_map->data() + cut(nfac, part.size(), pi);     // (the chunk's factors: the range extractFactors gave it)
+    for (const auto& fm : x.fac_map)
+      *fm_out++ = {fm.first, fm.second + (fm.first == GTG_FAC_GENERAL_SFM ? pl.o_sfm : fm.first == GTG_FAC_PROJECTION ? pl.o_pj :
+                                           fm.first == GTG_FAC_BETWEEN_POSE3 ? pl.o_bt : fm.first == GTG_FAC_PRIOR ? pl.o_pr : fm.first == -2 ? pl.o_sm : 0)};
+  });
+  return hp;
+}
 }  // namespace
 
 void GpuLevenbergMarquardtOptimizer::init(const NonlinearFactorGraph& graph, const Values& initial, int device, const ShardSpec& shards) {
   Impl& m = *impl_;
-  const bool timing = std::getenv("GTG_DEBUG_TIMING") != nullptr;   // host-side breakdown of the construction on stderr
-  auto tprev = std::chrono::high_resolution_clock::now();
-  auto lap = [&](const char* what) {
-    if (!timing) return;
-    const auto now = std::chrono::high_resolution_clock::now();
-    std::fprintf(stderr, "[gtsam_amd shim ] %-46s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - tprev).count());
-    tprev = now;
-  };
+  Lap lap;
   // Two copies the optimizer owes its base class run beside the extraction, which reads the CALLER's graph meanwhile:
   //  - graph_ (NonlinearOptimizer.h:78): one shared-pointer copy per factor -- 18 ms for the 0.68 M factors of the L1723 shape;
   //  - a deep copy of the caller's Values (one heap object per variable).  It stays in the Impl: values() needs a Values object
@@ -287,322 +639,32 @@ void GpuLevenbergMarquardtOptimizer::init(const NonlinearFactorGraph& graph, con
       for (const auto& kv : m.scratch) m.slots.push_back(const_cast<Value*>(&kv.value));   // (the GenericValue objects are non-const heap objects owned by the map's nodes)
     } catch (...) { copyErr2 = std::current_exception(); }
   });
-  struct Join { std::thread& t; ~Join() { if (t.joinable()) t.join(); } } joinCopier{copier};
-  Join joinCopier2{copier2};
+  Join joinCopier{copier}, joinCopier2{copier2};
   // The one-time work of the process -- HIP runtime start, code-object load, function objects of every kernel -- starts on a helper
   // thread now and runs under the host passes below (gtg_prewarm is idempotent: later constructions return at once).
   std::thread prewarmer([device] { gtg_prewarm(device); });
   Join joinPrewarmer{prewarmer};
-
-  // ---- variables: Values order (sorted by Key, Values.h:74-79).  The walk over the map that collects keys and value pointers is pointer
-  // chasing (1.5 - 5 ms for the 158 000 variables of the L1723 shape, beside the two copier threads); it is cut into key ranges walked
-  // side by side: the range boundaries are lower_bound()s of keys interpolated inside every symbol's index range (Symbol keys: character
-  // in the top byte, Key.h / Symbol.h; plain integer keys are one such range), so the pieces are equal where the indices are dense and
-  // merely unequal where they are not.  Classification (a chain of dynamic_casts) runs on the extraction's threads below, each thread its
-  // range; the values are packed on threads while the factor tables are merged.
   lap("(threads started)");
-  const size_t nvars = initial.size();
-  m.keys.reserve(nvars);
-  std::vector<const Value*> vptr; vptr.reserve(nvars);
-  {
-    const char* walk_env = std::getenv("GTG_VALUES_WALKERS");   // (tests: the split walk on small graphs)
-    const size_t walkers = nvars < 2 ? 1 : walk_env ? (size_t)std::max(1, std::atoi(walk_env)) : nvars >= 32768 ? 4 : 1;
-    std::vector<Values::deref_iterator> cut;           // walker t takes [cut[t], cut[t + 1])
-    cut.push_back(initial.begin());
-    if (walkers > 1) {
-      struct Seg { Key first, last; };
-      std::vector<Seg> segs;                            // the keys of one symbol character each
-      for (auto it = initial.begin(); it != initial.end();) {
-        const Key first = (*it).key, top = first >> 56;
-        auto next = top == 0xFF ? initial.end() : initial.lower_bound((top + 1) << 56);
-        auto last = next; --last.it_;
-        segs.push_back(Seg{first, (*last).key});
-        it = next;
-      }
-      long double total = 0;
-      for (const Seg& g : segs) total += (long double)(g.last - g.first) + 1;
-      size_t gi = 0; long double before = 0;
-      for (size_t t = 1; t < walkers; t++) {
-        const long double want = total * t / walkers;
-        while (gi + 1 < segs.size() && before + (long double)(segs[gi].last - segs[gi].first) + 1 <= want) { before += (long double)(segs[gi].last - segs[gi].first) + 1; gi++; }
-        const Key k = segs[gi].first + (Key)std::min<long double>(want - before, (long double)(segs[gi].last - segs[gi].first));
-        cut.push_back(initial.lower_bound(k));
-      }
-    }
-    cut.push_back(initial.end());
-    lap("(variables: key ranges)");
-    const size_t pieces = cut.size() - 1;
-    std::vector<std::vector<Key>> pk(pieces);
-    std::vector<std::vector<const Value*>> pv(pieces);
-    auto walk = [&](size_t t) {
-      pk[t].reserve(nvars / pieces + 16); pv[t].reserve(nvars / pieces + 16);
-      for (auto it = cut[t]; it != cut[t + 1]; ++it) { const auto kv = *it; pk[t].push_back(kv.key); pv[t].push_back(&kv.value); }
-    };
-    std::vector<std::thread> pool;
-    for (size_t t = 1; t < pieces; t++) pool.emplace_back(walk, t);
-    walk(0);
-    for (auto& th : pool) th.join();
-    lap("(variables: walk)");
-    for (size_t t = 0; t < pieces; t++) { m.keys.insert(m.keys.end(), pk[t].begin(), pk[t].end()); vptr.insert(vptr.end(), pv[t].begin(), pv[t].end()); }
-    if (m.keys.size() != nvars) throw std::logic_error("GpuLevenbergMarquardtOptimizer: the walk over the Values lost variables");
-  }
-  m.var_type.assign(nvars, -1);
-  // Key -> variable id: the keys are sorted, so a binary search over the contiguous array (a std::map of 158 000 keys cost 0.2 s of
-  // pointer chasing for the 1.35 M lookups of the L1723 shape)
-  auto idOf = [&](Key k) { return m.idOf(k); };
+  std::vector<const Value*> vptr;
+  walkValues(initial, &m.keys, &vptr, lap);
+  const size_t nvars = m.keys.size();
   lap("variables: keys + value pointers");
-
-  // ---- factors: dynamic_cast to the supported types (anything else is a hard error), on host threads ------------------
-  const size_t nfac = graph.size();
-  const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-  const char* thr_env = std::getenv("GTG_HOST_THREADS");
-  const size_t grain = std::getenv("GTG_EXTRACT_GRAIN") ? std::max(1, std::atoi(std::getenv("GTG_EXTRACT_GRAIN"))) : 4096;   // factors per thread at least (tests: 1)
-  const size_t nthreads = std::max<size_t>(1, std::min<size_t>({(size_t)(thr_env ? std::max(1, std::atoi(thr_env)) : (int)std::min(hw, 16u)), nfac / grain + 1}));
-  std::vector<Extract> part(nthreads);
-  auto work = [&](size_t ti) {
-    Extract& x = part[ti];
-    const size_t b = nfac * ti / nthreads, e = nfac * (ti + 1) / nthreads;
-    x.fac_map.reserve(e - b);
-    x.sm_ptr.push_back(0);
-    // (a chunk is nearly always one kind of factor: room for that kind up front -- vectors that grow by doubling go through mmap / munmap
-    // above 128 KB, and 16 threads doing that held up the thread that deep-copies the Values: it was the last thing the constructor
-    // waited for, 7 ms with 32 extraction threads, 0.3 ms with 16 -- round 6, L1723 shape)
-    if (b < e && graph.begin()[b]) {
-      const NonlinearFactor* f0 = graph.begin()[b].get();
-      if (dynamic_cast<const SfmFactor*>(f0)) { x.sfm_cam.reserve(e - b); x.sfm_pt.reserve(e - b); x.sfm_z.reserve(2 * (e - b)); }
-      else if (dynamic_cast<const ProjFactor*>(f0) || dynamic_cast<const ProjFactorDS2*>(f0)) { x.pj_pose.reserve(e - b); x.pj_pt.reserve(e - b); x.pj_sen.reserve(e - b); x.pj_z.reserve(2 * (e - b)); x.pj_cal.reserve(e - b); }
-      else if (dynamic_cast<const BetweenFactor<Pose3>*>(f0) || dynamic_cast<const BetweenFactor<Pose2>*>(f0)) { x.bt_1.reserve(e - b); x.bt_2.reserve(e - b); x.bt_z.reserve(12 * (e - b)); x.bt_dim.reserve(e - b); }
-    }
-    for (size_t v = nvars * ti / nthreads; v < nvars * (ti + 1) / nthreads; v++) {   // this thread's variables: their types (-1: unsupported, reported below)
-      const Value* val = vptr[v];
-      m.var_type[v] = dynamic_cast<const GenericValue<Point3>*>(val) ? GTG_VAR_POINT3 : dynamic_cast<const GenericValue<SfmCamera>*>(val) ? GTG_VAR_SFM_CAMERA :
-                      dynamic_cast<const GenericValue<Pose3>*>(val) ? GTG_VAR_POSE3 : dynamic_cast<const GenericValue<Pose2>*>(val) ? GTG_VAR_POSE2 : -1;
-    }
-    size_t i = b;
-    try {
-      for (; i < e; i++) {
-        const auto& f = (graph_.at(i) = graph.begin()[i]);   // (graph[i] returns a COPY of the pointer: two more atomic operations per factor)
-        if (!f) { x.fac_map.emplace_back(-1, 0); continue; }
-        if (auto s = dynamic_cast<const SfmFactor*>(f.get())) {
-          x.fac_map.emplace_back(GTG_FAC_GENERAL_SFM, (int64_t)x.sfm_cam.size());
-          x.sfm_cam.push_back(idOf(s->key1())); x.sfm_pt.push_back(idOf(s->key2()));
-          x.sfm_z.push_back(s->measured().x()); x.sfm_z.push_back(s->measured().y());
-          Extract::run(x.sfm_nz, s->noiseModel());
-        } else if (auto p = dynamic_cast<const ProjFactor*>(f.get())) {
-          x.fac_map.emplace_back(GTG_FAC_PROJECTION, (int64_t)x.pj_pose.size());
-          if (p->throwCheirality()) throw std::invalid_argument("GenericProjectionFactor with throwCheirality is not supported");
-          x.pj_pose.push_back(idOf(p->key1())); x.pj_pt.push_back(idOf(p->key2()));
-          x.pj_z.push_back(p->measured().x()); x.pj_z.push_back(p->measured().y());
-          Extract::run(x.pj_nz, p->noiseModel());
-          x.pj_cal.emplace_back(p->calibration().get(), 0);
-          if (p->body_P_sensor()) { x.pj_sen.push_back((int32_t)(x.sensor.size() / 12)); x.sensor.resize(x.sensor.size() + 12); packPose(*p->body_P_sensor(), x.sensor.data() + x.sensor.size() - 12); }
-          else x.pj_sen.push_back(-1);
-        } else if (auto pd = dynamic_cast<const ProjFactorDS2*>(f.get())) {   // the same factor with a Cal3DS2 calibration (section 8(f) #3)
-          x.fac_map.emplace_back(GTG_FAC_PROJECTION, (int64_t)x.pj_pose.size());
-          if (pd->throwCheirality()) throw std::invalid_argument("GenericProjectionFactor with throwCheirality is not supported");
-          x.pj_pose.push_back(idOf(pd->key1())); x.pj_pt.push_back(idOf(pd->key2()));
-          x.pj_z.push_back(pd->measured().x()); x.pj_z.push_back(pd->measured().y());
-          Extract::run(x.pj_nz, pd->noiseModel());
-          x.pj_cal.emplace_back(pd->calibration().get(), 1);
-          if (pd->body_P_sensor()) { x.pj_sen.push_back((int32_t)(x.sensor.size() / 12)); x.sensor.resize(x.sensor.size() + 12); packPose(*pd->body_P_sensor(), x.sensor.data() + x.sensor.size() - 12); }
-          else x.pj_sen.push_back(-1);
-        } else if (auto sf = dynamic_cast<const SmartFactor*>(f.get())) {
-          x.fac_map.emplace_back(-2, (int64_t)x.sm_prm.size() / 8);   // (no Jacobian record: its linearisation is a Hessian factor)
-          const SmartProjectionParams& sp = (*sf).*SmartAccess::params();
-          const TriangulationParameters& tp = sp.triangulation;
-          // HESSIAN, JACOBIAN_Q and JACOBIAN_SVD are the same normal equations (the device never forms the factor itself); an
-          // IMPLICIT_SCHUR factor cannot be eliminated by the reference's direct solvers either.  (throwCheirality / verboseCheirality
-          // are read by the pose-only smart factors, not by SmartProjectionFactor<CAMERA>.)
-          if (sp.linearizationMode == IMPLICIT_SCHUR) throw std::invalid_argument("SmartProjectionFactor: the IMPLICIT_SCHUR linearisation is not supported");
-          if (tp.useLOST) throw std::invalid_argument("SmartProjectionFactor: useLOST is not supported");
-          if (tp.enableEPI && tp.noiseModel) throw std::invalid_argument("SmartProjectionFactor: enableEPI with a noise model in the triangulation parameters is not supported");
-          const SharedIsotropic& iso = (*sf).*SmartAccess::noise();
-          Extract::run(x.sm_nz, iso);
-          const auto& zs = sf->measured();
-          if (zs.size() != sf->keys().size() || zs.empty()) throw std::invalid_argument("SmartProjectionFactor: measurements and keys do not match");
-          for (size_t k = 0; k < zs.size(); k++) { x.sm_cam.push_back(idOf(sf->keys()[k])); x.sm_z.push_back(zs[k].x()); x.sm_z.push_back(zs[k].y()); }
-          x.sm_ptr.push_back((int64_t)x.sm_cam.size());
-          x.sm_prm.insert(x.sm_prm.end(), {tp.rankTolerance, tp.landmarkDistanceThreshold, tp.dynamicOutlierRejectionThreshold, sp.retriangulationThreshold,
-                                           sp.degeneracyMode == ZERO_ON_DEGENERACY ? 1.0 : (sp.degeneracyMode == HANDLE_INFINITY ? 2.0 : 0.0),
-                                           sp.linearizationMode == JACOBIAN_Q ? 2.0 : (sp.linearizationMode == JACOBIAN_SVD ? 3.0 : 0.0), tp.enableEPI ? 1.0 : 0.0, 0.0});
-        } else if (auto bb = dynamic_cast<const BetweenFactor<Pose3>*>(f.get())) {
-          x.fac_map.emplace_back(GTG_FAC_BETWEEN_POSE3, (int64_t)x.bt_1.size());
-          x.bt_1.push_back(idOf(bb->key1())); x.bt_2.push_back(idOf(bb->key2()));
-          x.bt_z.resize(x.bt_z.size() + 12); packPose(bb->measured(), x.bt_z.data() + x.bt_z.size() - 12);
-          Extract::run(x.bt_nz, bb->noiseModel()); x.bt_dim.push_back(6);
-        } else if (auto b2 = dynamic_cast<const BetweenFactor<Pose2>*>(f.get())) {
-          // same table as BetweenFactor<Pose3>: the factor's type follows from its variables', (x, y, theta) in the first 3 doubles
-          x.fac_map.emplace_back(GTG_FAC_BETWEEN_POSE3, (int64_t)x.bt_1.size());
-          x.bt_1.push_back(idOf(b2->key1())); x.bt_2.push_back(idOf(b2->key2()));
-          const Pose2& z = b2->measured();
-          x.bt_z.insert(x.bt_z.end(), {z.x(), z.y(), z.theta(), 0, 0, 0, 0, 0, 0, 0, 0, 0});
-          Extract::run(x.bt_nz, b2->noiseModel()); x.bt_dim.push_back(3);
-        } else if (auto q2 = dynamic_cast<const PriorFactor<Pose2>*>(f.get())) {
-          x.fac_map.emplace_back(GTG_FAC_PRIOR, (int64_t)x.pr_var.size());
-          x.pr_var.push_back(idOf(q2->key())); x.pr_off.push_back((int64_t)x.pr_data.size());
-          x.pr_data.insert(x.pr_data.end(), {q2->prior().x(), q2->prior().y(), q2->prior().theta()});
-          Extract::run(x.pr_nz, q2->noiseModel()); x.pr_dim.push_back(3);
-        } else if (auto pp = dynamic_cast<const PriorFactor<Pose3>*>(f.get())) {
-          x.fac_map.emplace_back(GTG_FAC_PRIOR, (int64_t)x.pr_var.size());
-          x.pr_var.push_back(idOf(pp->key())); x.pr_off.push_back((int64_t)x.pr_data.size());
-          x.pr_data.resize(x.pr_data.size() + 12); packPose(pp->prior(), x.pr_data.data() + x.pr_data.size() - 12);
-          Extract::run(x.pr_nz, pp->noiseModel()); x.pr_dim.push_back(6);
-        } else if (auto pc = dynamic_cast<const PriorFactor<SfmCamera>*>(f.get())) {
-          x.fac_map.emplace_back(GTG_FAC_PRIOR, (int64_t)x.pr_var.size());
-          x.pr_var.push_back(idOf(pc->key())); x.pr_off.push_back((int64_t)x.pr_data.size());
-          x.pr_data.resize(x.pr_data.size() + 17); packCamera(pc->prior(), x.pr_data.data() + x.pr_data.size() - 17);
-          Extract::run(x.pr_nz, pc->noiseModel()); x.pr_dim.push_back(9);
-        } else if (auto p3 = dynamic_cast<const PriorFactor<Point3>*>(f.get())) {
-          x.fac_map.emplace_back(GTG_FAC_PRIOR, (int64_t)x.pr_var.size());
-          x.pr_var.push_back(idOf(p3->key())); x.pr_off.push_back((int64_t)x.pr_data.size());
-          x.pr_data.insert(x.pr_data.end(), {p3->prior().x(), p3->prior().y(), p3->prior().z()});
-          Extract::run(x.pr_nz, p3->noiseModel()); x.pr_dim.push_back(3);
-        } else {
-          throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: factor type outside the GPU hot path "
-                                      "(supported: GeneralSFMFactor<SfmCamera,Point3>, GenericProjectionFactor<Pose3,Point3,Cal3_S2|Cal3DS2>, "
-                                      "SmartProjectionFactor<SfmCamera>, BetweenFactor<Pose3|Pose2>, PriorFactor<Pose3|Pose2|SfmCamera|Point3>)");
-        }
-      }
-    } catch (...) { x.err = std::current_exception(); x.err_at = i; }
-  };
-  copier.join();
+  copier.join();   // (the extraction's threads fill the graph_ it sized)
   if (copyErr) std::rethrow_exception(copyErr);
-  {
-    std::vector<std::thread> pool;
-    for (size_t ti = 1; ti < nthreads; ti++) pool.emplace_back(work, ti);
-    work(0);
-    for (auto& t : pool) t.join();
-  }
-  for (size_t v = 0; v < nvars; v++)
-    if (m.var_type[v] < 0) throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: unsupported value type for key " + DefaultKeyFormatter(m.keys[v]));
-  for (const Extract& x : part) if (x.err) std::rethrow_exception(x.err);   // the first offending factor in graph order
+  const std::vector<Extract> part = extractFactors(graph, graph_, vptr, m.keys, &m.var_type);
   lap("factors: extraction, variables: classification (host threads)");
-  // offsets of the packed values / of the tangent vector, then the packing itself on threads beside the merge of the factor tables
-  m.val_off.resize(nvars + 1); m.dim_off.resize(nvars + 1);
-  m.val_off[0] = 0; m.dim_off[0] = 0;
-  for (size_t v = 0; v < nvars; v++) {
-    const int32_t t = m.var_type[v];
-    m.val_off[v + 1] = m.val_off[v] + (t == GTG_VAR_POSE3 ? 12 : t == GTG_VAR_SFM_CAMERA ? 17 : 3);
-    m.dim_off[v + 1] = m.dim_off[v] + (t == GTG_VAR_POSE3 ? 6 : t == GTG_VAR_SFM_CAMERA ? 9 : 3);
-  }
+  // the packing itself on threads beside the merge of the factor tables
+  layoutValues(m.var_type, &m.val_off, &m.dim_off);
   m.packed.resize((size_t)m.val_off[nvars]);
-  auto pack = [&](size_t b, size_t e) {
-    for (size_t v = b; v < e; v++) {
-      double* p = m.packed.data() + m.val_off[v];
-      const int32_t t = m.var_type[v];
-      if (t == GTG_VAR_POINT3) { const Point3& q = static_cast<const GenericValue<Point3>*>(vptr[v])->value(); p[0] = q.x(); p[1] = q.y(); p[2] = q.z(); }
-      else if (t == GTG_VAR_SFM_CAMERA) packCamera(static_cast<const GenericValue<SfmCamera>*>(vptr[v])->value(), p);
-      else if (t == GTG_VAR_POSE3) packPose(static_cast<const GenericValue<Pose3>*>(vptr[v])->value(), p);
-      else { const Pose2& q = static_cast<const GenericValue<Pose2>*>(vptr[v])->value(); p[0] = q.x(); p[1] = q.y(); p[2] = q.theta(); }
-    }
-  };
-  const size_t npack = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(nthreads, 8), nvars / 8192 + 1));
+  const size_t npack = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(part.size(), 8), nvars / 8192 + 1));
   std::vector<std::thread> packers;
-  for (size_t ti = 0; ti < npack; ti++) packers.emplace_back(pack, nvars * ti / npack, nvars * (ti + 1) / npack);
-  struct JoinAll { std::vector<std::thread>& v; ~JoinAll() { for (auto& t : v) if (t.joinable()) t.join(); } } joinPackers{packers};
-
-  // ---- merge in graph order: concatenate the tables, hand out the rows of the noise / calibration tables -----------------
-  NoiseTable nt;
-  // (the GeneralSFM tables and the factor map -- 30 MB on the L1723 shape -- are filled by threads, one chunk each, after this loop has
-  // handed out the offsets and the noise rows in graph order: plain buffers, not value-initialised)
-  struct RawI { std::unique_ptr<int32_t[]> p; size_t n = 0; void alloc(size_t k) { p.reset(new int32_t[k ? k : 1]); n = k; } int32_t* data() { return p.get(); } size_t size() const { return n; } };
-  struct RawD { std::unique_ptr<double[]> p; size_t n = 0; void alloc(size_t k) { p.reset(new double[k ? k : 1]); n = k; } double* data() { return p.get(); } size_t size() const { return n; } };
-  RawI sfm_cam, sfm_pt, sfm_nz;
-  RawD sfm_z;
-  std::vector<int32_t> pj_pose, pj_pt, pj_nz, pj_cal, pj_sen, bt_1, bt_2, bt_nz, pr_var, pr_nz;
-  std::vector<double> pj_z, calib, sensor, bt_z, pr_data;
-  std::vector<int64_t> pr_off;
-  std::map<const void*, int32_t> calib_id;   // shared calibration objects (Cal3_S2 or Cal3DS2) -> row of the calibration table
-  std::vector<double> calib_dist;            // k1 k2 p1 p2 per row (zero for a Cal3_S2)
-  std::vector<int64_t> sm_ptr(1, 0);          // smart factors: one track each
-  std::vector<int32_t> sm_cam, sm_nz;
-  std::vector<double> sm_z, sm_prm;
-  bool any_distortion = false;
-  {
-    size_t n_sfm = 0, n_pj = 0, n_bt = 0, n_pr = 0, n_smc = 0, n_sm = 0;
-    for (const Extract& x : part) { n_sfm += x.sfm_cam.size(); n_pj += x.pj_pose.size(); n_bt += x.bt_1.size(); n_pr += x.pr_var.size(); n_smc += x.sm_cam.size(); n_sm += x.sm_prm.size() / 8; }
-    sfm_cam.alloc(n_sfm); sfm_pt.alloc(n_sfm); sfm_nz.alloc(n_sfm); sfm_z.alloc(2 * n_sfm);
-    pj_pose.reserve(n_pj); pj_pt.reserve(n_pj); pj_nz.reserve(n_pj); pj_cal.reserve(n_pj); pj_sen.reserve(n_pj); pj_z.reserve(2 * n_pj);
-    bt_1.reserve(n_bt); bt_2.reserve(n_bt); bt_nz.reserve(n_bt); bt_z.reserve(12 * n_bt);
-    m.fac_map.clear(); m.fac_map.resize(nfac);
-  }
-  auto cat = [](auto& dst, const auto& src) { dst.insert(dst.end(), src.begin(), src.end()); };
-  struct Place { int64_t o_sfm, o_pj, o_bt, o_pr, o_sm; std::vector<std::pair<int64_t, int32_t>> sfm_rows; };   // per chunk: offsets of its tables, (count, noise row) of its GeneralSFM runs
-  std::vector<Place> place(part.size());
-  int64_t o_sfm_next = 0;
-  for (size_t pi = 0; pi < part.size(); pi++) {
-    const Extract& x = part[pi];
-    const int64_t o_sfm = o_sfm_next, o_pj = (int64_t)pj_pose.size(), o_bt = (int64_t)bt_1.size(), o_pr = (int64_t)pr_var.size(),
-                  o_sm = (int64_t)sm_nz.size(), o_sen = (int64_t)(sensor.size() / 12), o_prd = (int64_t)pr_data.size(), o_smc = (int64_t)sm_cam.size();
-    place[pi].o_sfm = o_sfm; place[pi].o_pj = o_pj; place[pi].o_bt = o_bt; place[pi].o_pr = o_pr; place[pi].o_sm = o_sm;
-    o_sfm_next += (int64_t)x.sfm_cam.size();
-    for (const auto& r : x.sfm_nz) place[pi].sfm_rows.emplace_back(r.first, nt.add(r.second, 2));
-    cat(pj_pose, x.pj_pose); cat(pj_pt, x.pj_pt); cat(pj_z, x.pj_z);
-    for (const auto& r : x.pj_nz) pj_nz.insert(pj_nz.end(), (size_t)r.first, nt.add(r.second, 2));
-    for (int32_t sidx : x.pj_sen) pj_sen.push_back(sidx < 0 ? -1 : (int32_t)(sidx + o_sen));
-    cat(sensor, x.sensor);
-    for (const auto& kc : x.pj_cal) {
-      auto it = calib_id.find(kc.first);
-      if (it == calib_id.end()) {
-        it = calib_id.emplace(kc.first, (int32_t)(calib.size() / 5)).first;
-        if (kc.second) {
-          const Cal3DS2* K = static_cast<const Cal3DS2*>(kc.first);
-          calib.insert(calib.end(), {K->fx(), K->fy(), K->skew(), K->px(), K->py()});
-          calib_dist.insert(calib_dist.end(), {K->k1(), K->k2(), K->p1(), K->p2()});
-          any_distortion = true;
-        } else {
-          const Cal3_S2* K = static_cast<const Cal3_S2*>(kc.first);
-          calib.insert(calib.end(), {K->fx(), K->fy(), K->skew(), K->px(), K->py()});
-          calib_dist.insert(calib_dist.end(), {0.0, 0.0, 0.0, 0.0});
-        }
-      }
-      pj_cal.push_back(it->second);
-    }
-    cat(bt_1, x.bt_1); cat(bt_2, x.bt_2); cat(bt_z, x.bt_z);
-    { size_t at = 0; for (const auto& r : x.bt_nz) { bt_nz.insert(bt_nz.end(), (size_t)r.first, nt.add(r.second, (size_t)x.bt_dim[at])); at += (size_t)r.first; } }
-    cat(pr_var, x.pr_var); cat(pr_data, x.pr_data);
-    for (int64_t o : x.pr_off) pr_off.push_back(o + o_prd);
-    { size_t at = 0; for (const auto& r : x.pr_nz) { pr_nz.insert(pr_nz.end(), (size_t)r.first, nt.add(r.second, (size_t)x.pr_dim[at])); at += (size_t)r.first; } }
-    cat(sm_cam, x.sm_cam); cat(sm_z, x.sm_z); cat(sm_prm, x.sm_prm);
-    for (size_t k = 1; k < x.sm_ptr.size(); k++) sm_ptr.push_back(x.sm_ptr[k] + o_smc);
-    for (const auto& r : x.sm_nz) sm_nz.insert(sm_nz.end(), (size_t)r.first, nt.add(r.second, 2));
-  }
-  {
-    auto fill = [&](size_t pi) {
-      const Extract& x = part[pi];
-      const Place& pl = place[pi];
-      const size_t k = x.sfm_cam.size();
-      if (k) {
-        std::memcpy(sfm_cam.data() + pl.o_sfm, x.sfm_cam.data(), 4 * k); std::memcpy(sfm_pt.data() + pl.o_sfm, x.sfm_pt.data(), 4 * k);
-        std::memcpy(sfm_z.data() + 2 * pl.o_sfm, x.sfm_z.data(), 16 * k);
-        int32_t* nz = sfm_nz.data() + pl.o_sfm;
-        for (const auto& r : pl.sfm_rows) { std::fill(nz, nz + r.first, r.second); nz += r.first; }
-      }
-      auto* fm_out = m.fac_map.data() + nfac * pi / nthreads;     // (the chunk's factors: graph indices [nfac pi / nthreads, nfac (pi + 1) / nthreads))
-      for (const auto& fm : x.fac_map)
-        *fm_out++ = {fm.first, fm.second + (fm.first == GTG_FAC_GENERAL_SFM ? pl.o_sfm : fm.first == GTG_FAC_PROJECTION ? pl.o_pj :
-                                             fm.first == GTG_FAC_BETWEEN_POSE3 ? pl.o_bt : fm.first == GTG_FAC_PRIOR ? pl.o_pr : fm.first == -2 ? pl.o_sm : 0)};
-    };
-    std::vector<std::thread> fillers;
-    for (size_t pi = 1; pi < part.size(); pi++) fillers.emplace_back(fill, pi);
-    fill(0);
-    for (auto& t : fillers) t.join();
-  }
+  JoinAll joinPackers{packers};
+  startRanges(packers, nvars, npack, 0, [&](size_t, size_t b, size_t e) {
+    for (size_t v = b; v < e; v++) pack(m.var_type[v], *vptr[v], m.packed.data() + m.val_off[v]);
+  });
+  const HostProblem hp = mergeTables(part, graph.size(), &m.fac_map);
   lap("factors: merge, noise / calibration tables");
-  gtg_problem pb{};
-  pb.n_vars = (int32_t)m.keys.size(); pb.var_type = m.var_type.data();
-  pb.n_noise = (int32_t)nt.kind.size(); pb.noise_kind = nt.kind.data(); pb.noise_dim = nt.dim.data();
-  pb.noise_off = nt.off.data(); pb.noise_data = nt.data.data();
-  pb.noise_robust = nt.rkind.data(); pb.noise_robust_param = nt.rparam.data();
-  pb.n_sfm = (int64_t)sfm_cam.size(); pb.sfm_cam = sfm_cam.data(); pb.sfm_point = sfm_pt.data(); pb.sfm_z = sfm_z.data(); pb.sfm_noise = sfm_nz.data();
-  pb.n_proj = (int64_t)pj_pose.size(); pb.proj_pose = pj_pose.data(); pb.proj_point = pj_pt.data(); pb.proj_z = pj_z.data();
-  pb.proj_noise = pj_nz.data(); pb.proj_calib = pj_cal.data(); pb.proj_sensor = pj_sen.data();
-  pb.n_calib = (int32_t)(calib.size() / 5); pb.calib = calib.data(); pb.calib_distortion = any_distortion ? calib_dist.data() : nullptr; pb.n_sensor = (int32_t)(sensor.size() / 12); pb.sensor = sensor.data();
-  pb.n_between = (int64_t)bt_1.size(); pb.between_v1 = bt_1.data(); pb.between_v2 = bt_2.data(); pb.between_z = bt_z.data(); pb.between_noise = bt_nz.data();
-  pb.n_smart = (int64_t)sm_nz.size(); pb.smart_ptr = sm_ptr.data(); pb.smart_cam = sm_cam.data(); pb.smart_z = sm_z.data();
-  pb.smart_noise = sm_nz.data(); pb.smart_params = sm_prm.data();
-  pb.n_prior = (int64_t)pr_var.size(); pb.prior_var = pr_var.data(); pb.prior_off = pr_off.data(); pb.prior_data = pr_data.data(); pb.prior_noise = pr_nz.data();
-
+  const gtg_problem pb = hp.view(m.var_type);
   if (shards.n_shards < 1 || shards.shard < 0 || shards.shard >= shards.n_shards) throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: bad ShardSpec");
   if (shards.n_shards > 1 && !shards.allreduce) throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: n_shards > 1 needs an all-reduce callback");
   for (auto& t : packers) t.join();
@@ -621,20 +683,15 @@ void GpuLevenbergMarquardtOptimizer::init(const NonlinearFactorGraph& graph, con
   lap("device: initial error");
   copier2.join();
   lap("wait for the copies of the graph and the Values");
-  if (copyErr) std::rethrow_exception(copyErr);
   if (copyErr2) std::rethrow_exception(copyErr2);
   // The State: the deep copy made beside the extraction moves into a GpuState (see GpuState::make: no second copy).  `slots` points
   // into the nodes of that Values' map -- heap objects that stay where they are when the map moves on into the next State -- and every
   // use checks first that state_ is still a State of this class holding that map (adoptStateIfForeign): a State published by anybody
   // else -- the inherited public tryLambda() does that -- is adopted, not written over.
-  {
-    if (m.slots.size() != nvars) throw std::logic_error("GpuLevenbergMarquardtOptimizer: the copy of the Values lost variables");
-    std::unique_ptr<GpuState> fresh = GpuState::make(std::move(m.scratch), e0, params_.lambdaInitial, params_.lambdaFactor, 0, 0);   // (`slots`, collected by the copier thread, points into the nodes that move here)
-    state_ = std::move(fresh);
-    m.published = &state_->values;
-  }
-  const State* s = static_cast<const State*>(state_.get());
-  m.error = s->error; m.lambda = s->lambda; m.factor = s->currentFactor; m.iterations = s->iterations; m.inner = s->totalNumberInnerIterations;
+  if (m.slots.size() != nvars) throw std::logic_error("GpuLevenbergMarquardtOptimizer: the copy of the Values lost variables");
+  state_ = GpuState::make(std::move(m.scratch), e0, params_.lambdaInitial, params_.lambdaFactor, 0, 0);   // (`slots`, collected by the copier thread, points into the nodes that move here)
+  m.published = &state_->values;
+  m.takeScalars(*static_cast<const State*>(state_.get()));
   lap("state");
   prewarmer.join();
   lap("wait for the prewarm thread");
@@ -659,12 +716,8 @@ void GpuLevenbergMarquardtOptimizer::adoptStateIfForeign() const {
     size_t id = 0;
     for (const auto& kv : v) {
       if (kv.key != m.keys[id]) throw std::logic_error("GpuLevenbergMarquardtOptimizer: the optimizer's State holds other variables than the graph was uploaded with");
-      double* p = m.packed.data() + m.val_off[id];
-      const int32_t t = m.var_type[id];
-      if (t == GTG_VAR_POINT3) { const Point3& q = kv.value.cast<Point3>(); p[0] = q.x(); p[1] = q.y(); p[2] = q.z(); }
-      else if (t == GTG_VAR_SFM_CAMERA) packCamera(kv.value.cast<SfmCamera>(), p);
-      else if (t == GTG_VAR_POSE3) packPose(kv.value.cast<Pose3>(), p);
-      else { const Pose2& q = kv.value.cast<Pose2>(); p[0] = q.x(); p[1] = q.y(); p[2] = q.theta(); }
+      if (classify(&kv.value) != m.var_type[id]) throw std::bad_cast();   // (what Value::cast<T>() throws: a variable that changed its type)
+      pack(m.var_type[id], kv.value, m.packed.data() + m.val_off[id]);
       m.slots.push_back(const_cast<Value*>(&kv.value));
       id++;
     }
@@ -672,7 +725,7 @@ void GpuLevenbergMarquardtOptimizer::adoptStateIfForeign() const {
     m.host_values_stale = false;
     m.published = &state_->values;
   }
-  m.error = st->error; m.lambda = st->lambda; m.factor = st->currentFactor; m.iterations = st->iterations; m.inner = st->totalNumberInnerIterations;
+  m.takeScalars(*st);
 }
 
 void GpuLevenbergMarquardtOptimizer::syncValuesToHost(bool force) {
@@ -684,22 +737,10 @@ void GpuLevenbergMarquardtOptimizer::syncValuesToHost(bool force) {
     check(gtg_get_values(m.h, m.packed.data(), (int64_t)m.packed.size()), "gtg_get_values");
     // overwrite the payloads of the State's Values in place (m.slots: the GenericValue objects by variable id), host threads
     const size_t nv = m.slots.size();
-    auto work = [&](size_t b, size_t e) {
-      for (size_t v = b; v < e; v++) {
-        const double* p = m.packed.data() + m.val_off[v];
-        Value& val = *m.slots[v];
-        if (m.var_type[v] == GTG_VAR_POINT3) static_cast<GenericValue<Point3>&>(val).value() = Point3(p[0], p[1], p[2]);
-        else if (m.var_type[v] == GTG_VAR_SFM_CAMERA) static_cast<GenericValue<SfmCamera>&>(val).value() = SfmCamera(unpackPose(p), Cal3Bundler(p[12], p[13], p[14], p[15], p[16]));
-        else if (m.var_type[v] == GTG_VAR_POSE3) static_cast<GenericValue<Pose3>&>(val).value() = unpackPose(p);
-        else static_cast<GenericValue<Pose2>&>(val).value() = Pose2(p[0], p[1], p[2]);
-      }
-    };
-    const char* thr_env = std::getenv("GTG_HOST_THREADS");
-    const size_t nthreads = std::max<size_t>(1, std::min<size_t>({(size_t)(thr_env ? std::max(1, std::atoi(thr_env)) : (int)std::min(std::max(1u, std::thread::hardware_concurrency()), 32u)), nv / 8192 + 1}));   // (8 until round 6: the 1.8 M payloads of the Venice shape took 12 % of its optimize())
-    std::vector<std::thread> pool;
-    for (size_t ti = 1; ti < nthreads; ti++) pool.emplace_back(work, nv * ti / nthreads, nv * (ti + 1) / nthreads);
-    work(0, nv / nthreads);
-    for (auto& t : pool) t.join();
+    const size_t nthreads = std::max<size_t>(1, std::min<size_t>(hostThreads(32), nv / 8192 + 1));   // (8 until round 6: the 1.8 M payloads of the Venice shape took 12 % of its optimize())
+    parallelRanges(nv, nthreads, [&](size_t, size_t b, size_t e) {
+      for (size_t v = b; v < e; v++) unpack(m.var_type[v], m.packed.data() + m.val_off[v], *m.slots[v]);
+    });
   }
   // the next State, with the device's error / lambda / counters
   std::unique_ptr<GpuState> fresh;
@@ -732,16 +773,13 @@ bool GpuLevenbergMarquardtOptimizer::tryLambdaDevice() {
   double out[4] = {0, 0, 0, 0};
   int rc;
   if (params_.isIterative()) {
-    // NonlinearOptimizer::solve, Iterative branch (NonlinearOptimizer.cpp:154-172): PCGSolverParameters only, and the
-    // device solver is block-Jacobi PCG on the implicit Schur complement (a Dummy preconditioner or a SubgraphSolver is
-    // outside the GPU path).
+    // NonlinearOptimizer::solve, Iterative branch (NonlinearOptimizer.cpp:154-172): PCGSolverParameters only, and the device solver is
+    // block-Jacobi PCG on the implicit Schur complement (a Dummy preconditioner or a SubgraphSolver is outside the GPU path).
     if (!params_.iterativeParams) throw std::runtime_error("NonlinearOptimizer::solve: cg parameter has to be assigned ...");
-    auto pcg = std::dynamic_pointer_cast<PCGSolverParameters>(params_.iterativeParams);
-    if (!pcg) throw std::runtime_error("GpuLevenbergMarquardtOptimizer: only PCGSolverParameters are handled by the GPU path");
-    if (!std::dynamic_pointer_cast<BlockJacobiPreconditionerParameters>(pcg->preconditioner))
+    double cg[4];
+    if (!std::dynamic_pointer_cast<BlockJacobiPreconditionerParameters>(pcgParameters(params_, "GpuLevenbergMarquardtOptimizer", cg)->preconditioner))
       throw std::runtime_error("GpuLevenbergMarquardtOptimizer: the GPU PCG solver is block-Jacobi preconditioned "
                                "(set PCGSolverParameters::preconditioner to BlockJacobiPreconditionerParameters)");
-    const double cg[4] = {(double)pcg->maxIterations, (double)pcg->minIterations, pcg->epsilon_rel, pcg->epsilon_abs};
     int32_t cg_iterations = 0;
     rc = gtg_try_lambda_pcg(m.h, m.lambda, params_.diagonalDamping, params_.minDiagonal, params_.maxDiagonal, cg, out, &cg_iterations);
     check(rc, "gtg_try_lambda_pcg");
@@ -845,39 +883,20 @@ GaussianFactorGraph::shared_ptr GpuLevenbergMarquardtOptimizer::iterate() {
 // NonlinearFactor.cpp:150-182), one per factor of graph_, in its order.
 GaussianFactorGraph::shared_ptr GpuLevenbergMarquardtOptimizer::downloadLinearization() const {
   const Impl& m = *impl_;
-  static const int64_t width[4] = {26, 20, 78, 90};
-  std::vector<double> rec[4];
-  int64_t count[4] = {0, 0, 0, 0};
-  for (const auto& tf : m.fac_map) if (tf.first >= 0) count[tf.first]++;   // (-1: null factor, -2: smart factor -- its linearisation is a
-                                                                            // Hessian factor the device never forms: left empty here)
-  for (int t = 0; t < 4; t++) {
-    if (!count[t]) continue;
-    rec[t].resize((size_t)(count[t] * width[t]));
-    check(gtg_get_jacobians(m.h, t, rec[t].data(), (int64_t)rec[t].size()), "gtg_get_jacobians");
-  }
+  const Records records = fetchRecords(m.h, m.fac_map);
   auto out = std::make_shared<GaussianFactorGraph>();
   out->reserve(graph_.size());
   typedef Eigen::Matrix<double, Eigen::Dynamic, Eigen::Dynamic, Eigen::RowMajor> RowMat;
   for (size_t i = 0; i < graph_.size(); i++) {
     const auto tf = m.fac_map[i];
-    if (tf.first < 0) { out->push_back(GaussianFactor::shared_ptr()); continue; }
-    const double* r = rec[tf.first].data() + tf.second * width[tf.first];
+    if (tf.first < 0) { out->push_back(GaussianFactor::shared_ptr()); continue; }   // (null, or a smart factor: left empty here)
+    const double* r = records.of(tf);
     const KeyVector& keys = graph_[i]->keys();
-    if (tf.first == GTG_FAC_GENERAL_SFM) {
-      out->emplace_shared<JacobianFactor>(keys[0], Matrix(Eigen::Map<const RowMat>(r, 2, 9)), keys[1], Matrix(Eigen::Map<const RowMat>(r + 18, 2, 3)),
-                                          Vector(Eigen::Map<const Vector>(r + 24, 2)));
-    } else if (tf.first == GTG_FAC_PROJECTION) {
-      out->emplace_shared<JacobianFactor>(keys[0], Matrix(Eigen::Map<const RowMat>(r, 2, 6)), keys[1], Matrix(Eigen::Map<const RowMat>(r + 12, 2, 3)),
-                                          Vector(Eigen::Map<const Vector>(r + 18, 2)));
-    } else if (tf.first == GTG_FAC_BETWEEN_POSE3) {
-      const int d = (m.var_type[m.idOf(keys[0])] == GTG_VAR_POSE2) ? 3 : 6;   // Pose2: 3x3 blocks inside the same record
-      out->emplace_shared<JacobianFactor>(keys[0], Matrix(Eigen::Map<const RowMat>(r, d, d)), keys[1], Matrix(Eigen::Map<const RowMat>(r + 36, d, d)),
-                                          Vector(Eigen::Map<const Vector>(r + 72, d)));
-    } else {
-      const int32_t vt = m.var_type[m.idOf(keys[0])];
-      const int d = vt == GTG_VAR_POSE3 ? 6 : vt == GTG_VAR_SFM_CAMERA ? 9 : 3;
-      out->emplace_shared<JacobianFactor>(keys[0], Matrix(Eigen::Map<const RowMat>(r, d, d)), Vector(Eigen::Map<const Vector>(r + 81, d)));
-    }
+    const RecordLayout lay = m.layoutOf(tf, keys[0]);
+    auto block = [&](int k) { return Matrix(Eigen::Map<const RowMat>(r + lay.boff[k], lay.rows, lay.bcols[k])); };
+    const Vector b = Eigen::Map<const Vector>(r + lay.rhs, lay.rows);
+    if (lay.nblk == 2) out->emplace_shared<JacobianFactor>(keys[0], block(0), keys[1], block(1), b);
+    else out->emplace_shared<JacobianFactor>(keys[0], block(0), b);
   }
   return out;
 }
@@ -915,56 +934,37 @@ VectorValues GpuLevenbergMarquardtOptimizer::solve(const GaussianFactorGraph& gf
   // other values, or with any factor edited by the caller, has the right SHAPE but not these numbers; it goes to the reference's CPU
   // solve like any other graph.  (Entries of smart factors -- Hessian factors the device never forms -- are skipped.)
   {
-    static const int64_t width[4] = {26, 20, 78, 90};
-    std::vector<double> rec[4];
-    int64_t count[4] = {0, 0, 0, 0};
-    for (const auto& tf : m.fac_map) if (tf.first >= 0) count[tf.first]++;
-    for (int t = 0; t < 4; t++) {
-      if (!count[t]) continue;
-      rec[t].resize((size_t)(count[t] * width[t]));
-      check(gtg_get_jacobians(m.h, t, rec[t].data(), (int64_t)rec[t].size()), "gtg_get_jacobians");
-    }
+    const Records records = fetchRecords(m.h, m.fac_map);
     std::atomic<bool> same{true};
-    auto work = [&](size_t b0, size_t e0) {
+    const size_t nthreads = std::max<size_t>(1, std::min<size_t>({(size_t)std::min(std::max(1u, std::thread::hardware_concurrency()), 16u), nf / 16384 + 1}));
+    parallelRanges(nf, nthreads, [&](size_t, size_t b0, size_t e0) {
       for (size_t i = b0; i < e0 && same.load(std::memory_order_relaxed); i++) {
         const auto tf = m.fac_map[i];
         if (tf.first < 0) continue;
         const auto* theirs = dynamic_cast<const JacobianFactor*>(gfg[i].get());
         if (!theirs || theirs->get_model() || theirs->keys() != graph_[i]->keys()) { same = false; return; }
-        const double* r = rec[tf.first].data() + tf.second * width[tf.first];
-        // the record's layout (what downloadLinearization wraps): row-major blocks, then b
-        int rows, nblk, boff[2], bcols[2], rhs;
-        if (tf.first == GTG_FAC_GENERAL_SFM) { rows = 2; nblk = 2; boff[0] = 0; bcols[0] = 9; boff[1] = 18; bcols[1] = 3; rhs = 24; }
-        else if (tf.first == GTG_FAC_PROJECTION) { rows = 2; nblk = 2; boff[0] = 0; bcols[0] = 6; boff[1] = 12; bcols[1] = 3; rhs = 18; }
-        else if (tf.first == GTG_FAC_BETWEEN_POSE3) { const int d = (m.var_type[m.idOf(theirs->keys()[0])] == GTG_VAR_POSE2) ? 3 : 6; rows = d; nblk = 2; boff[0] = 0; bcols[0] = d; boff[1] = 36; bcols[1] = d; rhs = 72; }
-        else { const int32_t vt = m.var_type[m.idOf(theirs->keys()[0])]; const int d = vt == GTG_VAR_POSE3 ? 6 : vt == GTG_VAR_SFM_CAMERA ? 9 : 3; rows = d; nblk = 1; boff[0] = 0; bcols[0] = d; boff[1] = 0; bcols[1] = 0; rhs = 81; }
-        if ((int)theirs->size() != nblk || (int)theirs->rows() != rows) { same = false; return; }
+        const double* r = records.of(tf);
+        const RecordLayout lay = m.layoutOf(tf, theirs->keys()[0]);   // (what downloadLinearization wraps: row-major blocks, then b)
+        if ((int)theirs->size() != lay.nblk || (int)theirs->rows() != lay.rows) { same = false; return; }
         double scale = 1.0, worst = 0.0;
-        for (int k = 0; k < nblk; k++) {
+        for (int k = 0; k < lay.nblk; k++) {
           const auto A = theirs->getA(theirs->begin() + k);
-          if ((int)A.cols() != bcols[k]) { same = false; return; }
-          for (int a = 0; a < rows; a++)
-            for (int cc = 0; cc < bcols[k]; cc++) { const double x = A(a, cc); scale = std::max(scale, std::abs(x)); worst = std::max(worst, std::abs(x - r[boff[k] + a * bcols[k] + cc])); }
+          if ((int)A.cols() != lay.bcols[k]) { same = false; return; }
+          for (int a = 0; a < lay.rows; a++)
+            for (int cc = 0; cc < lay.bcols[k]; cc++) { const double x = A(a, cc); scale = std::max(scale, std::abs(x)); worst = std::max(worst, std::abs(x - r[lay.boff[k] + a * lay.bcols[k] + cc])); }
         }
         const auto bb = theirs->getb();
-        for (int a = 0; a < rows; a++) { scale = std::max(scale, std::abs(bb(a))); worst = std::max(worst, std::abs(bb(a) - r[rhs + a])); }
+        for (int a = 0; a < lay.rows; a++) { scale = std::max(scale, std::abs(bb(a))); worst = std::max(worst, std::abs(bb(a) - r[lay.rhs + a])); }
         if (!(worst <= 1e-9 * scale)) { same = false; return; }
       }
-    };
-    const size_t nthreads = std::max<size_t>(1, std::min<size_t>({(size_t)std::min(std::max(1u, std::thread::hardware_concurrency()), 16u), nf / 16384 + 1}));
-    std::vector<std::thread> pool;
-    for (size_t ti = 1; ti < nthreads; ti++) pool.emplace_back(work, nf * ti / nthreads, nf * (ti + 1) / nthreads);
-    work(0, nf / nthreads);
-    for (auto& t : pool) t.join();
+    });
     if (!same) return LevenbergMarquardtOptimizer::solve(gfg, params);
   }
   double out[4];
   int rc;
   if (params.isIterative()) {
-    auto pcg = std::dynamic_pointer_cast<PCGSolverParameters>(params.iterativeParams);
-    if (!pcg) throw std::runtime_error("GpuLevenbergMarquardtOptimizer::solve: only PCGSolverParameters are handled by the GPU path");
-    const double cg[4] = {(double)pcg->maxIterations, (double)pcg->minIterations, pcg->epsilon_rel, pcg->epsilon_abs};
-    int32_t its = 0;
+    double cg[4]; int32_t its = 0;
+    pcgParameters(params, "GpuLevenbergMarquardtOptimizer::solve", cg);
     rc = gtg_try_lambda_pcg(m.h, lambda, diagonal, dmin, dmax, cg, out, &its);
   } else {
     rc = gtg_try_lambda(m.h, lambda, diagonal, dmin, dmax, out);

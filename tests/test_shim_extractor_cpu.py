@@ -46,6 +46,55 @@ d = ref.load_g2o3d(%(data)r + "pose3example.txt")
 p = pose_graph_problem(len(d["vertex_keys"]), d["v1"], d["v2"], d["z"], d["noise_kind"], d["noise"])
 p.add_prior(0, d["vertex_poses"][0], p.add_noise(NOISE_DIAGONAL, 6, np.sqrt([1e-6] * 3 + [1e-4] * 3)))
 res["pose3slam_pose3example"] = records(p, d["vertex_poses"].reshape(-1))
+# tests/cpp/test_shim_extractor.cpp, mixedEveryBranch(): the same graph from the same literals through the wrapped API's mirror
+from gtsam_amd import api as A
+C, P, X, Lm = A.symbol_shorthand.C, A.symbol_shorthand.P, A.symbol_shorthand.X, A.symbol_shorthand.L
+Rz, Rx, Ry = A.Rot3([0, -1, 0, 1, 0, 0, 0, 0, 1]), A.Rot3([1, 0, 0, 0, 0, -1, 0, 1, 0]), A.Rot3([0, 0, 1, 0, 1, 0, -1, 0, 0])
+X0, X1, X2 = A.Pose3(A.Rot3(), [0, 0, 0]), A.Pose3(Rz, [1, 2, -3]), A.Pose3(Rx, [-0.5, 4, 0.25])
+T1, T2, T3 = A.Pose3(Rz, [1, 0, 0.5]), A.Pose3(Ry, [0, -2, 8]), A.Pose3(Rx, [0.125, 3, -1])
+S1, S2 = A.Pose3(Ry, [0.5, 0, 0]), A.Pose3(Rz, [0, 0.25, -0.125])
+Cam = A.PinholeCameraCal3Bundler
+cam = [Cam(X1, A.Cal3Bundler(512, 0.25, -0.125, 0, 0)), Cam(T2, A.Cal3Bundler(256, 0, 0.5, 2, -4)),
+       Cam(T3, A.Cal3Bundler(640, -0.0625, 0, 0, 0)), Cam(X2, A.Cal3Bundler(128, 0.5, 0.25, -1, 1))]
+iv = A.Values()
+for i in range(4): iv.insert(C(i), cam[i])
+iv.insert(P(0), A.Point3(1, -2, 3)); iv.insert(P(1), A.Point3(0.5, 0.25, 16)); iv.insert(P(2), A.Point3(-4, 7, 9))
+iv.insert(Lm(0), A.Point3(0.5, 0.25, -4)); iv.insert(Lm(1), A.Point3(2, 2, 32))
+iv.insert(X(0), X0); iv.insert(X(1), X1); iv.insert(X(2), X2)
+nm = A.noiseModel
+nA, nA2 = nm.Isotropic.Sigma(2, 0.5), nm.Isotropic.Sigma(2, 0.5)
+nH = nm.Robust.Create(nm.mEstimator.Huber.Create(1.5), nm.Isotropic.Sigma(2, 0.25))
+nU = nm.Unit.Create(2)
+R = 2.0 * np.eye(6); R[0, 1] = 0.5; R[0, 5] = -0.25; R[2, 3] = 1; R[4, 5] = 0.125
+nG = nm.Gaussian.SqrtInformation(R)
+sig = [0.5, 0.5, 0.5, 0.25, 0.25, 0.125]
+nD, nD2 = nm.Diagonal.Sigmas(sig), nm.Diagonal.Sigmas(sig)
+n9, n3, n3b, nS = nm.Isotropic.Sigma(9, 0.125), nm.Isotropic.Sigma(3, 0.5), nm.Isotropic.Sigma(3, 0.5), nm.Isotropic.Sigma(2, 2.0)
+K1, K2 = A.Cal3_S2(500, 400, 0.5, 320, 240), A.Cal3_S2(250, 250, 0, 160, 120)
+D1 = A.Cal3DS2(300, 350, 0.25, 100, 50, 0.125, -0.0625, 0.03125, 0.015625)
+Sfm, Proj, ProjDS2, Btw = A.GeneralSFMFactorCal3Bundler, A.GenericProjectionFactorCal3_S2, A.GenericProjectionFactorCal3DS2, A.BetweenFactorPose3
+SP, Smart = A.SmartProjectionParams, A.SmartProjectionFactorPinholeCameraCal3Bundler
+g = A.NonlinearFactorGraph()
+g.add(Sfm([1, 2], nA, C(0), P(0))); g.add(Sfm([-3, 4], nA, C(1), P(0))); g.add(Sfm([0.5, -1.5], nA, C(2), P(0)))
+g.add(Sfm([8, -2], nA, C(0), P(1))); g.add(Sfm([2.25, 1], nH, C(1), P(1))); g.add(Sfm([-7, 3], nH, C(2), P(1)))
+g.add(Sfm([4, 4], nA2, C(0), P(2))); g.add(Sfm([-0.75, 6], nA2, C(2), P(2)))
+sp1 = SP(SP.JACOBIAN_Q, SP.HANDLE_INFINITY); sp1.setRankTolerance(4)
+s1 = Smart(nA2, sp1); s1.add([1, 1], C(0)); s1.add([2, -1], C(1)); s1.add([-3, 0.5], C(2)); g.add(s1)
+sp2 = SP(SP.JACOBIAN_SVD, SP.ZERO_ON_DEGENERACY, 0.125)
+sp2.setRankTolerance(0.25); sp2.setLandmarkDistanceThreshold(64); sp2.setDynamicOutlierRejectionThreshold(8)
+s2 = Smart(nA, sp2); s2.add([5, 2], C(3)); s2.add([-1, -2], C(0)); g.add(s2)
+g.add(Proj([10, 20], nA, X(0), Lm(0), K1)); g.add(Proj([-5, 7.5], nA, X(1), Lm(0), K1, S1))
+g.add(Proj([3, -4], nU, X(2), Lm(0), K2, S2)); g.add(ProjDS2([6.5, 1], nU, X(0), Lm(1), D1)); g.add(ProjDS2([-2, -8], nA, X(1), Lm(1), D1, S1))
+g.add(Btw(X(0), X(1), T1, nG)); g.add(Btw(X(1), X(2), T2, nD)); g.add(Btw(X(0), X(2), T3, nG))
+g.add(Btw(X(2), X(1), T1, nD2)); g.add(Btw(X(1), X(0), T2, nG))
+g.addPriorPose3(X(0), X0, nD); g.addPriorPinholeCameraCal3Bundler(C(0), cam[0], n9)
+g.addPriorPoint3(P(0), A.Point3(1, -2, 3), n3); g.addPriorPoint3(Lm(0), A.Point3(0.5, 0.25, -4), n3b)
+s3 = Smart(nS); s3.add([0, 1], C(1)); s3.add([1, 0], C(2)); g.add(s3)
+g.addPriorPose3(X(2), X2, nD2); g.add(Btw(X(2), X(0), T3, nG)); g.add(Proj([1.5, 2.5], nU, X(2), Lm(1), K2, S2))
+g.add(Sfm([9, -9], nH, C(1), P(2))); g.add(Sfm([-6, 0.5], nA, C(3), P(2)))
+assert g.size() == 30
+pm, vm, _ = A.extract(g, iv)
+res["mixed_every_branch"] = records(pm, vm)
 print("RESULT " + json.dumps(res))
 '''
 
@@ -74,7 +123,7 @@ def test_cpp_and_python_extractors_hand_the_library_identical_tables():
     cases = lambda out: [(ln.split()[1], sorted(ln.split()[2:])) for ln in out.splitlines() if ln.startswith("CASE ")]
     assert cases(r_mt.stdout) == cases(r.stdout)
     py = HP.run_snippet(_CHILD % {"root": ROOT, "data": DATA})
-    assert set(cpp) == set(py) == {"sfmexample_bal_dubrovnik_3_7", "pose2slam_w100", "pose3slam_pose3example"}
+    assert set(cpp) == set(py) == {"sfmexample_bal_dubrovnik_3_7", "pose2slam_w100", "pose3slam_pose3example", "mixed_every_branch"}
     for name in cpp:
         assert len(cpp[name]) > 30
         assert sorted(cpp[name]) == sorted(py[name]), name
