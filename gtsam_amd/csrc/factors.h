@@ -69,7 +69,13 @@ constexpr int kPriorRec = 81 + 9;            // [A dxd packed | pad ... | b d at
 // NOTE (reference behaviour, reproduced on purpose): GeneralSFMFactor::linearize whitens H1, H2 and b through
 // noiseModel->Whiten(Matrix) separately (GeneralSFMFactor.h:162-168); for a Robust model that path re-weights with
 // an EMPTY error vector, i.e. weight 1 -- the m-estimator changes this factor's error(), not its linear system.
+// The record must be the SAME DOUBLES in every kernel that inlines this function (k_lin_sfm and, since the fused linearisation, k_cam_fused,
+// k_lm_fused, k_obs_E, k_obs_v, the PCG kernels and the debug getter): H_cc, V and W = Jc^T Jp are then blocks of ONE J^T J, and
+// gtg_get_jacobians returns what was summed.  Left to itself the compiler contracts multiply-adds differently per kernel -- one rounding
+// of pi is hundreds of ulps of b = z - pi -- so contraction is off here and in what this calls (geom.h: sfm_project, project2,
+// mat3_tvec, whiten_cols); tests/test_gpu_reduced_system.py holds the sums to the summation bound on that ground.
 GT_HD void sfm_linearize(const double* cam, const double* pt, const double* z, const NoiseRef& n, double* J) {
+  _Pragma("clang fp contract(off)")
   const int nkind = n.kind; const double* nd = n.data;
   double pi[2];
   if (!sfm_project(cam, pt, pi, J, J + 18)) {  // CheiralityException: H1,H2,b = 0 (:153-158)

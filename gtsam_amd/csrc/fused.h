@@ -7,8 +7,8 @@
 // that needs it: a lane gathers its camera (17 doubles out of the L2-resident camera table), its point and its measurement -- 52 bytes
 // of HBM traffic per factor instead of 208 -- and evaluates factors.h::sfm_linearize in place.  The record is a pure function of
 // (values, measurement, noise row); k_lin_sfm's output is compared bit for bit with the stored-record build (tests/test_gpu_fused_linearization.py),
-// and the step of the fused build with that build's.  (Between the six kernels that inline sfm_linearize the compiler is free to contract
-// FMAs differently: they agree to rounding, not necessarily to the bit -- nothing relies on more.)
+// and the step of the fused build with that build's.  Every kernel that inlines sfm_linearize gets the same doubles: FMA contraction is off
+// inside it (factors.h), so the sums of tests/test_gpu_reduced_system.py can be held to the summation bound against gtg_get_jacobians' records.
 //
 // Not for graphs with smart factors: the records of their measurements depend on the triangulation status of the factor and are
 // overwritten by a second kernel for points at infinity (factors.hip) -- those graphs keep the stored records.

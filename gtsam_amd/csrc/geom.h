@@ -38,6 +38,7 @@ GT_HD void mat3_vec(const double* A, const double* x, double* y) {
   for (int i = 0; i < 3; i++) y[i] = A[3 * i] * x[0] + A[3 * i + 1] * x[1] + A[3 * i + 2] * x[2];
 }
 GT_HD void mat3_tvec(const double* A, const double* x, double* y) {  // y = A^T x
+  _Pragma("clang fp contract(off)")   // bit-reproducible wherever it is inlined: see sfm_linearize (factors.h)
   for (int i = 0; i < 3; i++) y[i] = A[i] * x[0] + A[3 + i] * x[1] + A[6 + i] * x[2];
 }
 GT_HD void skew3(double x, double y, double z, double* W) {  // skewSymmetric (base/Matrix.h)
@@ -193,6 +194,7 @@ GT_HD void pose_local(const double* A, const double* B, double* xi) {
 // Returns false on a CheiralityException (q.z <= 0, GTSAM_THROW_CHEIRALITY_EXCEPTION default ON).
 // Dpose 2x6, Dpoint 2x3 row-major; pass nullptr to skip derivatives.
 GT_HD bool project2(const double* T, const double* pw, double* pn, double* Dpose, double* Dpoint) {
+  _Pragma("clang fp contract(off)")   // bit-reproducible wherever it is inlined: see sfm_linearize (factors.h)
   const double dx[3] = {pw[0] - T[9], pw[1] - T[10], pw[2] - T[11]};
   double q[3];
   mat3_tvec(T, dx, q);
@@ -218,6 +220,7 @@ GT_HD bool project2(const double* T, const double* pw, double* pn, double* Dpose
 // (PinholePose.h:89-109) + Cal3Bundler::uncalibrate (Cal3Bundler.cpp:66-92).
 // cam = pose(12), f, k1, k2, u0, v0.  Dcam 2x9 = [Dp*Dpose | Dcal], Dpoint 2x3 (row-major).
 GT_HD bool sfm_project(const double* cam, const double* pw, double* pi, double* Dcam, double* Dpoint) {
+  _Pragma("clang fp contract(off)")   // bit-reproducible wherever it is inlined: see sfm_linearize (factors.h)
   double pn[2], Dpose[12], Dpt[6];
   // (both derivative buffers or none: a conditionally selected pointer keeps the local arrays in scratch memory on the device)
   const bool want = Dcam || Dpoint;
@@ -611,6 +614,7 @@ enum { kNoiseUnit = 0, kNoiseIsotropic = 1, kNoiseDiagonal = 2, kNoiseGaussian =
 //   Unit no-op; Isotropic v*invsigma (:641-663); Diagonal v.*invsigmas (:311-325); Gaussian R*v (:163-181)
 template <int M>
 GT_HD void whiten_cols(int kind, const double* nd, double* A, int ncols) {
+  _Pragma("clang fp contract(off)")   // bit-reproducible wherever it is inlined: see sfm_linearize (factors.h)
   if (kind == kNoiseUnit) return;
   if (kind == kNoiseIsotropic) {
     const double s = nd[0];
