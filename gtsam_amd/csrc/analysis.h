@@ -1,4 +1,5 @@
-// analysis.h -- the one-time host-side symbolic analysis of a graph (analysis.hip) and the few helpers it shares with the C ABI.
+// analysis.h -- the one-time host-side symbolic analysis of a graph (analysis.hip), the upload of the factor tables in front of it
+// (upload.hip) and the few helpers they share with the C ABI (api.hip).
 #pragma once
 #include <chrono>
 #include <cstdio>
@@ -43,5 +44,7 @@ HostIndex& host_index(gtg_context* c);     // the handle's host-side index array
 // of the Cholesky, device buffers; sharded handles derive the layout from the whole graph and verify it across the shards
 void analyze(gtg_context& c);
 void verify_layout(gtg_context& c);
+// gtg_upload_problem behind its argument checks (upload.hip): the handle holds no problem while it runs, the whole one when it returns
+void upload_problem(gtg_context& c, const gtg_problem& user, int shard, int n_shards);
 
 }  // namespace gt

@@ -1,15 +1,13 @@
-// api.hip -- the C ABI (include/gtsam_amd.h): handle life cycle, upload of the factor tables (shard filter, noise table),
-// the per-iteration entry points (linearize / try_lambda / accept) that issue the HIP kernels, getters and test hooks.
-// The one-time symbolic analysis of a graph is analysis.hip, what a handle owns on its device and how it is released
+// api.hip -- the C ABI (include/gtsam_amd.h): handle life cycle, the per-iteration entry points (linearize / try_lambda / accept)
+// that issue the HIP kernels, getters and test hooks.  The upload of the factor tables (shard filter, noise table) is upload.hip,
+// the one-time symbolic analysis of a graph analysis.hip, what a handle owns on its device and how it is released
 // device_memory.hip.  All arithmetic of the hot path runs in the HIP kernels.
 #include <algorithm>
 #include <atomic>
-#include <exception>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <thread>
 #include <cstring>
 #include <limits>
 #include <map>
@@ -22,11 +20,6 @@
 #include "factors.h"
 #include "kernels.h"
 
-// GTG_FUSED_SFM=0 at compile time builds the stored-record form of rounds 1-4 for every graph (the A/B of the fused linearisation,
-// `make records`); the product library is built with 1
-#ifndef GTG_FUSED_SFM
-#define GTG_FUSED_SFM 1
-#endif
 namespace gt {
 
 // gtg_prewarm's registry (kernels.h): filled by the static PrewarmUnit objects of the translation units
@@ -97,7 +90,7 @@ static void check_smart_supported(gtg_context& c, const char* where) {
 
 struct PhaseTimer {
   gtg_context& c; int ph; hipEvent_t a, b;
-  PhaseTimer(gtg_context& c_, int ph_, hipEvent_t* evs) : c(c_), ph(ph_), a(evs[2 * ph_]), b(evs[2 * ph_ + 1]) {
+  PhaseTimer(gtg_context& c_, int ph_) : c(c_), ph(ph_), a(c_.phase_events[2 * ph_]), b(c_.phase_events[2 * ph_ + 1]) {
     if (c.timing) (void)hipEventRecord(a, c.stream);
   }
   ~PhaseTimer() { if (c.timing) (void)hipEventRecord(b, c.stream); }
@@ -213,269 +206,7 @@ int gtg_upload_problem(gtg_handle c, const gtg_problem* p_user, int shard, int n
   if (!c || !p_user) throw std::invalid_argument("null argument");
   if (n_shards < 1 || shard < 0 || shard >= n_shards) throw std::invalid_argument("bad shard / n_shards");
   DeviceGuard on_device(c->device);
-  StageClock clk;
-  hipStream_t s = c->stream;
-  c->shard = shard; c->n_shards = n_shards;
-  // Smart factors become what the rest of the library already knows: a hidden POINT3 variable per factor behind the caller's
-  // variables and one GeneralSFM observation per measurement behind the caller's; the tables below are built from this view.
-  gtg_problem q = *p_user;
-  const gtg_problem* p = &q;
-  std::vector<int32_t> x_var_type, x_sfm_cam, x_sfm_point, x_sfm_noise, x_of_obs;
-  std::vector<double> x_sfm_z;
-  const int64_t n_smart = p_user->n_smart > 0 ? p_user->n_smart : 0;
-  c->n_smart = n_smart; c->n_user_vars = p_user->n_vars; c->smart_obs0 = p_user->n_sfm;
-  // GeneralSFM records recomputed where they are needed instead of stored (fused.h) -- not with smart factors, whose measurements'
-  // records depend on the factor's triangulation status
-  c->fused_sfm = GTG_FUSED_SFM != 0 && n_smart == 0;
-  if (n_smart) {
-    if (!p_user->smart_ptr || !p_user->smart_cam || !p_user->smart_z || !p_user->smart_noise || !p_user->smart_params)
-      throw std::invalid_argument("smart factor tables missing");
-    const int64_t n_meas = p_user->smart_ptr[n_smart];
-    x_var_type.assign(p_user->var_type, p_user->var_type + p_user->n_vars); x_var_type.resize((size_t)p_user->n_vars + n_smart, GTG_VAR_POINT3);
-    x_sfm_cam.assign(p_user->sfm_cam, p_user->sfm_cam + p_user->n_sfm); x_sfm_point.assign(p_user->sfm_point, p_user->sfm_point + p_user->n_sfm);
-    x_sfm_noise.assign(p_user->sfm_noise, p_user->sfm_noise + p_user->n_sfm); x_sfm_z.assign(p_user->sfm_z, p_user->sfm_z + 2 * p_user->n_sfm);
-    std::vector<int32_t> of_obs((size_t)p_user->n_sfm, -1);
-    // the device addresses a factor's measurements as smart_obs0 + smart_ptr[i] while the expanded observations are appended one
-    // after the other: the offsets must start at 0 and be strictly increasing
-    if (p_user->smart_ptr[0] != 0) throw std::invalid_argument("smart factors: smart_ptr[0] must be 0");
-    for (int64_t i = 0; i < n_smart; i++) {
-      const int64_t k0 = p_user->smart_ptr[i], k1 = p_user->smart_ptr[i + 1];
-      if (k1 <= k0 || k1 > n_meas) throw std::invalid_argument("smart factor without measurements / bad smart_ptr");
-      const double* sp = p_user->smart_params + 8 * i;
-      if (!(sp[4] == 0.0 || sp[4] == 1.0 || sp[4] == 2.0)) throw std::invalid_argument("smart factor: unknown degeneracy mode");
-      if (!(sp[6] == 0.0 || sp[6] == 1.0)) throw std::invalid_argument("smart factor: enableEPI must be 0 or 1");
-      // LinearizationMode (SmartFactorParams.h:31-33): HESSIAN, JACOBIAN_Q, JACOBIAN_SVD give the same normal equations (they differ in
-      // what a failed track contributes and in the constant of the linear error); IMPLICIT_SCHUR factors cannot be eliminated by
-      // the reference's direct solvers at all (RegularImplicitSchurFactor has no augmentedJacobian / augmentedInformation)
-      if (!(sp[5] == 0.0 || sp[5] == 2.0 || sp[5] == 3.0)) throw std::invalid_argument("smart factor: linearization mode must be 0 HESSIAN, 2 JACOBIAN_Q or 3 JACOBIAN_SVD");
-      // rankTolerance, landmarkDistanceThreshold, dynamicOutlierRejectionThreshold (negative = off, as in the reference),
-      // retriangulationThreshold: numbers, not NaN / inf (a NaN threshold silently disables the test it guards)
-      for (int e = 0; e < 4; e++) if (!std::isfinite(sp[e])) throw std::invalid_argument("smart factor: a threshold is not finite");
-      // the reference requires an isotropic model (SmartFactorBase.h:107-114: "SmartFactorBase: needs isotropic")
-      const int32_t nz = p_user->smart_noise[i];
-      if (nz < 0 || nz >= p_user->n_noise || p_user->noise_dim[nz] != 2 ||
-          !(p_user->noise_kind[nz] == GTG_NOISE_UNIT || p_user->noise_kind[nz] == GTG_NOISE_ISOTROPIC))
-        throw std::invalid_argument("smart factor: smart_noise must index a dim-2 Unit or Isotropic noise model");
-      for (int64_t k = k0; k < k1; k++) {
-        const int cam = p_user->smart_cam[k];
-        if (cam < 0 || cam >= p_user->n_vars || p_user->var_type[cam] != GTG_VAR_SFM_CAMERA)
-          throw std::invalid_argument("smart factor: its keys must be SFM_CAMERA variables");
-        x_sfm_cam.push_back(cam); x_sfm_point.push_back((int32_t)(p_user->n_vars + i)); x_sfm_noise.push_back(p_user->smart_noise[i]);
-        x_sfm_z.push_back(p_user->smart_z[2 * k]); x_sfm_z.push_back(p_user->smart_z[2 * k + 1]);
-        of_obs.push_back((int32_t)i);
-      }
-    }
-    q.n_vars = (int32_t)x_var_type.size(); q.var_type = x_var_type.data();
-    q.n_sfm = (int64_t)x_sfm_cam.size(); q.sfm_cam = x_sfm_cam.data(); q.sfm_point = x_sfm_point.data();
-    q.sfm_noise = x_sfm_noise.data(); q.sfm_z = x_sfm_z.data();
-    std::vector<double> prm(p_user->smart_params, p_user->smart_params + 8 * n_smart);
-    up(c->smart_params, prm, s);
-    x_of_obs = std::move(of_obs);           // (smart_ptr and sfm_smart follow the shard filter of the observation table below)
-    std::vector<int32_t> none((size_t)n_smart, -1);
-    up(c->smart_cache_state, none, s);
-    c->smart_status.alloc((size_t)n_smart); c->smart_lin_status.alloc((size_t)n_smart); c->smart_cache_point.alloc(3 * (size_t)n_smart); c->smart_cache_pose.alloc(12 * (size_t)n_meas);
-    check_hip(hipMemsetAsync(c->smart_status.p, 0, sizeof(int32_t) * n_smart, s), "memset");
-    check_hip(hipMemsetAsync(c->smart_lin_status.p, 0, sizeof(int32_t) * n_smart, s), "memset");
-  } else {
-    c->smart_ptr.free(); c->smart_params.free(); c->sfm_smart.free(); c->lm_smart.free(); c->smart_status.free(); c->smart_lin_status.free();
-    c->smart_cache_state.free(); c->smart_cache_pose.free(); c->smart_cache_point.free();
-  }
-  c->n_vars = p->n_vars;
-  c->h_var_type.assign(p->var_type, p->var_type + p->n_vars);
-  c->h_val_off.assign(p->n_vars + 1, 0); c->h_dim_off.assign(p->n_vars + 1, 0);
-  for (int v = 0; v < p->n_vars; v++) {
-    const int t = p->var_type[v];
-    if (t < 0 || t > GTG_VAR_POSE2) throw std::invalid_argument("unknown variable type");
-    c->h_val_off[v + 1] = c->h_val_off[v] + storage_size(t);
-    c->h_dim_off[v + 1] = c->h_dim_off[v] + tangent_dim(t);
-  }
-  c->val_size = c->h_val_off[p->n_vars]; c->dim_size = c->h_dim_off[p->n_vars];
-  c->user_val_size = c->h_val_off[c->n_user_vars]; c->user_dim_size = c->h_dim_off[c->n_user_vars];
-  up(c->var_type, c->h_var_type, s); up(c->val_off, c->h_val_off, s); up(c->dim_off, c->h_dim_off, s);
-  c->values.alloc(std::max<int64_t>(c->val_size, 1)); c->trial.alloc(std::max<int64_t>(c->val_size, 1));
-  c->delta.alloc(std::max<int64_t>(c->dim_size, 1));
-  check_hip(hipMemsetAsync(c->delta.p, 0, sizeof(double) * c->delta.n, s), "memset");
-
-  // noise table: derive the inverse sigmas like the reference constructors (NoiseModel.cpp:275-281, Isotropic ctor)
-  {
-    std::vector<int32_t> kind(p->noise_kind, p->noise_kind + p->n_noise);
-    std::vector<int64_t> noff(p->n_noise);
-    std::vector<double> data;
-    for (int i = 0; i < p->n_noise; i++) {
-      const int dim = p->noise_dim[i];
-      const double* d = p->noise_data + p->noise_off[i];
-      noff[i] = (int64_t)data.size();
-      switch (kind[i]) {
-        case GTG_NOISE_UNIT: data.push_back(0.0); break;
-        case GTG_NOISE_ISOTROPIC: data.push_back(1.0 / d[0]); break;
-        case GTG_NOISE_DIAGONAL: for (int k = 0; k < dim; k++) data.push_back(1.0 / d[k]); break;
-        case GTG_NOISE_GAUSSIAN: for (int k = 0; k < dim * dim; k++) data.push_back(d[k]); break;
-        default: throw std::invalid_argument("unsupported noise model kind (Robust/Constrained are out of scope)");
-      }
-    }
-    std::vector<int32_t> rkind(p->n_noise, GTG_ROBUST_NONE);
-    std::vector<double> rk(p->n_noise, 0.0);
-    for (int i = 0; i < p->n_noise; i++) {
-      if (p->noise_robust) rkind[i] = p->noise_robust[i];
-      if (rkind[i] < GTG_ROBUST_NONE || rkind[i] > GTG_ROBUST_L2WITHDEADZONE) throw std::invalid_argument("unsupported m-estimator");
-      if (rkind[i] != GTG_ROBUST_NONE) {
-        rk[i] = p->noise_robust_param ? p->noise_robust_param[i] : 0.0;
-        if (!(rk[i] > 0.0)) throw std::invalid_argument("m-estimator parameter must be > 0");   // LossFunctions.cpp ctor checks
-      }
-    }
-    up(c->noise_kind, kind, s); up(c->noise_off, noff, s); up(c->noise_data, data, s);
-    up(c->noise_rkind, rkind, s); up(c->noise_rk, rk, s);
-  }
-  auto check_noise = [&](int idx, int dim, const char* what) {
-    if (idx < 0 || idx >= p->n_noise || p->noise_dim[idx] != dim)
-      throw std::invalid_argument(std::string(what) + ": NoiseModel has wrong dimension");  // NonlinearFactor.cpp:97-104
-  };
-  auto check_var = [&](int v) { if (v < 0 || v >= p->n_vars) throw std::invalid_argument("factor refers to a key that is not in Values"); };
-
-  HostIndex& hi = host_index(c);
-  auto& f = c->f;
-  // shard filter: landmark factors follow their landmark (rank among POINT3 variables), others round-robin
-  std::vector<int32_t> lm_rank(p->n_vars, -1);
-  { int k = 0; for (int v = 0; v < p->n_vars; v++) if (p->var_type[v] == GTG_VAR_POINT3) lm_rank[v] = k++; }
-  auto own_lm = [&](int v) { return lm_rank[v] >= 0 && (lm_rank[v] % n_shards) == shard; };
-
-  hi.all_obs_red_var.clear(); hi.all_obs_point.clear(); hi.all_between_v1.clear(); hi.all_between_v2.clear();
-  if (n_shards > 1) {
-    for (int64_t i = 0; i < p->n_sfm; i++) { check_var(p->sfm_cam[i]); check_var(p->sfm_point[i]); }
-    for (int64_t i = 0; i < p->n_proj; i++) { check_var(p->proj_pose[i]); check_var(p->proj_point[i]); }
-    for (int64_t i = 0; i < p->n_between; i++) { check_var(p->between_v1[i]); check_var(p->between_v2[i]); }
-    hi.all_obs_red_var.assign(p->sfm_cam, p->sfm_cam + p->n_sfm); hi.all_obs_red_var.insert(hi.all_obs_red_var.end(), p->proj_pose, p->proj_pose + p->n_proj);
-    hi.all_obs_point.assign(p->sfm_point, p->sfm_point + p->n_sfm); hi.all_obs_point.insert(hi.all_obs_point.end(), p->proj_point, p->proj_point + p->n_proj);
-    hi.all_between_v1.assign(p->between_v1, p->between_v1 + p->n_between); hi.all_between_v2.assign(p->between_v2, p->between_v2 + p->n_between);
-  }
-  std::thread side_upload; std::exception_ptr side_err;
-  struct JoinSide { std::thread& t; ~JoinSide() { if (t.joinable()) t.join(); } } join_side{side_upload};
-  { // SFM
-    std::vector<int32_t> cam, pt, nz; std::vector<double> z;
-    for (int64_t i = 0; i < p->n_sfm; i++) { check_var(p->sfm_cam[i]); check_var(p->sfm_point[i]); check_noise(p->sfm_noise[i], 2, "GeneralSFMFactor"); }
-    const bool whole = n_shards == 1 && p->n_sfm > 0;   // the whole table: noise rows and measurements go up straight from the caller's arrays
-    if (n_shards == 1) {
-      cam.assign(p->sfm_cam, p->sfm_cam + p->n_sfm); pt.assign(p->sfm_point, p->sfm_point + p->n_sfm);   // (kept by the host index: gtg_set_reduced_ordering analyses again)
-      if (!whole) { nz.assign(p->sfm_noise, p->sfm_noise + p->n_sfm); z.assign(p->sfm_z, p->sfm_z + 2 * p->n_sfm); }
-    } else {
-      for (int64_t i = 0; i < p->n_sfm; i++) {
-        if (!own_lm(p->sfm_point[i])) continue;
-        cam.push_back(p->sfm_cam[i]); pt.push_back(p->sfm_point[i]); nz.push_back(p->sfm_noise[i]);
-        z.push_back(p->sfm_z[2 * i]); z.push_back(p->sfm_z[2 * i + 1]);
-      }
-    }
-    if (n_smart) {
-      // Sharded, a smart factor follows its hidden landmark like any landmark factor: this shard holds the measurements of the
-      // tracks it owns, in the order of the whole table.  The per-factor arrays keep the GLOBAL factor index (parameters, status,
-      // cache); a factor of another shard has no measurements here (smart_ptr[i + 1] == smart_ptr[i]) and is skipped.
-      std::vector<int64_t> rel((size_t)n_smart + 1, 0);
-      std::vector<int32_t> of_local;
-      int64_t obs0 = 0;
-      for (int64_t i = 0; i < p->n_sfm; i++) {
-        if (n_shards > 1 && !own_lm(p->sfm_point[i])) continue;
-        const int32_t sf = x_of_obs[(size_t)i];
-        of_local.push_back(sf);
-        if (sf < 0) obs0++; else rel[(size_t)sf + 1]++;
-      }
-      for (int64_t i = 0; i < n_smart; i++) rel[(size_t)i + 1] += rel[(size_t)i];
-      c->smart_obs0 = obs0;
-      up(c->smart_ptr, rel, s);
-      up(c->sfm_smart, of_local, s);
-    }
-    f.n_sfm = (int64_t)cam.size();
-    up(f.sfm_cam, cam, s); up(f.sfm_point, pt, s);
-    if (whole) {
-      // the noise rows and the measurements (20 bytes per factor: 13.5 MB on the L1723 shape, 1.2 ms from pageable memory) are not read by
-      // the symbolic analysis: they go up on a helper thread and the handle's copy stream beside it (joined below, before this call returns)
-      f.sfm_noise.alloc((size_t)p->n_sfm); f.sfm_z.alloc(2 * (size_t)p->n_sfm);
-      const int dev = c->device; hipStream_t cs = c->copy_stream;
-      int32_t* d_nz = f.sfm_noise.p; double* d_z = f.sfm_z.p;
-      const int32_t* h_nz = p->sfm_noise; const double* h_z = p->sfm_z; const size_t n = (size_t)p->n_sfm;
-      side_upload = std::thread([dev, cs, d_nz, d_z, h_nz, h_z, n, &side_err] {
-        try {
-          check_hip(hipSetDevice(dev), "hipSetDevice");
-          check_hip(hipMemcpyAsync(d_nz, h_nz, sizeof(int32_t) * n, hipMemcpyHostToDevice, cs), "H2D");
-          check_hip(hipMemcpyAsync(d_z, h_z, sizeof(double) * 2 * n, hipMemcpyHostToDevice, cs), "H2D");
-          check_hip(hipStreamSynchronize(cs), "sync");
-        } catch (...) { side_err = std::current_exception(); }
-      });
-    }
-    else { up(f.sfm_noise, nz, s); up(f.sfm_z, z, s); }
-    if (c->val_size >= (int64_t)1 << 31) throw std::invalid_argument("gtg_upload_problem: more than 2^31 packed value entries");
-    f.sfm_cam_at.alloc(std::max<size_t>(cam.size(), 1)); f.sfm_point_at.alloc(std::max<size_t>(pt.size(), 1));
-    launch_sfm_value_offsets(*c);     // where each factor's camera / point start in the packed values (a gather through val_off, on the device)
-    f.sfm_J.alloc(c->fused_sfm ? 1 : std::max<size_t>((size_t)kSfmRec * f.n_sfm, 1));
-    hi.sfm_cam = std::move(cam); hi.sfm_point = std::move(pt);
-  }
-  { // projection
-    std::vector<int32_t> pose, pt, nz, cal, sen; std::vector<double> z;
-    for (int64_t i = 0; i < p->n_proj; i++) {
-      check_var(p->proj_pose[i]); check_var(p->proj_point[i]); check_noise(p->proj_noise[i], 2, "GenericProjectionFactor");
-      if (p->proj_calib[i] < 0 || p->proj_calib[i] >= p->n_calib) throw std::invalid_argument("bad calibration index");
-      const int si = p->proj_sensor ? p->proj_sensor[i] : -1;
-      if (si >= p->n_sensor) throw std::invalid_argument("bad body_P_sensor index");
-      if (n_shards > 1 && !own_lm(p->proj_point[i])) continue;
-      pose.push_back(p->proj_pose[i]); pt.push_back(p->proj_point[i]); nz.push_back(p->proj_noise[i]);
-      cal.push_back(p->proj_calib[i]); sen.push_back(si);
-      z.push_back(p->proj_z[2 * i]); z.push_back(p->proj_z[2 * i + 1]);
-    }
-    f.n_proj = (int64_t)pose.size();
-    up(f.proj_pose, pose, s); up(f.proj_point, pt, s); up(f.proj_noise, nz, s); up(f.proj_calib, cal, s);
-    up(f.proj_sensor, sen, s); up(f.proj_z, z, s);
-    // device calibration table: 9 per entry, fx fy s u0 v0 k1 k2 p1 p2 (the distortion part zero for a Cal3_S2)
-    std::vector<double> calib(kCalibStride * (size_t)p->n_calib, 0.0), sensor(p->sensor, p->sensor + 12 * (size_t)p->n_sensor);
-    for (int32_t k = 0; k < p->n_calib; k++) {
-      for (int j = 0; j < 5; j++) calib[kCalibStride * (size_t)k + j] = p->calib[5 * (size_t)k + j];
-      if (p->calib_distortion) for (int j = 0; j < 4; j++) calib[kCalibStride * (size_t)k + 5 + j] = p->calib_distortion[4 * (size_t)k + j];
-    }
-    up(f.calib, calib, s); up(f.sensor, sensor, s);
-    f.proj_J.alloc(std::max<size_t>((size_t)kProjRec * f.n_proj, 1));
-    hi.proj_pose = pose; hi.proj_point = pt;
-  }
-  { // between
-    std::vector<int32_t> v1, v2, nz; std::vector<double> z;
-    for (int64_t i = 0; i < p->n_between; i++) {
-      check_var(p->between_v1[i]); check_var(p->between_v2[i]);
-      check_noise(p->between_noise[i], tangent_dim(p->var_type[p->between_v1[i]]), "BetweenFactor");
-      if (n_shards > 1 && (i % n_shards) != shard) continue;
-      v1.push_back(p->between_v1[i]); v2.push_back(p->between_v2[i]); nz.push_back(p->between_noise[i]);
-      for (int k = 0; k < 12; k++) z.push_back(p->between_z[12 * i + k]);
-    }
-    f.n_between = (int64_t)v1.size();
-    up(f.between_v1, v1, s); up(f.between_v2, v2, s); up(f.between_noise, nz, s); up(f.between_z, z, s);
-    f.between_J.alloc(std::max<size_t>((size_t)kBetweenRec * f.n_between, 1));
-    hi.between_v1 = v1; hi.between_v2 = v2;
-  }
-  { // priors
-    std::vector<int32_t> var, nz; std::vector<int64_t> poff; std::vector<double> data;
-    for (int64_t i = 0; i < p->n_prior; i++) {
-      const int v = p->prior_var[i];
-      check_var(v); check_noise(p->prior_noise[i], tangent_dim(p->var_type[v]), "PriorFactor");
-      const bool mine = lm_rank[v] >= 0 ? own_lm(v) : ((i % n_shards) == shard);
-      if (n_shards > 1 && !mine) continue;
-      var.push_back(v); nz.push_back(p->prior_noise[i]); poff.push_back((int64_t)data.size());
-      const double* d = p->prior_data + p->prior_off[i];
-      for (int k = 0; k < storage_size(p->var_type[v]); k++) data.push_back(d[k]);
-    }
-    f.n_prior = (int64_t)var.size();
-    up(f.prior_var, var, s); up(f.prior_noise, nz, s); up(f.prior_off, poff, s); up(f.prior_data, data, s);
-    f.prior_J.alloc(std::max<size_t>((size_t)kPriorRec * f.n_prior, 1));
-    hi.prior_var = var;
-  }
-  clk.lap("factor tables (shard filter + upload)");
-  analyze(*c);
-  if (side_upload.joinable()) side_upload.join();
-  if (side_err) std::rethrow_exception(side_err);
-  if (c->n_smart) {   // landmark index of every smart factor's hidden variable
-    std::vector<int32_t> lm_smart((size_t)std::max(c->n_lm, 1), -1);
-    for (int64_t i = 0; i < c->n_smart; i++) {
-      const int l = c->h_lm_index[c->n_user_vars + i];
-      if (l < 0) throw std::runtime_error("smart factor: its hidden landmark was not classified as a landmark");
-      lm_smart[(size_t)l] = (int32_t)i;
-    }
-    up(c->lm_smart, lm_smart, s);
-    check_hip(hipStreamSynchronize(s), "sync");
-  }
+  upload_problem(*c, *p_user, shard, n_shards);
   c->uploaded = true; c->linearized = false; c->have_trial = false;
   return GTG_OK;
   GTG_CATCH
@@ -524,7 +255,7 @@ int gtg_error(gtg_handle c, double* error) {
   if (!c || !c->uploaded || !error) throw std::invalid_argument("gtg_error: no problem uploaded");
   DeviceGuard on_device(c->device);
   if (c->n_smart) check_hip(hipMemsetAsync(c->scalars.p + SC_UNSUPPORTED, 0, sizeof(double), c->stream), "memset");
-  { PhaseTimer t(*c, GTG_PH_ERROR, c->phase_events.data()); launch_smart_triangulate(*c, c->values.p, nullptr, false); launch_error(*c, c->values.p, SC_ERROR); }
+  { PhaseTimer t(*c, GTG_PH_ERROR); launch_smart_triangulate(*c, c->values.p, nullptr, false); launch_error(*c, c->values.p, SC_ERROR); }
   read_scalars(*c);
   collect(*c, {GTG_PH_ERROR});
   check_smart_supported(*c, "gtg_error");
@@ -548,15 +279,90 @@ struct FirstCallClock {
 };
 static std::atomic<int> g_first_linearize{0}, g_first_try{0};
 
+// ---- the pieces gtg_try_lambda and gtg_try_lambda_pcg are made of ------------------------------------------------------------
+// Sharded: the one big exchange, reduced Hessian + rhs summed over the shards in place
+static void exchange_reduced_system(gtg_context& c) {
+  if (c.n_shards == 1) return;
+  if (c.n_xb == 0) {     // (no block list: whole stored 128x128 tiles, the first version of the exchange)
+    const int64_t nb = c.plan.n_exch * kTile * kTile;
+    if ((int64_t)c.xbuf.n != nb) c.xbuf.alloc(nb);
+    launch_pack_tiles(c, smat(c), c.plan, c.xbuf.p, false);
+    exchange(c, c.xbuf.p, nb);
+    launch_pack_tiles(c, smat(c), c.plan, c.xbuf.p, true);
+  } else {                // only the structurally non-zero d x d blocks (the same list on every shard) + rhs row + padding
+    const int64_t nb = exchange_block_doubles(c);
+    if ((int64_t)c.xbuf.n != nb) c.xbuf.alloc(nb);
+    launch_pack_blocks(c, smat(c), c.NP, c.xbuf.p, false);
+    exchange(c, c.xbuf.p, nb);
+    launch_pack_blocks(c, smat(c), c.NP, c.xbuf.p, true);
+  }
+}
+
+// post-mortem of a try (number `attempt`, dataflow schedule or not) that is about to be repeated: which wait gave up
+// (chol_dataflow.hip::wait_flags records the first one of a dataflow pass), what it saw, and what the same words hold in memory NOW,
+// read from the host after the kernels have drained.  GTG_QUIET: nothing
+static void report_wait_timeout(gtg_context& c, bool df, int attempt) {
+  static const bool quiet = std::getenv("GTG_QUIET") != nullptr;
+  if (quiet) return;
+  int32_t ctl[16] = {0};
+  long long now1 = -1, now2 = -1;
+  const int nt = c.NP / kTile;
+  if (df && c.df.ctrl.p) {
+    (void)hipMemcpy(ctl, c.df.ctrl.p, sizeof(ctl), hipMemcpyDeviceToHost);
+    const int kind = ctl[8], I = ctl[9], J = ctl[10], k = ctl[11];
+    const long long *w1 = nullptr, *w2 = nullptr;
+    // (flag words are indexed by tile slot; kinds 1 / 2 record the SLOT of the first operand tile in k)
+    auto slot_of = [&](int a, int b) { return (a >= 0 && a <= nt && b >= 0 && b < nt) ? (int64_t)c.plan.h_slot[(size_t)a * nt + b] : (int64_t)-1; };
+    if (kind == 1 || kind == 2) { if (k >= 0 && k < c.plan.n_stored) w1 = w2 = c.df.tile_flag.p + k; }
+    else if (kind == 3 && slot_of(J, J) >= 0) w1 = w2 = c.df.tile_flag.p + slot_of(J, J);
+    else if (kind == 4) w1 = w2 = c.df.pd_flag.p + I;
+    else if (kind == 5 && slot_of(I, J) >= 0) w1 = w2 = c.df.tile_flag.p + slot_of(I, J);
+    else if (kind == 7 && slot_of(I, J) >= 0) w1 = w2 = c.df.part_flag.p + slot_of(I, J);
+    if (w1) { (void)hipMemcpy(&now1, w1, 8, hipMemcpyDeviceToHost); (void)hipMemcpy(&now2, w2, 8, hipMemcpyDeviceToHost); }
+  }
+  std::fprintf(stderr, "[gtsam_amd] %s factorisation (epoch %lld): a dependency wait ran into its bound; repeating the lambda try with the %s "
+               "schedule.  wait kind %d at (%d, %d, %d): saw %d / %d, wanted %d / %d; memory now holds %lld / %lld; waiter on XCD %d (hw id 0x%x); "
+               "tickets taken %d, diagonal tiles started %d of %d; over this handle's life: waits that ended on the shadow words %d, on the read-modify-write poll %d\n",
+               df ? "dataflow" : "stream-schedule", c.chol_epoch, (c.use_df && attempt + 1 != 2) ? "dataflow" : "stream", ctl[8], ctl[9], ctl[10], ctl[11], ctl[12], ctl[13], ctl[14],
+               ctl[15], now1, now2, ctl[2], (unsigned)ctl[3], ctl[0], ctl[1], nt, ctl[6], ctl[7]);
+}
+
+// end of either solve: the landmarks' steps (sharded: every landmark's from the shard that owns it) into the step of all variables
+static void scatter_step(gtg_context& c) {
+  if (c.n_lm) exchange(c, c.delta_lm.p, 3 * (int64_t)c.n_lm);
+  launch_scatter_delta(c);
+}
+
+// behind either solve: linear error of the step, the trial point, its error (gated by the linear cost change); the scalars on the host
+static void evaluate_trial(gtg_context& c, FirstCallClock* first) {
+  { PhaseTimer t(c, GTG_PH_LINEAR_ERROR); launch_linear_error(c); launch_smart_lin1(c); }
+  { PhaseTimer t(c, GTG_PH_RETRACT); launch_retract(c); }
+  { PhaseTimer t(c, GTG_PH_ERROR); const double* gate = c.scalars.p + (smart_gate(c) ? 2 * SC_COUNT : 0);
+    launch_smart_triangulate(c, c.trial.p, gate, false); launch_error(c, c.trial.p, SC_TRIAL_ERROR, gate); }
+  if (first) first->lap("linear error, retract, error");
+  read_scalars(c);
+}
+
+// out[4] = linear error at zero and at the step, error of the trial point (inf: the model does not like the step), step length
+static int trial_result(const gtg_context& c, bool solver_ok, double out[4]) {
+  const double dsq = c.h_scalars[SC_DELTA_SQ];
+  if (c.h_scalars[SC_FAIL] != 0.0 || !std::isfinite(dsq) || !solver_ok) return GTG_INDETERMINATE;
+  out[0] = c.h_scalars[SC_LIN0];
+  out[1] = c.h_scalars[SC_LIN1];
+  out[2] = (out[0] - out[1] >= 0) ? c.h_scalars[SC_TRIAL_ERROR] : std::numeric_limits<double>::infinity();
+  out[3] = std::sqrt(dsq);
+  return GTG_OK;
+}
+
 int gtg_linearize(gtg_handle c) {
   GTG_TRY
   if (!c || !c->uploaded) throw std::invalid_argument("gtg_linearize: no problem uploaded");
   DeviceGuard on_device(c->device);
   if (c->n_smart) check_hip(hipMemsetAsync(c->scalars.p + SC_UNSUPPORTED, 0, sizeof(double), c->stream), "memset");
   FirstCallClock first(g_first_linearize, c->stream);
-  { PhaseTimer t(*c, GTG_PH_LINEARIZE, c->phase_events.data()); launch_smart_triangulate(*c, c->values.p, nullptr, true); launch_linearize(*c); }
+  { PhaseTimer t(*c, GTG_PH_LINEARIZE); launch_smart_triangulate(*c, c->values.p, nullptr, true); launch_linearize(*c); }
   first.lap("linearize");
-  { PhaseTimer t(*c, GTG_PH_ASSEMBLE, c->phase_events.data()); launch_assemble(*c);
+  { PhaseTimer t(*c, GTG_PH_ASSEMBLE); launch_assemble(*c);
     if (c->n_smart) {   // the cameras' Hessian diagonal is that of the Schur-complemented smart factors: needs their E blocks (undamped)
       launch_point_eliminate(*c, 1.0, 0, 1e-6, 1e32);
       launch_smart_hdiag(*c);
@@ -597,32 +403,18 @@ int gtg_try_lambda(gtg_handle c, double lambda, int diag, double dmin, double dm
   for (int attempt = 0; attempt < max_attempts; attempt++) {
     const bool df = c->use_df && attempt != 2;
     check_hip(hipMemsetAsync(c->scalars.p + SC_FAIL, 0, 3 * sizeof(double), c->stream), "memset");
-    { PhaseTimer t(*c, GTG_PH_POINT_ELIM, c->phase_events.data()); launch_point_eliminate(*c, lambda, diag, dmin, dmax); }
+    { PhaseTimer t(*c, GTG_PH_POINT_ELIM); launch_point_eliminate(*c, lambda, diag, dmin, dmax); }
     first.lap("point elimination");
-    { PhaseTimer t(*c, GTG_PH_SCHUR, c->phase_events.data()); launch_build_reduced(*c, lambda, diag, dmin, dmax); }
+    { PhaseTimer t(*c, GTG_PH_SCHUR); launch_build_reduced(*c, lambda, diag, dmin, dmax); }
     first.lap("reduced system");
-    if (c->n_shards > 1) {   // the one big exchange: reduced Hessian + rhs
-      if (c->n_xb == 0) {     // (no block list: whole stored 128x128 tiles, the first version of the exchange)
-        const int64_t nb = c->plan.n_exch * kTile * kTile;
-        if ((int64_t)c->xbuf.n != nb) c->xbuf.alloc(nb);
-        launch_pack_tiles(*c, smat(*c), c->plan, c->xbuf.p, false);
-        exchange(*c, c->xbuf.p, nb);
-        launch_pack_tiles(*c, smat(*c), c->plan, c->xbuf.p, true);
-      } else {                // only the structurally non-zero d x d blocks (the same list on every shard) + rhs row + padding
-        const int64_t nb = exchange_block_doubles(*c);
-        if ((int64_t)c->xbuf.n != nb) c->xbuf.alloc(nb);
-        launch_pack_blocks(*c, smat(*c), c->NP, c->xbuf.p, false);
-        exchange(*c, c->xbuf.p, nb);
-        launch_pack_blocks(*c, smat(*c), c->NP, c->xbuf.p, true);
-      }
-    }
+    exchange_reduced_system(*c);
     std::unique_lock<std::mutex> one_at_a_time;
     if (df) one_at_a_time = std::unique_lock<std::mutex>(df_device_lock(c->device));
-    { PhaseTimer t(*c, GTG_PH_CHOLESKY, c->phase_events.data());
+    { PhaseTimer t(*c, GTG_PH_CHOLESKY);
       if (df) launch_cholesky_df(*c, smat(*c), c->NP, c->df, c->Dinv.p, c->scalars.p + SC_FAIL, c->pivot_kind.p, c->tile_exp.p);
       else launch_cholesky(*c, smat(*c), c->NP, c->plan, c->Dinv.p, c->scalars.p + SC_FAIL, c->pivot_kind.p, c->tile_exp.p); }
     first.lap("factorisation");
-    { PhaseTimer t(*c, GTG_PH_SOLVE, c->phase_events.data());
+    { PhaseTimer t(*c, GTG_PH_SOLVE);
       launch_backward_solve(*c, smat(*c), c->NP, c->plan, c->Dinv.p, c->xred.p, c->scalars.p + SC_FAIL);
       launch_back_substitute(*c);
       first.lap("solves");
@@ -630,42 +422,11 @@ int gtg_try_lambda(gtg_handle c, double lambda, int diag, double dmin, double dm
         check_hip(hipStreamSynchronize(c->stream), "sync");   // process (two shards on one device in the tests): the factorisation is
         one_at_a_time.unlock();                                // done, let the other one start before waiting for it
       }
-      if (c->n_lm) exchange(*c, c->delta_lm.p, 3 * (int64_t)c->n_lm);
-      launch_scatter_delta(*c); }
-    { PhaseTimer t(*c, GTG_PH_LINEAR_ERROR, c->phase_events.data()); launch_linear_error(*c); launch_smart_lin1(*c); }
-    { PhaseTimer t(*c, GTG_PH_RETRACT, c->phase_events.data()); launch_retract(*c); }
-    { PhaseTimer t(*c, GTG_PH_ERROR, c->phase_events.data()); const double* gate = c->scalars.p + (smart_gate(*c) ? 2 * SC_COUNT : 0);
-      launch_smart_triangulate(*c, c->trial.p, gate, false); launch_error(*c, c->trial.p, SC_TRIAL_ERROR, gate); }
-    first.lap("linear error, retract, error");
-    read_scalars(*c);
+      scatter_step(*c); }
+    evaluate_trial(*c, &first);
     if (one_at_a_time.owns_lock()) one_at_a_time.unlock();
     if (attempt + 1 < max_attempts && c->h_scalars[SC_TIMEOUT] != 0.0) {
-      static const bool quiet = std::getenv("GTG_QUIET") != nullptr;
-      if (!quiet) {
-        // post-mortem: which wait gave up (chol_dataflow.hip::wait_flags records the first one of a dataflow pass), what it saw, and
-        // what the same words hold in memory NOW, read from the host after the kernels have drained
-        int32_t ctl[16] = {0};
-        long long now1 = -1, now2 = -1;
-        const int nt = c->NP / kTile;
-        if (df && c->df.ctrl.p) {
-          (void)hipMemcpy(ctl, c->df.ctrl.p, sizeof(ctl), hipMemcpyDeviceToHost);
-          const int kind = ctl[8], I = ctl[9], J = ctl[10], k = ctl[11];
-          const long long *w1 = nullptr, *w2 = nullptr;
-          // (flag words are indexed by tile slot; kinds 1 / 2 record the SLOT of the first operand tile in k)
-          auto slot_of = [&](int a, int b) { return (a >= 0 && a <= nt && b >= 0 && b < nt) ? (int64_t)c->plan.h_slot[(size_t)a * nt + b] : (int64_t)-1; };
-          if (kind == 1 || kind == 2) { if (k >= 0 && k < c->plan.n_stored) w1 = w2 = c->df.tile_flag.p + k; }
-          else if (kind == 3 && slot_of(J, J) >= 0) w1 = w2 = c->df.tile_flag.p + slot_of(J, J);
-          else if (kind == 4) w1 = w2 = c->df.pd_flag.p + I;
-          else if (kind == 5 && slot_of(I, J) >= 0) w1 = w2 = c->df.tile_flag.p + slot_of(I, J);
-          else if (kind == 7 && slot_of(I, J) >= 0) w1 = w2 = c->df.part_flag.p + slot_of(I, J);
-          if (w1) { (void)hipMemcpy(&now1, w1, 8, hipMemcpyDeviceToHost); (void)hipMemcpy(&now2, w2, 8, hipMemcpyDeviceToHost); }
-        }
-        std::fprintf(stderr, "[gtsam_amd] %s factorisation (epoch %lld): a dependency wait ran into its bound; repeating the lambda try with the %s "
-                     "schedule.  wait kind %d at (%d, %d, %d): saw %d / %d, wanted %d / %d; memory now holds %lld / %lld; waiter on XCD %d (hw id 0x%x); "
-                     "tickets taken %d, diagonal tiles started %d of %d; over this handle's life: waits that ended on the shadow words %d, on the read-modify-write poll %d\n",
-                     df ? "dataflow" : "stream-schedule", c->chol_epoch, (c->use_df && attempt + 1 != 2) ? "dataflow" : "stream", ctl[8], ctl[9], ctl[10], ctl[11], ctl[12], ctl[13], ctl[14],
-                     ctl[15], now1, now2, ctl[2], (unsigned)ctl[3], ctl[0], ctl[1], nt, ctl[6], ctl[7]);
-      }
+      report_wait_timeout(*c, df, attempt);
       c->df_fallbacks++;
       continue;
     }
@@ -673,15 +434,9 @@ int gtg_try_lambda(gtg_handle c, double lambda, int diag, double dmin, double dm
   }
   collect(*c, {GTG_PH_POINT_ELIM, GTG_PH_SCHUR, GTG_PH_CHOLESKY, GTG_PH_SOLVE, GTG_PH_LINEAR_ERROR, GTG_PH_RETRACT, GTG_PH_ERROR});
   c->have_trial = true;
-  const double dsq = c->h_scalars[SC_DELTA_SQ];
   check_smart_supported(*c, "gtg_try_lambda");
   if (c->h_scalars[SC_TIMEOUT] != 0.0) throw std::runtime_error("gtg_try_lambda: a dependency wait of the factorisation ran into its bound (GPU shared or preempted?); the step was not computed");
-  if (c->h_scalars[SC_FAIL] != 0.0 || !std::isfinite(dsq)) return GTG_INDETERMINATE;
-  out[0] = c->h_scalars[SC_LIN0];
-  out[1] = c->h_scalars[SC_LIN1];
-  out[2] = (out[0] - out[1] >= 0) ? c->h_scalars[SC_TRIAL_ERROR] : std::numeric_limits<double>::infinity();
-  out[3] = std::sqrt(dsq);
-  return GTG_OK;
+  return trial_result(*c, true, out);
   GTG_CATCH
 }
 
@@ -694,31 +449,20 @@ int gtg_try_lambda_pcg(gtg_handle c, double lambda, int diag, double dmin, doubl
   if (!(lambda > 0.0) || !cg) throw std::invalid_argument("gtg_try_lambda_pcg: lambda must be > 0, cg = {max, min, eps_rel, eps_abs}");
   DeviceGuard on_device(c->device);
   check_hip(hipMemsetAsync(c->scalars.p + SC_FAIL, 0, 3 * sizeof(double), c->stream), "memset");
-  { PhaseTimer t(*c, GTG_PH_POINT_ELIM, c->phase_events.data()); launch_point_eliminate(*c, lambda, diag, dmin, dmax); }
+  { PhaseTimer t(*c, GTG_PH_POINT_ELIM); launch_point_eliminate(*c, lambda, diag, dmin, dmax); }
   double g0 = 0.0, g1 = 0.0;
   int its = 0;
-  { PhaseTimer t(*c, GTG_PH_CHOLESKY, c->phase_events.data());
+  { PhaseTimer t(*c, GTG_PH_CHOLESKY);
     its = launch_pcg(*c, lambda, diag, dmin, dmax, (int)cg[0], (int)cg[1], cg[2], cg[3], &g0, &g1); }
   if (iterations) *iterations = its;
-  { PhaseTimer t(*c, GTG_PH_SOLVE, c->phase_events.data());
+  { PhaseTimer t(*c, GTG_PH_SOLVE);
     launch_back_substitute(*c);
-    if (c->n_lm) exchange(*c, c->delta_lm.p, 3 * (int64_t)c->n_lm);   // sharded: every landmark's step from the shard that owns it
-    launch_scatter_delta(*c); }
-  { PhaseTimer t(*c, GTG_PH_LINEAR_ERROR, c->phase_events.data()); launch_linear_error(*c); launch_smart_lin1(*c); }
-  { PhaseTimer t(*c, GTG_PH_RETRACT, c->phase_events.data()); launch_retract(*c); }
-  { PhaseTimer t(*c, GTG_PH_ERROR, c->phase_events.data()); const double* gate = c->scalars.p + (smart_gate(*c) ? 2 * SC_COUNT : 0);
-      launch_smart_triangulate(*c, c->trial.p, gate, false); launch_error(*c, c->trial.p, SC_TRIAL_ERROR, gate); }
-  read_scalars(*c);
+    scatter_step(*c); }
+  evaluate_trial(*c, nullptr);
   collect(*c, {GTG_PH_POINT_ELIM, GTG_PH_CHOLESKY, GTG_PH_SOLVE, GTG_PH_LINEAR_ERROR, GTG_PH_RETRACT, GTG_PH_ERROR});
   c->have_trial = true;
-  const double dsq = c->h_scalars[SC_DELTA_SQ];
   check_smart_supported(*c, "gtg_try_lambda_pcg");
-  if (c->h_scalars[SC_FAIL] != 0.0 || !std::isfinite(dsq) || !std::isfinite(g1)) return GTG_INDETERMINATE;
-  out[0] = c->h_scalars[SC_LIN0];
-  out[1] = c->h_scalars[SC_LIN1];
-  out[2] = (out[0] - out[1] >= 0) ? c->h_scalars[SC_TRIAL_ERROR] : std::numeric_limits<double>::infinity();
-  out[3] = std::sqrt(dsq);
-  return GTG_OK;
+  return trial_result(*c, std::isfinite(g1), out);
   GTG_CATCH
 }
 

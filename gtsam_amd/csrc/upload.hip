@@ -1,0 +1,355 @@
+// upload.hip -- gtg_upload_problem behind its argument checks: the caller's tables become the handle's device tables, stage by stage
+// (upload_problem at the bottom is the list).  Host code only; the symbolic analysis that follows the tables is analysis.hip.
+#include <algorithm>
+#include <cmath>
+#include <exception>
+#include <stdexcept>
+#include <string>
+#include <thread>
+
+#include "analysis.h"
+#include "factors.h"
+#include "kernels.h"
+
+// GTG_FUSED_SFM=0 at compile time builds the stored-record form of rounds 1-4 for every graph (the A/B of the fused linearisation,
+// `make records`); the product library is built with 1
+#ifndef GTG_FUSED_SFM
+#define GTG_FUSED_SFM 1
+#endif
+namespace gt {
+namespace {
+
+// Smart factors become what the rest of the library already knows: a hidden POINT3 variable per factor behind the caller's
+// variables and one GeneralSFM observation per measurement behind the caller's; every table is built from problem().  Without smart
+// factors that is the caller's struct and nothing is owned.  Pure host code.
+struct SmartView {
+  std::vector<int32_t> var_type, sfm_cam, sfm_point, sfm_noise;
+  std::vector<int32_t> of_obs;   // per observation of problem(): its smart factor, -1 for the caller's own GeneralSFM factors
+  std::vector<double> sfm_z;
+  explicit SmartView(const gtg_problem& user);
+  SmartView(const SmartView&) = delete;   // (p may point at q)
+  const gtg_problem& problem() const { return *p; }
+ private:
+  gtg_problem q; const gtg_problem* p;
+};
+
+SmartView::SmartView(const gtg_problem& user) : q(user), p(&user) {
+  const int64_t n_smart = user.n_smart > 0 ? user.n_smart : 0;
+  if (!n_smart) return;
+  if (!user.smart_ptr || !user.smart_cam || !user.smart_z || !user.smart_noise || !user.smart_params)
+    throw std::invalid_argument("smart factor tables missing");
+  const int64_t n_meas = user.smart_ptr[n_smart];
+  var_type.assign(user.var_type, user.var_type + user.n_vars); var_type.resize((size_t)user.n_vars + n_smart, GTG_VAR_POINT3);
+  sfm_cam.assign(user.sfm_cam, user.sfm_cam + user.n_sfm); sfm_point.assign(user.sfm_point, user.sfm_point + user.n_sfm);
+  sfm_noise.assign(user.sfm_noise, user.sfm_noise + user.n_sfm); sfm_z.assign(user.sfm_z, user.sfm_z + 2 * user.n_sfm);
+  of_obs.assign((size_t)user.n_sfm, -1);
+  // the device addresses a factor's measurements as smart_obs0 + smart_ptr[i] while the expanded observations are appended one
+  // after the other: the offsets must start at 0 and be strictly increasing
+  if (user.smart_ptr[0] != 0) throw std::invalid_argument("smart factors: smart_ptr[0] must be 0");
+  for (int64_t i = 0; i < n_smart; i++) {
+    const int64_t k0 = user.smart_ptr[i], k1 = user.smart_ptr[i + 1];
+    if (k1 <= k0 || k1 > n_meas) throw std::invalid_argument("smart factor without measurements / bad smart_ptr");
+    const double* sp = user.smart_params + 8 * i;
+    if (!(sp[4] == 0.0 || sp[4] == 1.0 || sp[4] == 2.0)) throw std::invalid_argument("smart factor: unknown degeneracy mode");
+    if (!(sp[6] == 0.0 || sp[6] == 1.0)) throw std::invalid_argument("smart factor: enableEPI must be 0 or 1");
+    // LinearizationMode (SmartFactorParams.h:31-33): HESSIAN, JACOBIAN_Q, JACOBIAN_SVD give the same normal equations (they differ in
+    // what a failed track contributes and in the constant of the linear error); IMPLICIT_SCHUR factors cannot be eliminated by
+    // the reference's direct solvers at all (RegularImplicitSchurFactor has no augmentedJacobian / augmentedInformation)
+    if (!(sp[5] == 0.0 || sp[5] == 2.0 || sp[5] == 3.0)) throw std::invalid_argument("smart factor: linearization mode must be 0 HESSIAN, 2 JACOBIAN_Q or 3 JACOBIAN_SVD");
+    // rankTolerance, landmarkDistanceThreshold, dynamicOutlierRejectionThreshold (negative = off, as in the reference),
+    // retriangulationThreshold: numbers, not NaN / inf (a NaN threshold silently disables the test it guards)
+    for (int e = 0; e < 4; e++) if (!std::isfinite(sp[e])) throw std::invalid_argument("smart factor: a threshold is not finite");
+    // the reference requires an isotropic model (SmartFactorBase.h:107-114: "SmartFactorBase: needs isotropic")
+    const int32_t nz = user.smart_noise[i];
+    if (nz < 0 || nz >= user.n_noise || user.noise_dim[nz] != 2 ||
+        !(user.noise_kind[nz] == GTG_NOISE_UNIT || user.noise_kind[nz] == GTG_NOISE_ISOTROPIC))
+      throw std::invalid_argument("smart factor: smart_noise must index a dim-2 Unit or Isotropic noise model");
+    for (int64_t k = k0; k < k1; k++) {
+      const int cam = user.smart_cam[k];
+      if (cam < 0 || cam >= user.n_vars || user.var_type[cam] != GTG_VAR_SFM_CAMERA)
+        throw std::invalid_argument("smart factor: its keys must be SFM_CAMERA variables");
+      sfm_cam.push_back(cam); sfm_point.push_back((int32_t)(user.n_vars + i)); sfm_noise.push_back(user.smart_noise[i]);
+      sfm_z.push_back(user.smart_z[2 * k]); sfm_z.push_back(user.smart_z[2 * k + 1]);
+      of_obs.push_back((int32_t)i);
+    }
+  }
+  q.n_vars = (int32_t)var_type.size(); q.var_type = var_type.data();
+  q.n_sfm = (int64_t)sfm_cam.size(); q.sfm_cam = sfm_cam.data(); q.sfm_point = sfm_point.data();
+  q.sfm_noise = sfm_noise.data(); q.sfm_z = sfm_z.data();
+  p = &q;
+}
+
+// per smart factor: parameters, an empty triangulation cache, cleared status words (smart_ptr and sfm_smart follow the shard
+// filter of the observation table: upload_smart_tracks); a handle without smart factors gives the buffers of an earlier problem back
+void upload_smart_state(gtg_context& c, const gtg_problem& user) {
+  const int64_t n_smart = c.n_smart;
+  if (!n_smart) {
+    c.smart_ptr.free(); c.smart_params.free(); c.sfm_smart.free(); c.lm_smart.free(); c.smart_status.free(); c.smart_lin_status.free();
+    c.smart_cache_state.free(); c.smart_cache_pose.free(); c.smart_cache_point.free();
+    return;
+  }
+  const int64_t n_meas = user.smart_ptr[n_smart];
+  std::vector<double> prm(user.smart_params, user.smart_params + 8 * n_smart);
+  up(c.smart_params, prm, c.stream);
+  std::vector<int32_t> none((size_t)n_smart, -1);
+  up(c.smart_cache_state, none, c.stream);
+  c.smart_status.alloc((size_t)n_smart); c.smart_lin_status.alloc((size_t)n_smart); c.smart_cache_point.alloc(3 * (size_t)n_smart); c.smart_cache_pose.alloc(12 * (size_t)n_meas);
+  check_hip(hipMemsetAsync(c.smart_status.p, 0, sizeof(int32_t) * n_smart, c.stream), "memset");
+  check_hip(hipMemsetAsync(c.smart_lin_status.p, 0, sizeof(int32_t) * n_smart, c.stream), "memset");
+}
+
+// where every variable starts in the packed values / tangent vectors; values, trial point and step
+void layout_variables(gtg_context& c, const gtg_problem& p) {
+  c.n_vars = p.n_vars;
+  c.h_var_type.assign(p.var_type, p.var_type + p.n_vars);
+  c.h_val_off.assign(p.n_vars + 1, 0); c.h_dim_off.assign(p.n_vars + 1, 0);
+  for (int v = 0; v < p.n_vars; v++) {
+    const int t = p.var_type[v];
+    if (t < 0 || t > GTG_VAR_POSE2) throw std::invalid_argument("unknown variable type");
+    c.h_val_off[v + 1] = c.h_val_off[v] + storage_size(t);
+    c.h_dim_off[v + 1] = c.h_dim_off[v] + tangent_dim(t);
+  }
+  c.val_size = c.h_val_off[p.n_vars]; c.dim_size = c.h_dim_off[p.n_vars];
+  c.user_val_size = c.h_val_off[c.n_user_vars]; c.user_dim_size = c.h_dim_off[c.n_user_vars];
+  up(c.var_type, c.h_var_type, c.stream); up(c.val_off, c.h_val_off, c.stream); up(c.dim_off, c.h_dim_off, c.stream);
+  c.values.alloc(std::max<int64_t>(c.val_size, 1)); c.trial.alloc(std::max<int64_t>(c.val_size, 1));
+  c.delta.alloc(std::max<int64_t>(c.dim_size, 1));
+  check_hip(hipMemsetAsync(c.delta.p, 0, sizeof(double) * c.delta.n, c.stream), "memset");
+}
+
+// noise table: derive the inverse sigmas like the reference constructors (NoiseModel.cpp:275-281, Isotropic ctor)
+void upload_noise_table(gtg_context& c, const gtg_problem& p) {
+  std::vector<int32_t> kind(p.noise_kind, p.noise_kind + p.n_noise);
+  std::vector<int64_t> noff(p.n_noise);
+  std::vector<double> data;
+  for (int i = 0; i < p.n_noise; i++) {
+    const int dim = p.noise_dim[i];
+    const double* d = p.noise_data + p.noise_off[i];
+    noff[i] = (int64_t)data.size();
+    switch (kind[i]) {
+      case GTG_NOISE_UNIT: data.push_back(0.0); break;
+      case GTG_NOISE_ISOTROPIC: data.push_back(1.0 / d[0]); break;
+      case GTG_NOISE_DIAGONAL: for (int k = 0; k < dim; k++) data.push_back(1.0 / d[k]); break;
+      case GTG_NOISE_GAUSSIAN: for (int k = 0; k < dim * dim; k++) data.push_back(d[k]); break;
+      default: throw std::invalid_argument("unsupported noise model kind (Robust/Constrained are out of scope)");
+    }
+  }
+  std::vector<int32_t> rkind(p.n_noise, GTG_ROBUST_NONE);
+  std::vector<double> rk(p.n_noise, 0.0);
+  for (int i = 0; i < p.n_noise; i++) {
+    if (p.noise_robust) rkind[i] = p.noise_robust[i];
+    if (rkind[i] < GTG_ROBUST_NONE || rkind[i] > GTG_ROBUST_L2WITHDEADZONE) throw std::invalid_argument("unsupported m-estimator");
+    if (rkind[i] != GTG_ROBUST_NONE) {
+      rk[i] = p.noise_robust_param ? p.noise_robust_param[i] : 0.0;
+      if (!(rk[i] > 0.0)) throw std::invalid_argument("m-estimator parameter must be > 0");   // LossFunctions.cpp ctor checks
+    }
+  }
+  up(c.noise_kind, kind, c.stream); up(c.noise_off, noff, c.stream); up(c.noise_data, data, c.stream);
+  up(c.noise_rkind, rkind, c.stream); up(c.noise_rk, rk, c.stream);
+}
+
+// what every factor family checks of its rows
+void check_var(const gtg_problem& p, int v) { if (v < 0 || v >= p.n_vars) throw std::invalid_argument("factor refers to a key that is not in Values"); }
+void check_noise(const gtg_problem& p, int idx, int dim, const char* what) {
+  if (idx < 0 || idx >= p.n_noise || p.noise_dim[idx] != dim)
+    throw std::invalid_argument(std::string(what) + ": NoiseModel has wrong dimension");  // NonlinearFactor.cpp:97-104
+}
+
+// shard filter: landmark factors follow their landmark (rank among POINT3 variables), others round-robin; a prior follows its
+// variable if that is a landmark.  (One shard owns everything: the family stages ask only when n_shards > 1.)
+struct ShardFilter {
+  std::vector<int32_t> lm_rank;
+  int shard, n_shards;
+  ShardFilter(const gtg_problem& p, int shard_, int n_shards_) : lm_rank(p.n_vars, -1), shard(shard_), n_shards(n_shards_) {
+    int k = 0; for (int v = 0; v < p.n_vars; v++) if (p.var_type[v] == GTG_VAR_POINT3) lm_rank[v] = k++;
+  }
+  bool owns_landmark(int v) const { return lm_rank[v] >= 0 && (lm_rank[v] % n_shards) == shard; }
+  bool owns_round_robin(int64_t i) const { return (i % n_shards) == shard; }
+  bool owns_prior(int v, int64_t i) const { return lm_rank[v] >= 0 ? owns_landmark(v) : owns_round_robin(i); }
+};
+
+// sharded layouts are derived from the keys of the WHOLE graph (HostIndex, analysis.h)
+void keep_whole_graph_keys(HostIndex& hi, const gtg_problem& p, int n_shards) {
+  hi.all_obs_red_var.clear(); hi.all_obs_point.clear(); hi.all_between_v1.clear(); hi.all_between_v2.clear();
+  if (n_shards == 1) return;
+  for (int64_t i = 0; i < p.n_sfm; i++) { check_var(p, p.sfm_cam[i]); check_var(p, p.sfm_point[i]); }
+  for (int64_t i = 0; i < p.n_proj; i++) { check_var(p, p.proj_pose[i]); check_var(p, p.proj_point[i]); }
+  for (int64_t i = 0; i < p.n_between; i++) { check_var(p, p.between_v1[i]); check_var(p, p.between_v2[i]); }
+  hi.all_obs_red_var.assign(p.sfm_cam, p.sfm_cam + p.n_sfm); hi.all_obs_red_var.insert(hi.all_obs_red_var.end(), p.proj_pose, p.proj_pose + p.n_proj);
+  hi.all_obs_point.assign(p.sfm_point, p.sfm_point + p.n_sfm); hi.all_obs_point.insert(hi.all_obs_point.end(), p.proj_point, p.proj_point + p.n_proj);
+  hi.all_between_v1.assign(p.between_v1, p.between_v1 + p.n_between); hi.all_between_v2.assign(p.between_v2, p.between_v2 + p.n_between);
+}
+
+// The noise rows and the measurements of a whole GeneralSFM table (20 bytes per factor: 13.5 MB on the L1723 shape, 1.2 ms from pageable
+// memory) are not read by the symbolic analysis: they go up from the caller's arrays on a helper thread and the handle's copy stream
+// beside it.  finish() waits for them and rethrows what the thread met; the destructor only waits.
+class SideUpload {
+  std::thread t;
+  std::exception_ptr err;
+ public:
+  ~SideUpload() { if (t.joinable()) t.join(); }
+  void start(gtg_context& c, const int32_t* h_nz, const double* h_z, size_t n) {
+    c.f.sfm_noise.alloc(n); c.f.sfm_z.alloc(2 * n);
+    const int dev = c.device; hipStream_t cs = c.copy_stream;
+    int32_t* d_nz = c.f.sfm_noise.p; double* d_z = c.f.sfm_z.p;
+    t = std::thread([this, dev, cs, d_nz, d_z, h_nz, h_z, n] {
+      try {
+        check_hip(hipSetDevice(dev), "hipSetDevice");
+        check_hip(hipMemcpyAsync(d_nz, h_nz, sizeof(int32_t) * n, hipMemcpyHostToDevice, cs), "H2D");
+        check_hip(hipMemcpyAsync(d_z, h_z, sizeof(double) * 2 * n, hipMemcpyHostToDevice, cs), "H2D");
+        check_hip(hipStreamSynchronize(cs), "sync");
+      } catch (...) { err = std::current_exception(); }
+    });
+  }
+  void finish() { if (t.joinable()) t.join(); if (err) std::rethrow_exception(err); }
+};
+
+// Sharded, a smart factor follows its hidden landmark like any landmark factor: this shard holds the measurements of the
+// tracks it owns, in the order of the whole table.  The per-factor arrays keep the GLOBAL factor index (parameters, status,
+// cache); a factor of another shard has no measurements here (smart_ptr[i + 1] == smart_ptr[i]) and is skipped.
+void upload_smart_tracks(gtg_context& c, const gtg_problem& p, const std::vector<int32_t>& of_obs, const ShardFilter& own) {
+  std::vector<int64_t> rel((size_t)c.n_smart + 1, 0);
+  std::vector<int32_t> of_local;
+  int64_t obs0 = 0;
+  for (int64_t i = 0; i < p.n_sfm; i++) {
+    if (own.n_shards > 1 && !own.owns_landmark(p.sfm_point[i])) continue;
+    const int32_t sf = of_obs[(size_t)i];
+    of_local.push_back(sf);
+    if (sf < 0) obs0++; else rel[(size_t)sf + 1]++;
+  }
+  for (int64_t i = 0; i < c.n_smart; i++) rel[(size_t)i + 1] += rel[(size_t)i];
+  c.smart_obs0 = obs0;
+  up(c.smart_ptr, rel, c.stream);
+  up(c.sfm_smart, of_local, c.stream);
+}
+
+void upload_sfm(gtg_context& c, HostIndex& hi, const gtg_problem& p, const std::vector<int32_t>& of_obs, const ShardFilter& own, SideUpload& side) {
+  auto& f = c.f;
+  for (int64_t i = 0; i < p.n_sfm; i++) { check_var(p, p.sfm_cam[i]); check_var(p, p.sfm_point[i]); check_noise(p, p.sfm_noise[i], 2, "GeneralSFMFactor"); }
+  std::vector<int32_t> cam, pt, nz; std::vector<double> z;
+  const bool whole = own.n_shards == 1 && p.n_sfm > 0;
+  if (whole) {   // the whole table: the keys are copied (kept by the host index: gtg_set_reduced_ordering analyses again), the rest goes up beside the analysis
+    cam.assign(p.sfm_cam, p.sfm_cam + p.n_sfm); pt.assign(p.sfm_point, p.sfm_point + p.n_sfm);
+  } else {       // this shard's rows (or none at all)
+    for (int64_t i = 0; i < p.n_sfm; i++) {
+      if (!own.owns_landmark(p.sfm_point[i])) continue;
+      cam.push_back(p.sfm_cam[i]); pt.push_back(p.sfm_point[i]); nz.push_back(p.sfm_noise[i]);
+      z.push_back(p.sfm_z[2 * i]); z.push_back(p.sfm_z[2 * i + 1]);
+    }
+  }
+  if (c.n_smart) upload_smart_tracks(c, p, of_obs, own);
+  f.n_sfm = (int64_t)cam.size();
+  up(f.sfm_cam, cam, c.stream); up(f.sfm_point, pt, c.stream);
+  if (whole) side.start(c, p.sfm_noise, p.sfm_z, (size_t)p.n_sfm);
+  else { up(f.sfm_noise, nz, c.stream); up(f.sfm_z, z, c.stream); }
+  if (c.val_size >= (int64_t)1 << 31) throw std::invalid_argument("gtg_upload_problem: more than 2^31 packed value entries");
+  f.sfm_cam_at.alloc(std::max<size_t>(cam.size(), 1)); f.sfm_point_at.alloc(std::max<size_t>(pt.size(), 1));
+  launch_sfm_value_offsets(c);     // where each factor's camera / point start in the packed values (a gather through val_off, on the device)
+  f.sfm_J.alloc(c.fused_sfm ? 1 : std::max<size_t>((size_t)kSfmRec * f.n_sfm, 1));
+  hi.sfm_cam = std::move(cam); hi.sfm_point = std::move(pt);
+}
+
+void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, const ShardFilter& own) {
+  auto& f = c.f;
+  std::vector<int32_t> pose, pt, nz, cal, sen; std::vector<double> z;
+  for (int64_t i = 0; i < p.n_proj; i++) {
+    check_var(p, p.proj_pose[i]); check_var(p, p.proj_point[i]); check_noise(p, p.proj_noise[i], 2, "GenericProjectionFactor");
+    if (p.proj_calib[i] < 0 || p.proj_calib[i] >= p.n_calib) throw std::invalid_argument("bad calibration index");
+    const int si = p.proj_sensor ? p.proj_sensor[i] : -1;
+    if (si >= p.n_sensor) throw std::invalid_argument("bad body_P_sensor index");
+    if (own.n_shards > 1 && !own.owns_landmark(p.proj_point[i])) continue;
+    pose.push_back(p.proj_pose[i]); pt.push_back(p.proj_point[i]); nz.push_back(p.proj_noise[i]);
+    cal.push_back(p.proj_calib[i]); sen.push_back(si);
+    z.push_back(p.proj_z[2 * i]); z.push_back(p.proj_z[2 * i + 1]);
+  }
+  f.n_proj = (int64_t)pose.size();
+  up(f.proj_pose, pose, c.stream); up(f.proj_point, pt, c.stream); up(f.proj_noise, nz, c.stream); up(f.proj_calib, cal, c.stream);
+  up(f.proj_sensor, sen, c.stream); up(f.proj_z, z, c.stream);
+  // device calibration table: 9 per entry, fx fy s u0 v0 k1 k2 p1 p2 (the distortion part zero for a Cal3_S2)
+  std::vector<double> calib(kCalibStride * (size_t)p.n_calib, 0.0), sensor(p.sensor, p.sensor + 12 * (size_t)p.n_sensor);
+  for (int32_t k = 0; k < p.n_calib; k++) {
+    for (int j = 0; j < 5; j++) calib[kCalibStride * (size_t)k + j] = p.calib[5 * (size_t)k + j];
+    if (p.calib_distortion) for (int j = 0; j < 4; j++) calib[kCalibStride * (size_t)k + 5 + j] = p.calib_distortion[4 * (size_t)k + j];
+  }
+  up(f.calib, calib, c.stream); up(f.sensor, sensor, c.stream);
+  f.proj_J.alloc(std::max<size_t>((size_t)kProjRec * f.n_proj, 1));
+  hi.proj_pose = pose; hi.proj_point = pt;
+}
+
+void upload_between(gtg_context& c, HostIndex& hi, const gtg_problem& p, const ShardFilter& own) {
+  auto& f = c.f;
+  std::vector<int32_t> v1, v2, nz; std::vector<double> z;
+  for (int64_t i = 0; i < p.n_between; i++) {
+    check_var(p, p.between_v1[i]); check_var(p, p.between_v2[i]);
+    check_noise(p, p.between_noise[i], tangent_dim(p.var_type[p.between_v1[i]]), "BetweenFactor");
+    if (own.n_shards > 1 && !own.owns_round_robin(i)) continue;
+    v1.push_back(p.between_v1[i]); v2.push_back(p.between_v2[i]); nz.push_back(p.between_noise[i]);
+    for (int k = 0; k < 12; k++) z.push_back(p.between_z[12 * i + k]);
+  }
+  f.n_between = (int64_t)v1.size();
+  up(f.between_v1, v1, c.stream); up(f.between_v2, v2, c.stream); up(f.between_noise, nz, c.stream); up(f.between_z, z, c.stream);
+  f.between_J.alloc(std::max<size_t>((size_t)kBetweenRec * f.n_between, 1));
+  hi.between_v1 = v1; hi.between_v2 = v2;
+}
+
+void upload_priors(gtg_context& c, HostIndex& hi, const gtg_problem& p, const ShardFilter& own) {
+  auto& f = c.f;
+  std::vector<int32_t> var, nz; std::vector<int64_t> poff; std::vector<double> data;
+  for (int64_t i = 0; i < p.n_prior; i++) {
+    const int v = p.prior_var[i];
+    check_var(p, v); check_noise(p, p.prior_noise[i], tangent_dim(p.var_type[v]), "PriorFactor");
+    if (own.n_shards > 1 && !own.owns_prior(v, i)) continue;
+    var.push_back(v); nz.push_back(p.prior_noise[i]); poff.push_back((int64_t)data.size());
+    const double* d = p.prior_data + p.prior_off[i];
+    for (int k = 0; k < storage_size(p.var_type[v]); k++) data.push_back(d[k]);
+  }
+  f.n_prior = (int64_t)var.size();
+  up(f.prior_var, var, c.stream); up(f.prior_noise, nz, c.stream); up(f.prior_off, poff, c.stream); up(f.prior_data, data, c.stream);
+  f.prior_J.alloc(std::max<size_t>((size_t)kPriorRec * f.n_prior, 1));
+  hi.prior_var = var;
+}
+
+// landmark index of every smart factor's hidden variable (known once analyze() has classified the variables)
+void link_smart_landmarks(gtg_context& c) {
+  if (!c.n_smart) return;
+  std::vector<int32_t> lm_smart((size_t)std::max(c.n_lm, 1), -1);
+  for (int64_t i = 0; i < c.n_smart; i++) {
+    const int l = c.h_lm_index[c.n_user_vars + i];
+    if (l < 0) throw std::runtime_error("smart factor: its hidden landmark was not classified as a landmark");
+    lm_smart[(size_t)l] = (int32_t)i;
+  }
+  up(c.lm_smart, lm_smart, c.stream);
+  check_hip(hipStreamSynchronize(c.stream), "sync");
+}
+
+}  // namespace
+
+void upload_problem(gtg_context& c, const gtg_problem& user, int shard, int n_shards) {
+  // a handle holds one whole problem or none: an upload that throws half-way leaves none, not the tables of two behind "uploaded"
+  c.uploaded = false; c.linearized = false; c.have_trial = false;
+  StageClock clk;
+  c.shard = shard; c.n_shards = n_shards;
+  c.n_smart = user.n_smart > 0 ? user.n_smart : 0; c.n_user_vars = user.n_vars; c.smart_obs0 = user.n_sfm;
+  // GeneralSFM records recomputed where they are needed instead of stored (fused.h) -- not with smart factors, whose measurements'
+  // records depend on the factor's triangulation status
+  c.fused_sfm = GTG_FUSED_SFM != 0 && c.n_smart == 0;
+  const SmartView view(user);
+  const gtg_problem& p = view.problem();
+  upload_smart_state(c, user);
+  layout_variables(c, p);
+  upload_noise_table(c, p);
+  const ShardFilter own(p, shard, n_shards);
+  HostIndex& hi = host_index(&c);
+  keep_whole_graph_keys(hi, p, n_shards);
+  SideUpload side;   // started by upload_sfm for a whole, non-empty table
+  upload_sfm(c, hi, p, view.of_obs, own, side);
+  upload_projection(c, hi, p, own);
+  upload_between(c, hi, p, own);
+  upload_priors(c, hi, p, own);
+  clk.lap("factor tables (shard filter + upload)");
+  analyze(c);
+  side.finish();
+  link_smart_landmarks(c);
+}
+
+}  // namespace gt

@@ -168,6 +168,13 @@ for name, fn in REJECTED:
 hh, rc, e = upload(good, shard=2, n=2); out["bad_shard"] = [rc, e]; lib.gtg_destroy(hh)
 hh, rc, e = upload(good, shard=0, n=2); lib.gtg_set_values(hh, v0.ctypes.data, v0.size)
 out["sharded_without_allreduce"] = [rc, lib.gtg_linearize(hh), err()]; lib.gtg_destroy(hh)
+# --- a rejected upload on a handle that holds a problem leaves it without one; the next good upload makes it whole again ----
+hh, rc, e = upload(good); q, _ = bal_problem(*D.synthetic_bal(6, 40, seed=1)); wrong_dim(q); cq = q.to_ctypes()
+out["reupload_rejected"] = [rc, lib.gtg_upload_problem(hh, C.byref(cq), 0, 1), err()]
+out["linearize_after_rejected_upload"] = [lib.gtg_linearize(hh), err()]
+cg = good.to_ctypes()
+out["reupload_good"] = [lib.gtg_upload_problem(hh, C.byref(cg), 0, 1), lib.gtg_set_values(hh, v0.ctypes.data, v0.size), lib.gtg_linearize(hh)]
+lib.gtg_destroy(hh)
 hh = C.c_void_p(); out["bad_device"] = [lib.gtg_create(C.byref(hh), 64), err()]   # the stub shows 8 devices
 print("RESULT " + json.dumps(out))
 '''
@@ -177,7 +184,8 @@ def test_c_abi_protocol_and_error_behaviour(stub):
     """The boundary's error behaviour without a GPU: wrong call order, wrong sizes, content the reference rejects with an
     exception (noise dimension NonlinearFactor.cpp:97-104, unknown key, estimator parameter LossFunctions.cpp) come back as
     GTG_ERR_USAGE (-1) with a message, never as a crash or a silent success; a sharded upload without an all-reduce
-    callback is a runtime error (-2)."""
+    callback is a runtime error (-2).  An upload that is rejected on a handle that already holds a problem leaves the handle
+    without one ("no problem uploaded") until the next good upload."""
     r = HP.run_snippet(_PROTOCOL)
     assert r["upload_ok"] == 0 and r["set_values"] == 0 and r["linearize"] == 0 and r["reorder_ok"] == 0
     assert r["destroy"] == 0 and r["destroy_null"] == 0 and r["values_size_null"] == -1
@@ -192,6 +200,9 @@ def test_c_abi_protocol_and_error_behaviour(stub):
         assert r[key][0] == -1 and text in r[key][1], (key, r[key])
     # the callback may be registered after the upload; the first exchange without one is a runtime error (-2)
     assert r["sharded_without_allreduce"][:2] == [0, -2] and "no allreduce callback" in r["sharded_without_allreduce"][2]
+    assert r["reupload_rejected"][:2] == [0, -1] and "NoiseModel has wrong dimension" in r["reupload_rejected"][2]
+    assert r["linearize_after_rejected_upload"][0] == -1 and "no problem uploaded" in r["linearize_after_rejected_upload"][1]
+    assert r["reupload_good"] == [0, 0, 0]
 
 
 def test_degenerate_graphs_through_the_host_path(stub):

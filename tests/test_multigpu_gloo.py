@@ -20,7 +20,7 @@ from tests.conftest import load_golden
 
 
 def shard_problem(p: Problem, shard: int, n: int) -> Problem:
-    """The same filter gtg_upload_problem applies (gtsam_amd/csrc/api.hip)."""
+    """The same filter gtg_upload_problem applies (gtsam_amd/csrc/upload.hip: ShardFilter)."""
     lm_rank = -np.ones(p.n_vars, np.int64)
     pts = np.where(p.var_type == VAR_POINT3)[0]
     lm_rank[pts] = np.arange(pts.size)

@@ -177,7 +177,7 @@ def test_noise_model_constructors_literals(hm):
         want = unwhitened if m.kind == 0 else whitened
         assert np.abs(W @ unwhitened - want).max() <= 1e-12
         # device: PriorFactor<Point3> error with x - z = unwhitened; noise rows as gtg_upload_problem derives them
-        # (1/sigma, 1/sigmas, R) -- api.hip "noise table"
+        # (1/sigma, 1/sigmas, R) -- upload.hip "noise table"
         dev = {0: [0.0], 1: [1.0 / m.params[0]] if m.kind == 1 else [0.0], 2: list(1.0 / np.asarray(m.params)) if m.kind == 2 else [0.0],
                3: list(m.params)}[m.kind]
         dev = np.array(dev, float); x = unwhitened.copy(); z = np.zeros(3)
