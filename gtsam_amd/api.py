@@ -49,6 +49,11 @@ def Point2(x=0.0, y=0.0):
     return np.array([x, y], np.float64)
 
 
+def StereoPoint2(uL=0.0, uR=0.0, v=0.0):
+    """gtsam.StereoPoint2(uL, uR, v) (geometry/StereoPoint2.h); stored as its vector()."""
+    return np.array([uL, uR, v], np.float64)
+
+
 class Pose3:
     def __init__(self, R: Rot3 | None = None, t=None):
         self.R = (R or Rot3()).R; self.t = np.zeros(3) if t is None else np.asarray(t, np.float64).reshape(3)
@@ -95,6 +100,15 @@ class Cal3DS2:
 
     def __init__(self, fx=1.0, fy=1.0, s=0.0, u0=0.0, v0=0.0, k1=0.0, k2=0.0, p1=0.0, p2=0.0):
         self.v = np.array([fx, fy, s, u0, v0, k1, k2, p1, p2], np.float64)
+
+
+class Cal3_S2Stereo:
+    """fx, fy, s, u0, v0 and the baseline b (geometry/Cal3_S2Stereo.h); StereoCamera::project2 does not use the skew."""
+
+    def __init__(self, fx=1.0, fy=1.0, s=0.0, u0=0.0, v0=0.0, b=1.0):
+        self.v = np.array([fx, fy, s, u0, v0, b], np.float64)
+
+    def baseline(self): return self.v[5]
 
 
 class PinholeCameraCal3Bundler:
@@ -238,6 +252,13 @@ class GenericProjectionFactorCal3DS2(GenericProjectionFactorCal3_S2):
     """GenericProjectionFactor<Pose3, Point3, Cal3DS2> (wrapped name of slam/slam.i's instantiation): same factor, K a Cal3DS2."""
 
 
+class GenericStereoFactor3D:
+    """GenericStereoFactor<Pose3, Point3> under the name of GTSAM's Python wrapper (slam/slam.i): measured = StereoPoint2."""
+
+    def __init__(self, measured, model, poseKey, landmarkKey, K: Cal3_S2Stereo, body_P_sensor: Pose3 | None = None):
+        self.z, self.model, self.keys_, self.K, self.sensor = np.asarray(measured, np.float64).reshape(3), model, (poseKey, landmarkKey), K, body_P_sensor
+
+
 class SmartProjectionParams:
     """slam/SmartFactorParams.h:42-66 + geometry/triangulation.h:558-600 (IMPLICIT_SCHUR is refused at upload)."""
     IGNORE_DEGENERACY, ZERO_ON_DEGENERACY, HANDLE_INFINITY = 0, 1, 2
@@ -360,7 +381,7 @@ def extract(graph: NonlinearFactorGraph, values: Values):
             raise KeyError(f"ValuesKeyDoesNotExist: {k}")
         return ids[k]
 
-    sfm, proj, btw = [], [], []
+    sfm, proj, btw, stereo = [], [], [], []
     calibs, sensors = {}, []
     for f in graph.factors:
         if isinstance(f, GeneralSFMFactorCal3Bundler):
@@ -373,6 +394,14 @@ def extract(graph: NonlinearFactorGraph, values: Values):
             if f.sensor is not None:
                 si = len(sensors); sensors.append(f.sensor.packed())
             proj.append((vid(f.keys_[0]), vid(f.keys_[1]), f.z, nid(f.model, 2), calibs[ck][0], si))
+        elif isinstance(f, GenericStereoFactor3D):   # same calib / sensor tables; the baseline goes to calib_baseline
+            ck = f.K.v.tobytes()
+            if ck not in calibs:
+                calibs[ck] = (len(calibs), f.K.v)
+            si = -1
+            if f.sensor is not None:
+                si = len(sensors); sensors.append(f.sensor.packed())
+            stereo.append((vid(f.keys_[0]), vid(f.keys_[1]), f.z, nid(f.model, 3), calibs[ck][0], si))
         elif isinstance(f, SmartProjectionFactorPinholeCameraCal3Bundler):
             sp = f.params
             p.add_smart([vid(k) for k in f.keys_], np.concatenate(f.zs), nid(f.model, 2), sp.rankTolerance, sp.landmarkDistanceThreshold,
@@ -396,10 +425,17 @@ def extract(graph: NonlinearFactorGraph, values: Values):
         p.proj_pose = np.array([s[0] for s in proj], np.int32); p.proj_point = np.array([s[1] for s in proj], np.int32)
         p.proj_z = np.concatenate([s[2] for s in proj]); p.proj_noise = np.array([s[3] for s in proj], np.int32)
         p.proj_calib = np.array([s[4] for s in proj], np.int32); p.proj_sensor = np.array([s[5] for s in proj], np.int32)
+    if stereo:
+        p.stereo_pose = np.array([s[0] for s in stereo], np.int32); p.stereo_point = np.array([s[1] for s in stereo], np.int32)
+        p.stereo_z = np.concatenate([s[2] for s in stereo]); p.stereo_noise = np.array([s[3] for s in stereo], np.int32)
+        p.stereo_calib = np.array([s[4] for s in stereo], np.int32); p.stereo_sensor = np.array([s[5] for s in stereo], np.int32)
+    if proj or stereo:
         rows = [c[1] for c in sorted(calibs.values(), key=lambda c: c[0])]
         p.calib = np.concatenate([r[:5] for r in rows])
         if any(r.size == 9 for r in rows):      # Cal3DS2 entries: k1, k2, p1, p2 per calibration (zero rows for a Cal3_S2)
             p.calib_distortion = np.concatenate([r[5:] if r.size == 9 else np.zeros(4) for r in rows])
+        if stereo:                              # Cal3_S2Stereo entries: their baseline (zero for the monocular calibrations)
+            p.calib_baseline = np.array([r[5] if r.size == 6 else 0.0 for r in rows], np.float64)
         p.sensor = np.concatenate(sensors) if sensors else np.zeros(0)
     if btw:
         p.between_v1 = np.array([s[0] for s in btw], np.int32); p.between_v2 = np.array([s[1] for s in btw], np.int32)

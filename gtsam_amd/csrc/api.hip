@@ -537,9 +537,10 @@ int gtg_get_jacobians(gtg_handle c, int type, double* out, int64_t n) {
   const double* src; int64_t cnt;
   switch (type) {
     case GTG_FAC_GENERAL_SFM: src = c->f.sfm_J.p; cnt = (c->n_smart ? c->smart_obs0 : c->f.n_sfm) * kSfmRec; break;   // (not the observations of smart factors)
-    case GTG_FAC_PROJECTION: src = c->f.proj_J.p; cnt = c->f.n_proj * kProjRec; break;
+    case GTG_FAC_PROJECTION: src = c->f.proj_J.p; cnt = c->f.n_mono * kProjRec; break;
     case GTG_FAC_BETWEEN_POSE3: src = c->f.between_J.p; cnt = c->f.n_between * kBetweenRec; break;
     case GTG_FAC_PRIOR: src = c->f.prior_J.p; cnt = c->f.n_prior * kPriorRec; break;
+    case GTG_FAC_STEREO: src = c->f.proj_J.p + (int64_t)kStereoRec * c->f.n_mono; cnt = (c->f.n_proj - c->f.n_mono) * kStereoRec; break;
     default: throw std::invalid_argument("unknown factor type");
   }
   if (n != cnt) throw std::invalid_argument("gtg_get_jacobians: wrong output size");
@@ -549,6 +550,20 @@ int gtg_get_jacobians(gtg_handle c, int type, double* out, int64_t n) {
     launch_sfm_records(*c, recomputed.p);
     check_hip(hipStreamSynchronize(c->stream), "sync");
     src = recomputed.p;
+  }
+  if (type == GTG_FAC_PROJECTION && c->f.stereo && cnt) {
+    // beside stereo factors the monocular records are stored with three rows, the third zero: give back the two-row records
+    // [A1 2x6 | A2 2x3 | b 2] they hold
+    std::vector<double> wide((size_t)c->f.n_mono * kStereoRec);
+    check_hip(hipMemcpy(wide.data(), src, sizeof(double) * wide.size(), hipMemcpyDeviceToHost), "D2H");
+    for (int64_t i = 0; i < c->f.n_mono; i++) {
+      const double* w = &wide[(size_t)i * kStereoRec];
+      double* o = out + i * kProjRec;
+      for (int k = 0; k < 12; k++) o[k] = w[k];
+      for (int k = 0; k < 6; k++) o[12 + k] = w[18 + k];
+      o[18] = w[27]; o[19] = w[28];
+    }
+    return GTG_OK;
   }
   if (cnt) check_hip(hipMemcpy(out, src, sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H");
   return GTG_OK;

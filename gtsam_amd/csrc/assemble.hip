@@ -28,21 +28,25 @@ struct JTabs {
   int64_t n_sfm;
 };
 
-// (A, rows, row stride, b) of one contribution to a reduced variable
+// (A, rows, row stride, b) of one contribution to a reduced variable.  PR: rows of a projection record -- 2, or 3 in a graph with
+// stereo factors, where every observation of the projection range has the record [A1 PR x 6 | A2 PR x 3 | b PR] (factors.h kStereoRec)
+static_assert(kProjRec == 10 * 2 && kStereoRec == 10 * 3, "a projection record is addressed by its row count");
+template <int PR>
 __device__ __forceinline__ void contribution(const JTabs& t, int kind, int idx, int d, const double*& A,
                                              int& rows, const double*& b) {
   if (kind == INC_SFM) { const double* J = t.sfm_J + (int64_t)kSfmRec * idx; A = J; rows = 2; b = J + 24; }
-  else if (kind == INC_PROJ) { const double* J = t.proj_J + (int64_t)kProjRec * idx; A = J; rows = 2; b = J + 18; }
+  else if (kind == INC_PROJ) { const double* J = t.proj_J + (int64_t)(10 * PR) * idx; A = J; rows = PR; b = J + 9 * PR; }
   else if (kind == INC_BTW_A) { const double* J = t.bt_J + (int64_t)kBetweenRec * idx; A = J; rows = d; b = J + 72; }   // d = 6 Pose3, 3 Pose2
   else if (kind == INC_BTW_B) { const double* J = t.bt_J + (int64_t)kBetweenRec * idx; A = J + 36; rows = d; b = J + 72; }
   else { const double* J = t.pr_J + (int64_t)kPriorRec * idx; A = J; rows = d; b = J + 81; }
 }
 
-// observation o -> (Jc 2 x dc, Jp 2x3, b 2)
+// observation o -> (Jc rows x dc, Jp rows x 3, b rows); rows = 2, or PR for a projection observation
+template <int PR>
 __device__ __forceinline__ void obs_rec(const JTabs& t, int64_t o, const double*& Jc, const double*& Jp,
-                                        const double*& b, int& dc) {
-  if (o < t.n_sfm) { const double* J = t.sfm_J + (int64_t)kSfmRec * o; Jc = J; Jp = J + 18; b = J + 24; dc = 9; }
-  else { const double* J = t.proj_J + (int64_t)kProjRec * (o - t.n_sfm); Jc = J; Jp = J + 12; b = J + 18; dc = 6; }
+                                        const double*& b, int& dc, int& rows) {
+  if (o < t.n_sfm) { const double* J = t.sfm_J + (int64_t)kSfmRec * o; Jc = J; Jp = J + 18; b = J + 24; dc = 9; rows = 2; }
+  else { const double* J = t.proj_J + (int64_t)(10 * PR) * (o - t.n_sfm); Jc = J; Jp = J + 6 * PR; b = J + 9 * PR; dc = 6; rows = PR; }
 }
 
 // ---- lambda-invariant assembly --------------------------------------------------------------------
@@ -53,6 +57,7 @@ __device__ __forceinline__ void obs_rec(const JTabs& t, int64_t o, const double*
 // contribution list and are combined through LDS in wave order (deterministic).
 typedef double v4f64a __attribute__((ext_vector_type(4)));
 constexpr int kRedWaves = 16;   // waves per reduced variable: a 16-camera problem still has 256 wavefronts of work
+template <int PR>
 __global__ __launch_bounds__(64 * kRedWaves) void k_red_diag(int32_t n_red_vars, const int64_t* __restrict__ inc_ptr,
     const int32_t* __restrict__ inc_kind, const int32_t* __restrict__ inc_idx, const int32_t* __restrict__ red_dim,
     const int64_t* __restrict__ red_off, JTabs t, double* __restrict__ Hd, double* __restrict__ g,
@@ -70,7 +75,7 @@ __global__ __launch_bounds__(64 * kRedWaves) void k_red_diag(int32_t n_red_vars,
   for (int64_t k = beg + wave; k < end; k += kRedWaves) {
     const double* A; const double* b; int rows;
     if (after_fused && inc_kind[k] == INC_SFM) continue;   // (wave-uniform)
-    contribution(t, inc_kind[k], inc_idx[k], d, A, rows, b);
+    contribution<PR>(t, inc_kind[k], inc_idx[k], d, A, rows, b);
     const int boff = (int)(b - A);
     for (int q0 = 0; q0 < rows; q0 += 4) {
       const int q = q0 + lk;
@@ -240,18 +245,27 @@ __global__ __launch_bounds__(kBlock) void k_lm_fused(int32_t n_lm, const int64_t
   }
 }
 
-// One lane per landmark: V = sum Jp^T Jp (+ priors), gp = sum Jp^T b.
+// One lane per landmark: V = sum Jp^T Jp (+ priors), gp = sum Jp^T b.  PR = 3 (a graph with stereo factors): the projection
+// observations add their third row.
+template <int PR>
 __global__ __launch_bounds__(kBlock) void k_lm_diag(int32_t n_lm, const int64_t* __restrict__ obs_ptr,
     const int32_t* __restrict__ obs, const int64_t* __restrict__ pri_ptr, const int32_t* __restrict__ pri,
     JTabs t, double* __restrict__ V, double* __restrict__ gp) {
   for (int64_t l = blockIdx.x * (int64_t)kBlock + threadIdx.x; l < n_lm; l += (int64_t)gridDim.x * kBlock) {
     double v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
     for (int64_t k = obs_ptr[l]; k < obs_ptr[l + 1]; k++) {
-      const double *Jc, *Jp, *b; int dc;
-      obs_rec(t, obs[k], Jc, Jp, b, dc);
+      const double *Jc, *Jp, *b; int dc, rows;
+      obs_rec<PR>(t, obs[k], Jc, Jp, b, dc, rows);
       for (int i = 0; i < 3; i++) {
         for (int j = 0; j < 3; j++) v[3 * i + j] += Jp[i] * Jp[j] + Jp[3 + i] * Jp[3 + j];
         g[i] += Jp[i] * b[0] + Jp[3 + i] * b[1];
+      }
+      if constexpr (PR == 3) {
+        if (rows == 3)
+          for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) v[3 * i + j] += Jp[6 + i] * Jp[6 + j];
+            g[i] += Jp[6 + i] * b[2];
+          }
       }
     }
     for (int64_t k = pri_ptr[l]; k < pri_ptr[l + 1]; k++) {
@@ -364,7 +378,8 @@ __global__ __launch_bounds__(kBlock) void k_point_factor(int32_t n_lm, const int
 // Also out: w_o = E_o y_l (9 doubles per observation, zero padded), the observation's summand of the reduced right-hand side, stored at the
 // observation's place in its camera's contribution list -- so that k_build_diag reads 72 contiguous bytes per entry instead of gathering the
 // 216-byte E block and y (283 MB per try on the L1723 shape until round 4).
-template <int REC, int DC, bool FUSED>
+// ROWS: residual rows of the record [Jc ROWS x DC | Jp ROWS x 3 | b ROWS] (3: the projection range of a graph with stereo factors).
+template <int REC, int DC, int ROWS, bool FUSED>
 __global__ __launch_bounds__(kBlock) void k_obs_E(int64_t n, const double* __restrict__ J, SfmTabs t, const int32_t* __restrict__ obs_lm,
     const double* __restrict__ Linv, const double* __restrict__ ylm, double* __restrict__ E, double* __restrict__ W,
     const int32_t* __restrict__ wpos) {
@@ -385,24 +400,28 @@ __global__ __launch_bounds__(kBlock) void k_obs_E(int64_t n, const double* __res
 #pragma unroll
     for (int i = 0; i < 9; i++) w[i] = 0.0;
     if (o < n) {
-      const double* rec = my + lane * IN::PITCH;     // [Jc 2 x DC | Jp 2 x 3 | b 2]
+      static_assert(REC == ROWS * (DC + 4) && (ROWS == 2 || ROWS == 3), "record layout");
+      const double* rec = my + lane * IN::PITCH;     // [Jc ROWS x DC | Jp ROWS x 3 | b ROWS]
       const int64_t lm = obs_lm[o];
       const double* Li = Linv + 9 * lm;
       const double* y = ylm + 3 * lm;
-      double T[6];
+      double T[3 * ROWS];
 #pragma unroll
-      for (int r = 0; r < 2; r++)
+      for (int r = 0; r < ROWS; r++)
 #pragma unroll
         for (int m = 0; m < 3; m++) {
           double acc = 0.0;
 #pragma unroll
-          for (int k = 0; k <= m; k++) acc += rec[2 * DC + 3 * r + k] * Li[3 * m + k];
+          for (int k = 0; k <= m; k++) acc += rec[ROWS * DC + 3 * r + k] * Li[3 * m + k];
           T[3 * r + m] = acc;
         }
 #pragma unroll
       for (int i = 0; i < DC; i++)
 #pragma unroll
-        for (int m = 0; m < 3; m++) Eo[3 * i + m] = rec[i] * T[m] + rec[DC + i] * T[3 + m];
+        for (int m = 0; m < 3; m++) {
+          if constexpr (ROWS == 2) Eo[3 * i + m] = rec[i] * T[m] + rec[DC + i] * T[3 + m];
+          else Eo[3 * i + m] = rec[i] * T[m] + rec[DC + i] * T[3 + m] + rec[2 * DC + i] * T[6 + m];
+        }
       const double y0 = y[0], y1 = y[1], y2 = y[2];
 #pragma unroll
       for (int i = 0; i < DC; i++) w[i] = Eo[3 * i] * y0 + Eo[3 * i + 1] * y1 + Eo[3 * i + 2] * y2;
@@ -423,7 +442,7 @@ __global__ __launch_bounds__(kBlock) void k_obs_E(int64_t n, const double* __res
 }
 
 // v_o = Jp^T (Jc x_cam) for the back-substitution, one observation per lane, records through LDS as above
-template <int REC, int DC, bool FUSED>
+template <int REC, int DC, int ROWS, bool FUSED>
 __global__ __launch_bounds__(kBlock) void k_obs_v(int64_t n, const double* __restrict__ J, SfmTabs t, const int32_t* __restrict__ obs_red,
     const int64_t* __restrict__ red_off, const double* __restrict__ x, double* __restrict__ v) {
   typedef RecIO<REC> IN;
@@ -438,11 +457,20 @@ __global__ __launch_bounds__(kBlock) void k_obs_v(int64_t n, const double* __res
     if (o < n) {
       const double* rec = my + lane * IN::PITCH;
       const double* xr = x + red_off[obs_red[o]];
+      static_assert(REC == ROWS * (DC + 4) && (ROWS == 2 || ROWS == 3), "record layout");
       double w0 = 0.0, w1 = 0.0;
 #pragma unroll
       for (int i = 0; i < DC; i++) { w0 += rec[i] * xr[i]; w1 += rec[DC + i] * xr[i]; }
-      const double* Jp = rec + 2 * DC;
-      v[3 * o] = Jp[0] * w0 + Jp[3] * w1; v[3 * o + 1] = Jp[1] * w0 + Jp[4] * w1; v[3 * o + 2] = Jp[2] * w0 + Jp[5] * w1;
+      const double* Jp = rec + ROWS * DC;
+      if constexpr (ROWS == 2) {
+        v[3 * o] = Jp[0] * w0 + Jp[3] * w1; v[3 * o + 1] = Jp[1] * w0 + Jp[4] * w1; v[3 * o + 2] = Jp[2] * w0 + Jp[5] * w1;
+      } else {
+        double w2 = 0.0;
+#pragma unroll
+        for (int i = 0; i < DC; i++) w2 += rec[2 * DC + i] * xr[i];
+        v[3 * o] = Jp[0] * w0 + Jp[3] * w1 + Jp[6] * w2; v[3 * o + 1] = Jp[1] * w0 + Jp[4] * w1 + Jp[7] * w2;
+        v[3 * o + 2] = Jp[2] * w0 + Jp[5] * w1 + Jp[8] * w2;
+      }
     }
   }
 }
@@ -717,16 +745,22 @@ void launch_assemble(gtg_context& c) {
       hipLaunchKernelGGL(k_cam_combine, dim3((unsigned)c.n_red_vars), dim3(128), 0, c.stream, c.n_red_vars, splits, c.red_dim.p, c.red_off.p,
                          c.cam_part.p, c.Hd.p, c.gred0.p, c.hdiag_red.p);
     if (c.f.n_proj + c.f.n_between + c.f.n_prior > 0)     // the other factor types' contributions on top
-      hipLaunchKernelGGL(k_red_diag, dim3(c.n_red_vars), dim3(64 * kRedWaves), 0, c.stream, c.n_red_vars, c.red_inc_ptr.p,
+      hipLaunchKernelGGL(k_red_diag<2>, dim3(c.n_red_vars), dim3(64 * kRedWaves), 0, c.stream, c.n_red_vars, c.red_inc_ptr.p,
                          c.red_inc_kind.p, c.red_inc_idx.p, c.red_dim.p, c.red_off.p, t, c.Hd.p, c.gred0.p, c.hdiag_red.p, 1);
-  } else if (c.n_red_vars)
-    hipLaunchKernelGGL(k_red_diag, dim3(c.n_red_vars), dim3(64 * kRedWaves), 0, c.stream, c.n_red_vars, c.red_inc_ptr.p,
+  } else if (c.n_red_vars && c.f.stereo)     // (a graph with stereo factors is never fused: upload.hip)
+    hipLaunchKernelGGL(k_red_diag<3>, dim3(c.n_red_vars), dim3(64 * kRedWaves), 0, c.stream, c.n_red_vars, c.red_inc_ptr.p,
+                       c.red_inc_kind.p, c.red_inc_idx.p, c.red_dim.p, c.red_off.p, t, c.Hd.p, c.gred0.p, c.hdiag_red.p, 0);
+  else if (c.n_red_vars)
+    hipLaunchKernelGGL(k_red_diag<2>, dim3(c.n_red_vars), dim3(64 * kRedWaves), 0, c.stream, c.n_red_vars, c.red_inc_ptr.p,
                        c.red_inc_kind.p, c.red_inc_idx.p, c.red_dim.p, c.red_off.p, t, c.Hd.p, c.gred0.p, c.hdiag_red.p, 0);
   if (c.n_lm && c.fused_sfm)
     hipLaunchKernelGGL(k_lm_fused, dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_obs_ptr.p, c.lm_obs.p,
                        c.lm_pri_ptr.p, c.lm_pri.p, t, sfm_tabs(c), c.V.p, c.gp.p);
+  else if (c.n_lm && c.f.stereo)
+    hipLaunchKernelGGL(k_lm_diag<3>, dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_obs_ptr.p, c.lm_obs.p,
+                       c.lm_pri_ptr.p, c.lm_pri.p, t, c.V.p, c.gp.p);
   else if (c.n_lm)
-    hipLaunchKernelGGL(k_lm_diag, dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_obs_ptr.p, c.lm_obs.p,
+    hipLaunchKernelGGL(k_lm_diag<2>, dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_obs_ptr.p, c.lm_obs.p,
                        c.lm_pri_ptr.p, c.lm_pri.p, t, c.V.p, c.gp.p);
   if (c.n_hoff)
     hipLaunchKernelGGL(k_hoff, dim3((unsigned)c.n_hoff), dim3(64), 0, c.stream, c.n_hoff, c.hoff_ptr.p, c.hoff_fac.p,
@@ -812,13 +846,16 @@ void launch_point_eliminate(gtg_context& c, double lambda, int diag, double dmin
                      c.gp.p, is, diag, dmin, dmax, c.Linv.p, c.ylm.p, c.scalars.p + SC_FAIL, c.n_smart ? c.lm_smart.p : nullptr, c.smart_lin_status.p);
   const SfmTabs st = sfm_tabs(c);
   if (c.f.n_sfm && c.fused_sfm)
-    hipLaunchKernelGGL((k_obs_E<kSfmRec, 9, true>), dim3(grid1(c.f.n_sfm / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_sfm, c.f.sfm_J.p, st,
+    hipLaunchKernelGGL((k_obs_E<kSfmRec, 9, 2, true>), dim3(grid1(c.f.n_sfm / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_sfm, c.f.sfm_J.p, st,
                        c.obs_lm.p, c.Linv.p, c.ylm.p, c.E.p, c.wobs.p, c.obs_wpos.p);
   else if (c.f.n_sfm)
-    hipLaunchKernelGGL((k_obs_E<kSfmRec, 9, false>), dim3(grid1(c.f.n_sfm / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_sfm, c.f.sfm_J.p, st,
+    hipLaunchKernelGGL((k_obs_E<kSfmRec, 9, 2, false>), dim3(grid1(c.f.n_sfm / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_sfm, c.f.sfm_J.p, st,
                        c.obs_lm.p, c.Linv.p, c.ylm.p, c.E.p, c.wobs.p, c.obs_wpos.p);
-  if (c.f.n_proj)
-    hipLaunchKernelGGL((k_obs_E<kProjRec, 6, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
+  if (c.f.n_proj && c.f.stereo)
+    hipLaunchKernelGGL((k_obs_E<kStereoRec, 6, 3, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
+                       c.f.proj_J.p, st, c.obs_lm.p + c.f.n_sfm, c.Linv.p, c.ylm.p, c.E.p + (int64_t)kEStride * c.f.n_sfm, c.wobs.p, c.obs_wpos.p + c.f.n_sfm);
+  else if (c.f.n_proj)
+    hipLaunchKernelGGL((k_obs_E<kProjRec, 6, 2, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
                        c.f.proj_J.p, st, c.obs_lm.p + c.f.n_sfm, c.Linv.p, c.ylm.p, c.E.p + (int64_t)kEStride * c.f.n_sfm, c.wobs.p, c.obs_wpos.p + c.f.n_sfm);
   check_hip(hipGetLastError(), "point_eliminate");
 }
@@ -849,13 +886,16 @@ void launch_build_reduced(gtg_context& c, double lambda, int diag, double dmin, 
 void launch_back_substitute(gtg_context& c) {
   const SfmTabs st = sfm_tabs(c);
   if (c.f.n_sfm && c.n_lm && c.fused_sfm)
-    hipLaunchKernelGGL((k_obs_v<kSfmRec, 9, true>), dim3(grid1(c.f.n_sfm / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_sfm, c.f.sfm_J.p, st,
+    hipLaunchKernelGGL((k_obs_v<kSfmRec, 9, 2, true>), dim3(grid1(c.f.n_sfm / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_sfm, c.f.sfm_J.p, st,
                        c.obs_red.p, c.red_off.p, c.xred.p, c.vobs.p);
   else if (c.f.n_sfm && c.n_lm)
-    hipLaunchKernelGGL((k_obs_v<kSfmRec, 9, false>), dim3(grid1(c.f.n_sfm / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_sfm, c.f.sfm_J.p, st,
+    hipLaunchKernelGGL((k_obs_v<kSfmRec, 9, 2, false>), dim3(grid1(c.f.n_sfm / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_sfm, c.f.sfm_J.p, st,
                        c.obs_red.p, c.red_off.p, c.xred.p, c.vobs.p);
-  if (c.f.n_proj && c.n_lm)
-    hipLaunchKernelGGL((k_obs_v<kProjRec, 6, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
+  if (c.f.n_proj && c.n_lm && c.f.stereo)
+    hipLaunchKernelGGL((k_obs_v<kStereoRec, 6, 3, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
+                       c.f.proj_J.p, st, c.obs_red.p + c.f.n_sfm, c.red_off.p, c.xred.p, c.vobs.p + 3 * c.f.n_sfm);
+  else if (c.f.n_proj && c.n_lm)
+    hipLaunchKernelGGL((k_obs_v<kProjRec, 6, 2, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
                        c.f.proj_J.p, st, c.obs_red.p + c.f.n_sfm, c.red_off.p, c.xred.p, c.vobs.p + 3 * c.f.n_sfm);
   if (c.n_lm)
     hipLaunchKernelGGL(k_backsub_lm, dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_owned.p,
@@ -871,9 +911,9 @@ void launch_scatter_delta(gtg_context& c) {
 
 // gtg_prewarm: this unit's kernels (kernels.h)
 static void prewarm_assemble(int) {
-  prewarm_kernels({(const void*)k_red_diag, (const void*)k_cam_fused, (const void*)k_cam_combine, (const void*)k_lm_fused, (const void*)k_lm_diag, (const void*)k_hoff,
-                   (const void*)k_point_factor, (const void*)k_obs_E<kSfmRec, 9, true>, (const void*)k_obs_E<kSfmRec, 9, false>, (const void*)k_obs_E<kProjRec, 6, false>,
-                   (const void*)k_obs_v<kSfmRec, 9, true>, (const void*)k_obs_v<kSfmRec, 9, false>, (const void*)k_obs_v<kProjRec, 6, false>, (const void*)k_build_diag,
+  prewarm_kernels({(const void*)k_red_diag<2>, (const void*)k_red_diag<3>, (const void*)k_cam_fused, (const void*)k_cam_combine, (const void*)k_lm_fused, (const void*)k_lm_diag<2>, (const void*)k_lm_diag<3>, (const void*)k_hoff,
+                   (const void*)k_point_factor, (const void*)k_obs_E<kSfmRec, 9, 2, true>, (const void*)k_obs_E<kSfmRec, 9, 2, false>, (const void*)k_obs_E<kProjRec, 6, 2, false>, (const void*)k_obs_E<kStereoRec, 6, 3, false>, (const void*)k_obs_v<kStereoRec, 6, 3, false>,
+                   (const void*)k_obs_v<kSfmRec, 9, 2, true>, (const void*)k_obs_v<kSfmRec, 9, 2, false>, (const void*)k_obs_v<kProjRec, 6, 2, false>, (const void*)k_build_diag,
                    (const void*)k_scatter_hoff, (const void*)k_schur_pairs, (const void*)k_schur_pairs_heavy, (const void*)k_pad_diag, (const void*)k_backsub_lm,
                    (const void*)k_scatter_delta, (const void*)k_obs_wpos, (const void*)k_cam_pack, (const void*)k_smart_hdiag, (const void*)k_smart_lin1});
 }

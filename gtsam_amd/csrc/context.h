@@ -146,6 +146,12 @@ struct FactorTables {
   int64_t n_proj = 0;
   DevBuf<int32_t> proj_pose, proj_point, proj_noise, proj_calib, proj_sensor;
   DevBuf<double> proj_z, proj_J, calib, sensor;
+  // GenericStereoFactor<Pose3, Point3>: the stereo factors are the observations [n_mono, n_proj) of the projection range.  A graph
+  // with at least one (stereo, decided on the WHOLE graph, not on a shard's rows) keeps three-row records (kStereoRec) and three
+  // measurement entries for every observation of the range, the monocular ones with a zero third row.
+  int64_t n_mono = 0;
+  bool stereo = false;
+  DevBuf<double> calib_baseline;   // [n_calib] Cal3_S2Stereo::baseline
   // between
   int64_t n_between = 0;
   DevBuf<int32_t> between_v1, between_v2, between_noise;

@@ -3,6 +3,7 @@
 // Each function is what ONE lane executes for ONE factor.  They restate, for the GPU,
 //   GeneralSFMFactor::linearize / evaluateError      slam/GeneralSFMFactor.h:127-177
 //   GenericProjectionFactor::evaluateError           slam/ProjectionFactor.h:138-166
+//   GenericStereoFactor<Pose3,Point3>::evaluateError  slam/StereoFactor.h:126-154
 //   BetweenFactor<Pose3>::evaluateError              slam/BetweenFactor.h:111-124
 //   PriorFactor<T>::evaluateError                    nonlinear/PriorFactor.h:98-102
 // followed by NoiseModelFactor::linearize's  b = -r, WhitenSystem(A, b)
@@ -62,6 +63,7 @@ GT_HD double reweight_factor(const NoiseRef& n, const double* b, int m) {
 // row lengths of the per-factor Jacobian records (doubles)
 constexpr int kSfmRec = 2 * 9 + 2 * 3 + 2;   // [A1 2x9 | A2 2x3 | b 2]
 constexpr int kProjRec = 2 * 6 + 2 * 3 + 2;  // [A1 2x6 | A2 2x3 | b 2]
+constexpr int kStereoRec = 3 * 6 + 3 * 3 + 3;  // [A1 3x6 | A2 3x3 | b 3]: every projection observation of a graph WITH stereo factors
 constexpr int kBetweenRec = 36 + 36 + 6;     // [A1 6x6 | A2 6x6 | b 6]
 constexpr int kPriorRec = 81 + 9;            // [A dxd packed | pad ... | b d at 81]
 
@@ -177,6 +179,75 @@ GT_HD double proj_error(const double* pose, const double* K, const double* senso
   else { r[0] = 2.0 * K[0]; r[1] = 2.0 * K[0]; }
   whiten_cols<2>(n.kind, n.data, r, 1);
   return factor_loss(n, r[0] * r[0] + r[1] * r[1]);
+}
+
+// ---- GenericStereoFactor<Pose3,Point3> ---------------------------------------------------------
+// Three residual rows (uL, uR, v) where the monocular factor has two; K = the calib table entry (skew unused), bl = its baseline.
+GT_HD void stereo_linearize(const double* pose, const double* K, double bl, const double* sensor, const double* pt,
+                            const double* z, const NoiseRef& n, double* J) {
+  const int nkind = n.kind; const double* nd = n.data;
+  double pi[3];
+  bool ok;
+  if (sensor) {  // pose.compose(body_P_sensor, H0); H1 = H1 * H0 (StereoFactor.h:129-135)
+    double T[12], Dp[18], Si[12], H0[36];
+    pose_compose(pose, sensor, T);
+    ok = stereo_project(T, K, bl, pt, pi, Dp, J + 18);
+    if (ok) {
+      pose_inverse(sensor, Si);
+      pose_adjoint(Si, H0);
+      for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 6; c++) {
+          double acc = 0.0;
+          for (int k = 0; k < 6; k++) acc += Dp[6 * r + k] * H0[6 * k + c];
+          J[6 * r + c] = acc;
+        }
+    }
+  } else {
+    ok = stereo_project(pose, K, bl, pt, pi, J, J + 18);
+  }
+  if (!ok) {  // H = 0 and residual Vector3::Constant(2 fx) (StereoFactor.h:144-153, throwCheirality_ = false)
+    for (int i = 0; i < 27; i++) J[i] = 0.0;
+    J[27] = -2.0 * K[0]; J[28] = -2.0 * K[0]; J[29] = -2.0 * K[0];
+  } else {
+    J[27] = -(pi[0] - z[0]); J[28] = -(pi[1] - z[1]); J[29] = -(pi[2] - z[2]);
+  }
+  whiten_cols<3>(nkind, nd, J, 6);
+  whiten_cols<3>(nkind, nd, J + 18, 3);
+  whiten_cols<3>(nkind, nd, J + 27, 1);
+  if (n.rkind) { const double w = reweight_factor(n, J + 27, 3); for (int i = 0; i < kStereoRec; i++) J[i] *= w; }
+}
+// the whitened residual h(x) - z of the factor (what its error is the loss of)
+GT_HD void stereo_residual(const double* pose, const double* K, double bl, const double* sensor, const double* pt,
+                           const double* z, const NoiseRef& n, double* r) {
+  double pi[3];
+  bool ok;
+  if (sensor) {
+    double T[12];
+    pose_compose(pose, sensor, T);
+    ok = stereo_project(T, K, bl, pt, pi, nullptr, nullptr);
+  } else {
+    ok = stereo_project(pose, K, bl, pt, pi, nullptr, nullptr);
+  }
+  if (ok) { r[0] = pi[0] - z[0]; r[1] = pi[1] - z[1]; r[2] = pi[2] - z[2]; }
+  else { r[0] = 2.0 * K[0]; r[1] = 2.0 * K[0]; r[2] = 2.0 * K[0]; }
+  whiten_cols<3>(n.kind, n.data, r, 1);
+}
+GT_HD double stereo_error(const double* pose, const double* K, double bl, const double* sensor, const double* pt,
+                          const double* z, const NoiseRef& n) {
+  double r[3];
+  stereo_residual(pose, K, bl, sensor, pt, z, n, r);
+  return factor_loss(n, r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+}
+// A monocular factor of a graph that also has stereo factors: the same doubles as proj_linearize gives, in the three-row layout with
+// a zero third row, so that one record size serves the whole observation range.
+GT_HD void proj_linearize_rows3(const double* pose, const double* K, const double* sensor, const double* pt,
+                                const double* z, const NoiseRef& n, double* J) {
+  proj_linearize(pose, K, sensor, pt, z, n, J);   // [A1 2x6 | A2 2x3 | b 2] in the first 20 places
+  const double a0 = J[12], a1 = J[13], a2 = J[14], a3 = J[15], a4 = J[16], a5 = J[17], b0 = J[18], b1 = J[19];
+  for (int i = 12; i < 18; i++) J[i] = 0.0;
+  J[18] = a0; J[19] = a1; J[20] = a2; J[21] = a3; J[22] = a4; J[23] = a5;
+  J[24] = 0.0; J[25] = 0.0; J[26] = 0.0;
+  J[27] = b0; J[28] = b1; J[29] = 0.0;
 }
 
 // ---- BetweenFactor<Pose3> ---------------------------------------------------------------------

@@ -104,6 +104,41 @@ __global__ __launch_bounds__(kBlock) void k_lin_proj(int64_t n, const int32_t* _
   }
 }
 
+// The projection range of a graph WITH stereo factors: observations [0, n_mono) are monocular, [n_mono, n) GenericStereoFactors; every
+// record has three rows (kStereoRec, the monocular ones a zero third row) and every measurement three entries.  Records in place in the
+// LDS image as above.
+__global__ __launch_bounds__(kBlock) void k_lin_stereo(int64_t n, int64_t n_mono, const int32_t* __restrict__ pose,
+    const int32_t* __restrict__ pt, const double* __restrict__ z, const int32_t* __restrict__ nz,
+    const int32_t* __restrict__ calib_idx, const int32_t* __restrict__ sensor_idx,
+    const double* __restrict__ calib, const double* __restrict__ baseline, const double* __restrict__ sensor,
+    const double* __restrict__ values, const int64_t* __restrict__ val_off, NoiseTab nt,
+    double* __restrict__ J) {
+  typedef RecIO<kStereoRec> IO;
+  __shared__ double img[kBlock / 64][IO::LDS_DOUBLES];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double* my = img[wave];
+  const int64_t nchunks = (n + 63) / 64, stride = (int64_t)gridDim.x * (kBlock / 64);
+  for (int64_t ch = blockIdx.x * (int64_t)(kBlock / 64) + wave; ch < nchunks; ch += stride) {
+    const int64_t i = ch * 64 + lane;
+    if (i < n) {
+      double T[12], p[3], zz[3], K[kCalibStride], S[12];
+      const double* tp = values + val_off[pose[i]];
+      const double* pp = values + val_off[pt[i]];
+      for (int k = 0; k < 12; k++) T[k] = tp[k];
+      for (int k = 0; k < 3; k++) p[k] = pp[k];
+      const int ci = calib_idx[i];
+      for (int k = 0; k < kCalibStride; k++) K[k] = calib[kCalibStride * ci + k];
+      const int si = sensor_idx[i];
+      if (si >= 0) for (int k = 0; k < 12; k++) S[k] = sensor[12 * si + k];
+      for (int k = 0; k < 3; k++) zz[k] = z[3 * i + k];
+      if (i < n_mono) proj_linearize_rows3(T, K, si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]), my + lane * IO::PITCH);
+      else stereo_linearize(T, K, baseline[ci], si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]), my + lane * IO::PITCH);
+    }
+    const int64_t left = n - ch * 64;
+    IO::store(my, J + (int64_t)kStereoRec * ch * 64, left < 64 ? (int)left : 64, lane);
+  }
+}
+
 // BetweenFactor<Pose3> or BetweenFactor<Pose2>: decided by the type of the factor's variables (both of one type)
 __global__ __launch_bounds__(kBlock) void k_lin_between(int64_t n, const int32_t* __restrict__ v1,
     const int32_t* __restrict__ v2, const double* __restrict__ z, const int32_t* __restrict__ nz,
@@ -205,6 +240,33 @@ __global__ __launch_bounds__(kBlock) void k_error(ErrArgs a, const double* __res
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
+// The projection range of a graph with stereo factors (k_lin_stereo): k_error<2> is then launched without that range.  Fixed slices
+// per block as above.
+__global__ __launch_bounds__(kBlock) void k_error_stereo(int64_t n, int64_t n_mono, const int32_t* __restrict__ pose,
+    const int32_t* __restrict__ pt, const double* __restrict__ z, const int32_t* __restrict__ nz,
+    const int32_t* __restrict__ calib_idx, const int32_t* __restrict__ sensor_idx,
+    const double* __restrict__ calib, const double* __restrict__ baseline, const double* __restrict__ sensor,
+    const double* __restrict__ values, const int64_t* __restrict__ val_off, NoiseTab nt, double* __restrict__ partials) {
+  double acc = 0.0;
+  const int64_t tid = blockIdx.x * (int64_t)kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = tid; i < n; i += stride) {
+    double T[12], p[3], zz[3], K[kCalibStride], S[12];
+    const double* tp = values + val_off[pose[i]];
+    const double* pp = values + val_off[pt[i]];
+    for (int k = 0; k < 12; k++) T[k] = tp[k];
+    for (int k = 0; k < 3; k++) p[k] = pp[k];
+    const int ci = calib_idx[i];
+    for (int k = 0; k < kCalibStride; k++) K[k] = calib[kCalibStride * ci + k];
+    const int si = sensor_idx[i];
+    if (si >= 0) for (int k = 0; k < 12; k++) S[k] = sensor[12 * si + k];
+    for (int k = 0; k < 3; k++) zz[k] = z[3 * i + k];
+    if (i < n_mono) acc += proj_error(T, K, si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]));
+    else acc += stereo_error(T, K, baseline[ci], si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]));
+  }
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
 // sums `n` partials (n <= kMaxBlocks) in a fixed order into out[slot]; nslots interleaved partial arrays
 __global__ __launch_bounds__(kBlock) void k_final_sum(const double* __restrict__ partials, int n, int nslots,
                                                       double* __restrict__ out, int slot0) {
@@ -226,8 +288,9 @@ struct LinErrArgs {
 };
 
 // FUSED: the records of the GeneralSFM factors are recomputed (fused.h) instead of read: chunk c of 64 consecutive factors belongs to
-// wavefront c of the grid, as in k_lin_sfm
-template <bool FUSED>
+// wavefront c of the grid, as in k_lin_sfm.  PR: rows of a projection record -- 2, or 3 in a graph with stereo factors ([A1 PR x 6 |
+// A2 PR x 3 | b PR], factors.h).
+template <bool FUSED, int PR>
 __global__ __launch_bounds__(kBlock) void k_linear_error(LinErrArgs a, SfmTabs t, const double* __restrict__ delta,
                                                          double* __restrict__ partials) {
   typedef RecIO<kSfmRec> IO;
@@ -267,14 +330,14 @@ __global__ __launch_bounds__(kBlock) void k_linear_error(LinErrArgs a, SfmTabs t
   }
   }
   for (int64_t i = tid; i < a.n_proj; i += stride) {
-    const double* J = a.proj_J + (int64_t)kProjRec * i;
+    const double* J = a.proj_J + (int64_t)(10 * PR) * i;
     const double* dc = delta + a.dim_off[a.proj_pose[i]];
     const double* dp = delta + a.dim_off[a.proj_pt[i]];
-    for (int r = 0; r < 2; r++) {
-      const double b = J[18 + r];
+    for (int r = 0; r < PR; r++) {
+      const double b = J[9 * PR + r];
       double v = -b;
       for (int k = 0; k < 6; k++) v += J[6 * r + k] * dc[k];
-      for (int k = 0; k < 3; k++) v += J[12 + 3 * r + k] * dp[k];
+      for (int k = 0; k < 3; k++) v += J[6 * PR + 3 * r + k] * dp[k];
       e0 += b * b; e1 += v * v;
     }
   }
@@ -457,7 +520,11 @@ void launch_linearize(gtg_context& c) {
     hipLaunchKernelGGL(k_lin_smart_at_infinity, dim3(grid_for(f.n_sfm - c.smart_obs0)), dim3(kBlock), 0, c.stream, f.n_sfm - c.smart_obs0, c.smart_obs0,
                        f.sfm_cam.p, f.sfm_point.p, f.sfm_z.p, f.sfm_noise.p, c.values.p, c.val_off.p, nt, f.sfm_J.p, c.sfm_smart.p,
                        c.smart_lin_status.p, c.scalars.p);
-  if (f.n_proj)
+  if (f.n_proj && f.stereo)
+    hipLaunchKernelGGL(k_lin_stereo, dim3(grid_for(f.n_proj)), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.proj_pose.p,
+                       f.proj_point.p, f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_baseline.p,
+                       f.sensor.p, c.values.p, c.val_off.p, nt, f.proj_J.p);
+  else if (f.n_proj)
     hipLaunchKernelGGL(k_lin_proj, dim3(grid_for(f.n_proj)), dim3(kBlock), 0, c.stream, f.n_proj, f.proj_pose.p,
                        f.proj_point.p, f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p,
                        f.sensor.p, c.values.p, c.val_off.p, nt, f.proj_J.p);
@@ -500,18 +567,24 @@ void launch_sfm_records(gtg_context& c, double* dst) {
 
 void launch_error(gtg_context& c, const double* values, int slot, const double* gate) {
   auto& f = c.f;
-  ErrArgs a{f.n_sfm, f.n_proj, f.n_between, f.n_prior,
+  // (a graph with stereo factors: its projection range goes to k_error_stereo, the third group of block partials)
+  ErrArgs a{f.n_sfm, f.stereo ? 0 : f.n_proj, f.n_between, f.n_prior,
             f.sfm_cam.p, f.sfm_point.p, f.sfm_noise.p, f.sfm_z.p,
             f.proj_pose.p, f.proj_point.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.proj_z.p, f.calib.p, f.sensor.p,
             f.between_v1.p, f.between_v2.p, f.between_noise.p, f.between_z.p,
             f.prior_var.p, f.prior_noise.p, f.prior_off.p, f.prior_data.p,
             c.var_type.p, c.val_off.p, c.n_smart ? c.sfm_smart.p : nullptr, c.smart_status.p};
   // the GeneralSFM factors and the other types in a kernel each, their block partials one behind the other
-  const int64_t nrest = std::max(f.n_proj, std::max(f.n_between, f.n_prior));
-  const int g1 = f.n_sfm ? std::min(grid_for(f.n_sfm), kMaxBlocks / 2) : 0, g2 = (nrest || !g1) ? std::min(grid_for(nrest), kMaxBlocks / 2) : 0;
+  const int64_t nrest = std::max(a.n_proj, std::max(f.n_between, f.n_prior));
+  const int gmax = f.stereo ? kMaxBlocks / 4 : kMaxBlocks / 2;
+  const int g1 = f.n_sfm ? std::min(grid_for(f.n_sfm), gmax) : 0, g2 = (nrest || !g1) ? std::min(grid_for(nrest), gmax) : 0;
+  const int g3 = f.stereo && f.n_proj ? std::min(grid_for(f.n_proj), gmax) : 0;
   if (g1) hipLaunchKernelGGL(k_error<1>, dim3(g1), dim3(kBlock), 0, c.stream, a, values, noise_tab(c), c.partials.p);
   if (g2) hipLaunchKernelGGL(k_error<2>, dim3(g2), dim3(kBlock), 0, c.stream, a, values, noise_tab(c), c.partials.p + g1);
-  hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(kBlock), 0, c.stream, c.partials.p, g1 + g2, 1, c.scalars.p, slot);
+  if (g3) hipLaunchKernelGGL(k_error_stereo, dim3(g3), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.proj_pose.p, f.proj_point.p, f.proj_z.p,
+                             f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_baseline.p, f.sensor.p, values, c.val_off.p,
+                             noise_tab(c), c.partials.p + g1 + g2);
+  hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(kBlock), 0, c.stream, c.partials.p, g1 + g2 + g3, 1, c.scalars.p, slot);
   if (c.n_smart)
     hipLaunchKernelGGL(k_error_smart_at_infinity, dim3(1), dim3(kBlock), 0, c.stream, f.n_sfm - c.smart_obs0, c.smart_obs0, f.sfm_cam.p, f.sfm_point.p,
                        f.sfm_z.p, f.sfm_noise.p, values, c.val_off.p, noise_tab(c), c.sfm_smart.p, c.smart_status.p,
@@ -526,8 +599,10 @@ void launch_linear_error(gtg_context& c) {
                f.sfm_J.p, f.proj_J.p, f.between_J.p, f.prior_J.p, c.var_type.p, c.dim_off.p};
   const int64_t nmax = std::max(std::max(f.n_sfm, f.n_proj), std::max(f.n_between, f.n_prior));
   const int g = grid_for(nmax);
-  if (c.fused_sfm) hipLaunchKernelGGL(k_linear_error<true>, dim3(g), dim3(kBlock), 0, c.stream, a, sfm_tabs(c), c.delta.p, c.partials.p);
-  else hipLaunchKernelGGL(k_linear_error<false>, dim3(g), dim3(kBlock), 0, c.stream, a, sfm_tabs(c), c.delta.p, c.partials.p);
+  static_assert(kProjRec == 10 * 2 && kStereoRec == 10 * 3, "k_linear_error addresses a projection record by its row count");
+  if (f.stereo) hipLaunchKernelGGL((k_linear_error<false, 3>), dim3(g), dim3(kBlock), 0, c.stream, a, sfm_tabs(c), c.delta.p, c.partials.p);   // (stereo: never fused, upload.hip)
+  else if (c.fused_sfm) hipLaunchKernelGGL((k_linear_error<true, 2>), dim3(g), dim3(kBlock), 0, c.stream, a, sfm_tabs(c), c.delta.p, c.partials.p);
+  else hipLaunchKernelGGL((k_linear_error<false, 2>), dim3(g), dim3(kBlock), 0, c.stream, a, sfm_tabs(c), c.delta.p, c.partials.p);
   hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(kBlock), 0, c.stream, c.partials.p, g, 2, c.scalars.p, (int)SC_LIN0);
   check_hip(hipGetLastError(), "linear_error");
 }
@@ -547,8 +622,8 @@ void launch_retract(gtg_context& c) {
 namespace {
 void prewarm_factors(int) {
   gt::prewarm_kernels({(const void*)gt::k_lin_sfm, (const void*)gt::k_lin_proj, (const void*)gt::k_lin_between, (const void*)gt::k_lin_prior,
-                       (const void*)gt::k_error<1>, (const void*)gt::k_error<2>, (const void*)gt::k_final_sum, (const void*)gt::k_linear_error<true>,
-                       (const void*)gt::k_linear_error<false>, (const void*)gt::k_retract, (const void*)gt::k_sumsq, (const void*)gt::k_smart_triangulate,
+                       (const void*)gt::k_error<1>, (const void*)gt::k_error<2>, (const void*)gt::k_final_sum, (const void*)gt::k_linear_error<true, 2>,
+                       (const void*)gt::k_linear_error<false, 2>, (const void*)gt::k_linear_error<false, 3>, (const void*)gt::k_lin_stereo, (const void*)gt::k_error_stereo, (const void*)gt::k_retract, (const void*)gt::k_sumsq, (const void*)gt::k_smart_triangulate,
                        (const void*)gt::k_lin_smart_at_infinity, (const void*)gt::k_error_smart_at_infinity, (const void*)gt::k_sfm_value_offsets});
 }
 gt::PrewarmUnit prewarm_factors_registered(prewarm_factors);

@@ -607,6 +607,38 @@ GT_HD bool s2_project(const double* T, const double* K, const double* pw, double
   return true;
 }
 
+// StereoCamera::project2 (geometry/StereoCamera.cpp:37-79) with a Cal3_S2Stereo: K = fx, fy, s, u0, v0 as in the calib table and the
+// baseline b.  The skew is stored and NOT used, as in the reference.  pi = (uL, uR, v); Dpose 3x6, Dpoint 3x3 row-major.
+// Returns false on a StereoCheiralityException (q.z <= 0).
+GT_HD bool stereo_project(const double* T, const double* K, double b, const double* pw, double* pi, double* Dpose,
+                          double* Dpoint) {
+  _Pragma("clang fp contract(off)")   // the host compile of the CPU parity test and the device then round alike
+  const double dp[3] = {pw[0] - T[9], pw[1] - T[10], pw[2] - T[11]};
+  double q[3];
+  mat3_tvec(T, dp, q);
+  if (q[2] <= 0) return false;
+  const double fx = K[0], fy = K[1];
+  const double d = 1.0 / q[2];
+  const double x = q[0], y = q[1];
+  const double dfx = d * fx, dfy = d * fy;
+  const double uL = dfx * x, uR = dfx * (x - b), v = dfy * y;
+  if (Dpose) {
+    const double v1 = v / fy, v2 = fx * v1, dx = d * x;
+    Dpose[0] = uL * v1; Dpose[1] = -fx - dx * uL; Dpose[2] = v2; Dpose[3] = -dfx; Dpose[4] = 0.0; Dpose[5] = d * uL;
+    Dpose[6] = uR * v1; Dpose[7] = -fx - dx * uR; Dpose[8] = v2; Dpose[9] = -dfx; Dpose[10] = 0.0; Dpose[11] = d * uR;
+    Dpose[12] = fy + v * v1; Dpose[13] = -dx * v; Dpose[14] = -x * dfy; Dpose[15] = 0.0; Dpose[16] = -dfy; Dpose[17] = d * v;
+  }
+  if (Dpoint) {  // R(j, c) = T[3 j + c]
+    for (int j = 0; j < 3; j++) {
+      Dpoint[j] = d * (fx * T[3 * j + 0] - T[3 * j + 2] * uL);
+      Dpoint[3 + j] = d * (fx * T[3 * j + 0] - T[3 * j + 2] * uR);
+      Dpoint[6 + j] = d * (fy * T[3 * j + 1] - T[3 * j + 2] * v);
+    }
+  }
+  pi[0] = K[3] + uL; pi[1] = K[3] + uR; pi[2] = K[4] + v;
+  return true;
+}
+
 // ---- noise models (linear/NoiseModel.cpp) ------------------------------------------------------
 enum { kNoiseUnit = 0, kNoiseIsotropic = 1, kNoiseDiagonal = 2, kNoiseGaussian = 3 };
 // Device noise table entry data: ISOTROPIC {invsigma}; DIAGONAL invsigmas[dim]; GAUSSIAN R row-major.

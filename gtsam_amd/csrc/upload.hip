@@ -174,9 +174,13 @@ void keep_whole_graph_keys(HostIndex& hi, const gtg_problem& p, int n_shards) {
   if (n_shards == 1) return;
   for (int64_t i = 0; i < p.n_sfm; i++) { check_var(p, p.sfm_cam[i]); check_var(p, p.sfm_point[i]); }
   for (int64_t i = 0; i < p.n_proj; i++) { check_var(p, p.proj_pose[i]); check_var(p, p.proj_point[i]); }
+  const int64_t n_stereo = p.n_stereo > 0 && p.stereo_pose && p.stereo_point ? p.n_stereo : 0;   // (the tables are checked by upload_projection)
+  for (int64_t i = 0; i < n_stereo; i++) { check_var(p, p.stereo_pose[i]); check_var(p, p.stereo_point[i]); }
   for (int64_t i = 0; i < p.n_between; i++) { check_var(p, p.between_v1[i]); check_var(p, p.between_v2[i]); }
   hi.all_obs_red_var.assign(p.sfm_cam, p.sfm_cam + p.n_sfm); hi.all_obs_red_var.insert(hi.all_obs_red_var.end(), p.proj_pose, p.proj_pose + p.n_proj);
+  hi.all_obs_red_var.insert(hi.all_obs_red_var.end(), p.stereo_pose, p.stereo_pose + n_stereo);
   hi.all_obs_point.assign(p.sfm_point, p.sfm_point + p.n_sfm); hi.all_obs_point.insert(hi.all_obs_point.end(), p.proj_point, p.proj_point + p.n_proj);
+  hi.all_obs_point.insert(hi.all_obs_point.end(), p.stereo_point, p.stereo_point + n_stereo);
   hi.all_between_v1.assign(p.between_v1, p.between_v1 + p.n_between); hi.all_between_v2.assign(p.between_v2, p.between_v2 + p.n_between);
 }
 
@@ -252,6 +256,9 @@ void upload_sfm(gtg_context& c, HostIndex& hi, const gtg_problem& p, const std::
 void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, const ShardFilter& own) {
   auto& f = c.f;
   std::vector<int32_t> pose, pt, nz, cal, sen; std::vector<double> z;
+  const int64_t n_stereo = p.n_stereo > 0 ? p.n_stereo : 0;
+  f.stereo = n_stereo > 0;
+  const int zdim = f.stereo ? 3 : 2;   // a graph with stereo factors keeps three measurement entries per observation (context.h)
   for (int64_t i = 0; i < p.n_proj; i++) {
     check_var(p, p.proj_pose[i]); check_var(p, p.proj_point[i]); check_noise(p, p.proj_noise[i], 2, "GenericProjectionFactor");
     if (p.proj_calib[i] < 0 || p.proj_calib[i] >= p.n_calib) throw std::invalid_argument("bad calibration index");
@@ -261,6 +268,26 @@ void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, cons
     pose.push_back(p.proj_pose[i]); pt.push_back(p.proj_point[i]); nz.push_back(p.proj_noise[i]);
     cal.push_back(p.proj_calib[i]); sen.push_back(si);
     z.push_back(p.proj_z[2 * i]); z.push_back(p.proj_z[2 * i + 1]);
+    if (f.stereo) z.push_back(0.0);
+  }
+  f.n_mono = (int64_t)pose.size();
+  // the stereo factors join the observation range behind the monocular ones: the symbolic analysis, the incidence lists, the E slots,
+  // the Schur terms, PCG and the shard filter see more projection observations and nothing else
+  if (f.stereo) {
+    if (!p.stereo_pose || !p.stereo_point || !p.stereo_z || !p.stereo_noise || !p.stereo_calib) throw std::invalid_argument("stereo factor tables missing");
+    if (!p.calib_baseline) throw std::invalid_argument("GenericStereoFactor: calib_baseline is missing");
+  }
+  for (int64_t i = 0; i < n_stereo; i++) {
+    check_var(p, p.stereo_pose[i]); check_var(p, p.stereo_point[i]); check_noise(p, p.stereo_noise[i], 3, "GenericStereoFactor");
+    if (p.var_type[p.stereo_pose[i]] != GTG_VAR_POSE3 || p.var_type[p.stereo_point[i]] != GTG_VAR_POINT3)
+      throw std::invalid_argument("GenericStereoFactor keys must be (POSE3, POINT3)");
+    if (p.stereo_calib[i] < 0 || p.stereo_calib[i] >= p.n_calib) throw std::invalid_argument("bad calibration index");
+    const int si = p.stereo_sensor ? p.stereo_sensor[i] : -1;
+    if (si >= p.n_sensor) throw std::invalid_argument("bad body_P_sensor index");
+    if (own.n_shards > 1 && !own.owns_landmark(p.stereo_point[i])) continue;
+    pose.push_back(p.stereo_pose[i]); pt.push_back(p.stereo_point[i]); nz.push_back(p.stereo_noise[i]);
+    cal.push_back(p.stereo_calib[i]); sen.push_back(si < 0 ? -1 : si);
+    for (int k = 0; k < 3; k++) z.push_back(p.stereo_z[3 * i + k]);
   }
   f.n_proj = (int64_t)pose.size();
   up(f.proj_pose, pose, c.stream); up(f.proj_point, pt, c.stream); up(f.proj_noise, nz, c.stream); up(f.proj_calib, cal, c.stream);
@@ -272,7 +299,11 @@ void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, cons
     if (p.calib_distortion) for (int j = 0; j < 4; j++) calib[kCalibStride * (size_t)k + 5 + j] = p.calib_distortion[4 * (size_t)k + j];
   }
   up(f.calib, calib, c.stream); up(f.sensor, sensor, c.stream);
-  f.proj_J.alloc(std::max<size_t>((size_t)kProjRec * f.n_proj, 1));
+  if (f.stereo) {   // the baselines beside the table, so that the table and the kernels of a graph without stereo factors stay as they are
+    std::vector<double> bl(p.calib_baseline, p.calib_baseline + p.n_calib);
+    up(f.calib_baseline, bl, c.stream);
+  } else f.calib_baseline.free();
+  f.proj_J.alloc(std::max<size_t>((size_t)(f.stereo ? kStereoRec : kProjRec) * f.n_proj, 1));
   hi.proj_pose = pose; hi.proj_point = pt;
 }
 
@@ -331,8 +362,9 @@ void upload_problem(gtg_context& c, const gtg_problem& user, int shard, int n_sh
   c.shard = shard; c.n_shards = n_shards;
   c.n_smart = user.n_smart > 0 ? user.n_smart : 0; c.n_user_vars = user.n_vars; c.smart_obs0 = user.n_sfm;
   // GeneralSFM records recomputed where they are needed instead of stored (fused.h) -- not with smart factors, whose measurements'
-  // records depend on the factor's triangulation status
-  c.fused_sfm = GTG_FUSED_SFM != 0 && c.n_smart == 0;
+  // records depend on the factor's triangulation status, and not beside stereo factors, whose three-row records only the
+  // stored-record kernels read
+  c.fused_sfm = GTG_FUSED_SFM != 0 && c.n_smart == 0 && !(user.n_stereo > 0);
   const SmartView view(user);
   const gtg_problem& p = view.problem();
   upload_smart_state(c, user);

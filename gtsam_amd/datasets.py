@@ -384,3 +384,100 @@ def synthetic_orbit_scene(n_cams=10, n_points=120, seed=0, see=0.7, pixel_noise=
     cams[:, :9] = (R @ dR).reshape(n_cams, 9); cams[:, 9:12] = centers + rng.normal(0, init_noise[1], centers.shape)
     cams[:, 12] = f + rng.normal(0, 1.0, n_cams); cams[:, 13] = k1; cams[:, 14] = k2
     return cams, pts + rng.normal(0, 0.05, pts.shape), np.array(oc, np.int32), np.array(op, np.int32), np.array(oz)
+
+
+def stereo_mixed_graph(n_poses=6, n_points=40, seed=7):
+    """A small stereo visual-odometry graph that enters every branch of GenericStereoFactor<Pose3, Point3> on the device, built
+    through the API mirror (gtsam_amd.api) the way user code would: poses on an arc looking at a point cloud; a stereo factor for
+    every (pose, landmark) pair with one Cal3_S2Stereo, a second rig -- another Cal3_S2Stereo, with a NON-ZERO skew (which
+    StereoCamera::project2 ignores), mounted through body_P_sensor -- on a third of the pairs; dim-3 Unit / Isotropic / Diagonal /
+    Gaussian noise and Robust(Huber) on some; monocular GenericProjectionFactors (Cal3_S2, one Cal3DS2) on a subset of the same
+    landmarks; the last landmark lies BEHIND pose 0 (cheirality branch) and in front of the last two poses, its other observers; a prior on one landmark and on two poses, BetweenFactor<Pose3>
+    along the arc.  Graph order: projection, stereo, between, prior.  Returns (graph, initial values, index of the behind-camera stereo factor)."""
+    from . import api as A
+    rng = np.random.default_rng(seed)
+    ang = np.linspace(-0.5, 0.5, n_poses)
+    centers = np.stack([8 * np.sin(ang), 0.3 * rng.normal(size=n_poses), -8 * np.cos(ang)], 1)
+    R = _rodrigues(np.stack([0.02 * rng.normal(size=n_poses), -ang, 0.02 * rng.normal(size=n_poses)], 1))   # looks at the origin (+z)
+    pts = np.stack([rng.uniform(-2, 2, n_points), rng.uniform(-1.5, 1.5, n_points), rng.uniform(-2, 2, n_points)], 1)
+    pts[-1] = centers[0] - 0.5 * R[0][:, 2] + np.array([0.2, -0.1, 0.0])       # 0.5 behind pose 0 along its optical axis
+    X, L = A.symbol_shorthand.X, A.symbol_shorthand.L
+    K1 = A.Cal3_S2Stereo(720.0, 715.0, 0.0, 600.0, 170.0, 0.54)
+    K2 = A.Cal3_S2Stereo(500.0, 510.0, 0.7, 320.0, 240.0, 0.25)                 # skew 0.7: stored, not used by the projection
+    Km = A.Cal3_S2(520.0, 515.0, 0.3, 320.0, 240.0)
+    Kd = A.Cal3DS2(400.0, 400.0, 0.0, 300.0, 200.0, 0.05, -0.01, 0.001, -0.002)
+    sR = _rodrigues(np.array([[0.02, -0.03, 0.01]]))[0]; st = np.array([0.1, -0.05, 0.2])
+    sensor = A.Pose3(A.Rot3(sR), st)
+    Rg = np.array([[1.1, 0.2, -0.1], [0.0, 0.9, 0.3], [0.0, 0.0, 1.3]])
+    nm = A.noiseModel
+    models3 = [nm.Unit.Create(3), nm.Isotropic.Sigma(3, 1.5), nm.Diagonal.Sigmas([1.0, 1.2, 0.8]), nm.Gaussian.SqrtInformation(Rg),
+               nm.Robust.Create(nm.mEstimator.Huber.Create(1.345), nm.Isotropic.Sigma(3, 1.2))]
+    m2 = [nm.Isotropic.Sigma(2, 1.5), nm.Unit.Create(2)]
+
+    def stereo_z(K, Rw, tw, pt):
+        q = Rw.T @ (pt - tw)
+        if q[2] <= 0:
+            return rng.normal(300.0, 50.0, 3)
+        fx, fy, _, u0, v0, b = K.v
+        return np.array([u0 + fx * q[0] / q[2], u0 + fx * (q[0] - b) / q[2], v0 + fy * q[1] / q[2]]) + rng.normal(0, 0.7, 3)
+
+    graph, initial = A.NonlinearFactorGraph(), A.Values()
+    for i in range(min(4, n_poses)):                      # monocular factors on the first ten landmarks
+        for j in range(10):
+            q = R[i].T @ (pts[j] - centers[i])
+            u, v = q[0] / q[2], q[1] / q[2]
+            z = np.array([Km.v[0] * u + Km.v[2] * v + Km.v[3], Km.v[1] * v + Km.v[4]]) + rng.normal(0, 1.0, 2)
+            graph.add(A.GenericProjectionFactorCal3_S2(z, m2[j % 2], X(i), L(j), Km))
+    q = R[4].T @ (pts[3] - centers[4]); u, v = q[0] / q[2], q[1] / q[2]
+    rr = u * u + v * v; gg = 1 + 0.05 * rr - 0.01 * rr * rr
+    ud, vd = gg * u + 2 * 0.001 * u * v - 0.002 * (rr + 2 * u * u), gg * v + 2 * -0.002 * u * v + 0.001 * (rr + 2 * v * v)
+    graph.add(A.GenericProjectionFactorCal3DS2(np.array([400.0 * ud + 300.0, 400.0 * vd + 200.0]) + rng.normal(0, 1.0, 2), m2[0], X(4), L(3), Kd))
+    behind, k = -1, 0
+    for i in range(n_poses):
+        for j in range(n_points):
+            if j == n_points - 1 and 0 < i < n_poses - 2:
+                continue                                  # (the last landmark: seen from behind by pose 0, from the front by the last two poses only)
+            if i == 0 and j == n_points - 1:
+                behind = k
+            graph.add(A.GenericStereoFactor3D(stereo_z(K1, R[i], centers[i], pts[j]), models3[k % 5], X(i), L(j), K1)); k += 1
+            if (i * n_points + j) % 3 == 0:               # the second rig, through body_P_sensor
+                Rw, tw = R[i] @ sR, centers[i] + R[i] @ st
+                graph.add(A.GenericStereoFactor3D(stereo_z(K2, Rw, tw, pts[j]), models3[k % 5], X(i), L(j), K2, sensor)); k += 1
+    n6 = nm.Diagonal.Sigmas([0.01] * 3 + [0.05] * 3); n6b = nm.Diagonal.Sigmas([0.02, 0.02, 0.03, 0.1, 0.1, 0.15])
+    for i in range(n_poses - 1):
+        Rz = R[i].T @ R[i + 1]; tz = R[i].T @ (centers[i + 1] - centers[i])
+        graph.add(A.BetweenFactorPose3(X(i), X(i + 1), A.Pose3(A.Rot3(Rz @ _rodrigues(rng.normal(0, 0.005, (1, 3)))[0]), tz + rng.normal(0, 0.02, 3)), n6b))
+    graph.addPriorPose3(X(0), A.Pose3(A.Rot3(R[0]), centers[0]), n6)
+    graph.addPriorPose3(X(1), A.Pose3(A.Rot3(R[1]), centers[1]), n6)
+    graph.addPriorPoint3(L(0), pts[0], nm.Isotropic.Sigma(3, 0.1))
+    dR = _rodrigues(rng.normal(0, 0.01, (n_poses, 3)))
+    for i in range(n_poses):
+        initial.insert(X(i), A.Pose3(A.Rot3(R[i] @ dR[i]), centers[i] + rng.normal(0, 0.05, 3)))
+    for j in range(n_points):
+        initial.insert(L(j), pts[j] + rng.normal(0, 0.05, 3))
+    return graph, initial, behind
+
+
+def stereo_vo_graph(calibration_path, poses_path, factors_path):
+    """The graph of examples/StereoVOExample_large.cpp (:45-107) from its three data files, through the API mirror: one shared
+    Cal3_S2Stereo, Isotropic::Sigma(3, 1) (= Unit) on every GenericStereoFactor, camera poses from the 4 x 4 matrices of the pose
+    file, a landmark initialised from the first factor that names it (camPose.transformFrom of the triangulated camera-frame point).
+    Constrained noise is outside the device path: the example's NonlinearEquality<Pose3> on pose 1 is a
+    PriorFactor<Pose3> with Isotropic::Sigma(6, 1e-6) here.  Returns (graph, initial values)."""
+    from . import api as A
+    X, L = A.symbol_shorthand.X, A.symbol_shorthand.L
+    K = A.Cal3_S2Stereo(*np.loadtxt(calibration_path).reshape(-1)[:6])
+    model = A.noiseModel.Isotropic.Sigma(3, 1.0)
+    graph, initial = A.NonlinearFactorGraph(), A.Values()
+    poses = {}
+    for row in np.loadtxt(poses_path).reshape(-1, 17):
+        m = row[1:].reshape(4, 4)
+        poses[int(row[0])] = A.Pose3(A.Rot3(m[:3, :3]), m[:3, 3])
+        initial.insert(X(int(row[0])), poses[int(row[0])])
+    for x, l, uL, uR, v, px, py, pz in np.loadtxt(factors_path).reshape(-1, 8):
+        x, l = int(x), int(l)
+        graph.add(A.GenericStereoFactor3D(A.StereoPoint2(uL, uR, v), model, X(x), L(l), K))
+        if not initial.exists(L(l)):
+            initial.insert(L(l), poses[x].R @ np.array([px, py, pz]) + poses[x].t)
+    graph.addPriorPose3(X(1), poses[1], A.noiseModel.Isotropic.Sigma(6, 1e-6))
+    return graph, initial

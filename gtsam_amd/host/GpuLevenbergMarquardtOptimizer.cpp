@@ -19,6 +19,7 @@
 #include <gtsam/slam/GeneralSFMFactor.h>
 #include <gtsam/slam/ProjectionFactor.h>
 #include <gtsam/slam/SmartProjectionFactor.h>
+#include <gtsam/slam/StereoFactor.h>
 
 #include <gtsam/config.h>
 
@@ -67,6 +68,7 @@ typedef PinholeCamera<Cal3Bundler> SfmCamera;
 typedef GeneralSFMFactor<SfmCamera, Point3> SfmFactor;
 typedef GenericProjectionFactor<Pose3, Point3, Cal3_S2> ProjFactor;
 typedef GenericProjectionFactor<Pose3, Point3, Cal3DS2> ProjFactorDS2;
+typedef GenericStereoFactor<Pose3, Point3> StereoFactor;
 typedef SmartProjectionFactor<SfmCamera> SmartFactor;   // the factor of timing/timeSFMBALsmart.cpp
 // The smart factor keeps its noise model and its parameters protected and has no accessor for them; a class derived from it may
 // name them, and the pointers to member it forms are ordinary pointers to members of the factor (a maintainer binding this into
@@ -157,12 +159,13 @@ void unpack(int32_t t, const double* p, Value& v) {
 }
 // ---- Jacobian records (gtg_get_jacobians): one whitened [A1 | A2 | b] per factor, row-major blocks at fixed offsets; the record's width follows
 // the factor type, the block sizes the factor's first variable (Pose2: 3x3 blocks inside the record of the Pose3 factor)
-const int64_t kRecordWidth[4] = {26, 20, 78, 90};   // by GTG_FAC_*
+const int64_t kRecordWidth[5] = {26, 20, 78, 90, 30};   // by GTG_FAC_*
 struct RecordLayout { int rows, nblk, boff[2], bcols[2], rhs; int64_t width; };
 template <class F> RecordLayout recordLayout(int32_t fac, F&& firstVarType) {   // firstVarType(): GTG_VAR_* of the factor's first variable, asked only where the layout depends on it
   const int64_t w = kRecordWidth[fac];
   if (fac == GTG_FAC_GENERAL_SFM) return {2, 2, {0, 18}, {tangentDim(GTG_VAR_SFM_CAMERA), 3}, 24, w};
   if (fac == GTG_FAC_PROJECTION) return {2, 2, {0, 12}, {tangentDim(GTG_VAR_POSE3), 3}, 18, w};
+  if (fac == GTG_FAC_STEREO) return {3, 2, {0, 18}, {tangentDim(GTG_VAR_POSE3), 3}, 27, w};
   const int d = tangentDim(firstVarType());
   if (fac == GTG_FAC_BETWEEN_POSE3) return {d, 2, {0, 36}, {d, d}, 72, w};
   return {d, 1, {0, 0}, {d, 0}, 81, w};
@@ -170,14 +173,14 @@ template <class F> RecordLayout recordLayout(int32_t fac, F&& firstVarType) {   
 typedef std::vector<std::pair<int32_t, int64_t>> FactorMap;   // factor of graph_ -> (GTG_FAC_*, index in that type's table); (-1, 0): null; (-2, i): smart factor i
 // The device's current records, one buffer per GTG_FAC_* (null and smart factors have none: a smart factor's linearisation is a Hessian factor the device never forms)
 struct Records {
-  std::vector<double> rec[4];
+  std::vector<double> rec[5];
   const double* of(const std::pair<int32_t, int64_t>& tf) const { return rec[tf.first].data() + tf.second * kRecordWidth[tf.first]; }
 };
 Records fetchRecords(gtg_handle h, const FactorMap& fac_map) {
   Records out;
-  int64_t count[4] = {0, 0, 0, 0};
+  int64_t count[5] = {0, 0, 0, 0, 0};
   for (const auto& tf : fac_map) if (tf.first >= 0) count[tf.first]++;
-  for (int t = 0; t < 4; t++) {
+  for (int t = 0; t < 5; t++) {
     if (!count[t]) continue;
     out.rec[t].resize((size_t)(count[t] * kRecordWidth[t]));
     check(gtg_get_jacobians(h, t, out.rec[t].data(), (int64_t)out.rec[t].size()), "gtg_get_jacobians");
@@ -346,14 +349,15 @@ namespace {
 // calibrations as (run length, object) -- rows of the shared tables are handed out afterwards, sequentially, in first-occurrence
 // order, so that the tables are those of a single-threaded pass whatever the thread count.
 struct Extract {
-  std::vector<int32_t> sfm_cam, sfm_pt, pj_pose, pj_pt, pj_sen, bt_1, bt_2, pr_var, sm_cam;
-  std::vector<double> sfm_z, pj_z, sensor, bt_z, pr_data, sm_z, sm_prm;
+  std::vector<int32_t> sfm_cam, sfm_pt, pj_pose, pj_pt, pj_sen, st_pose, st_pt, st_sen, bt_1, bt_2, pr_var, sm_cam;
+  std::vector<double> sfm_z, pj_z, st_z, sensor, bt_z, pr_data, sm_z, sm_prm;
   std::vector<int64_t> pr_off, sm_ptr;
   FactorMap fac_map;                                                        // (type, index in THIS chunk's table of that type)
   typedef std::vector<std::pair<int64_t, SharedNoiseModel>> Runs;
-  Runs sfm_nz, pj_nz, bt_nz, pr_nz, sm_nz;
+  Runs sfm_nz, pj_nz, st_nz, bt_nz, pr_nz, sm_nz;
   std::vector<int32_t> bt_dim, pr_dim;                                      // expected noise dimension per between / prior factor
   std::vector<std::pair<const void*, int>> pj_cal;                          // calibration object per projection factor, 1 = Cal3DS2
+  std::vector<const Cal3_S2Stereo*> st_cal;                                 // calibration object per stereo factor
   std::exception_ptr err;                                                   // what the chunk's first offending factor threw
   static void run(Runs& r, const SharedNoiseModel& nm) { if (!r.empty() && r.back().second.get() == nm.get()) r.back().first++; else r.emplace_back(1, nm); }
   static double* grow(std::vector<double>& v, size_t n) { v.resize(v.size() + n); return v.data() + v.size() - n; }   // n more doubles, zero-filled
@@ -374,6 +378,18 @@ template <class CAL> void addProjection(Extract& x, const GenericProjectionFacto
   x.pj_cal.emplace_back(p.calibration().get(), std::is_same<CAL, Cal3DS2>::value ? 1 : 0);
   if (p.body_P_sensor()) { x.pj_sen.push_back((int32_t)(x.sensor.size() / 12)); packPose(*p.body_P_sensor(), Extract::grow(x.sensor, 12)); }
   else x.pj_sen.push_back(-1);
+}
+// GenericStereoFactor<Pose3, Point3> (slam/StereoFactor.h): measurement (uL, uR, v), shared Cal3_S2Stereo, optional body_P_sensor in the
+// sensor table of the projection factors
+void addStereo(Extract& x, const StereoFactor& p, const std::vector<Key>& keys) {
+  x.fac_map.emplace_back(GTG_FAC_STEREO, (int64_t)x.st_pose.size());
+  if (p.throwCheirality()) throw std::invalid_argument("GenericStereoFactor with throwCheirality is not supported");
+  x.st_pose.push_back(idOf(keys, p.key1())); x.st_pt.push_back(idOf(keys, p.key2()));
+  x.st_z.push_back(p.measured().uL()); x.st_z.push_back(p.measured().uR()); x.st_z.push_back(p.measured().v());
+  Extract::run(x.st_nz, p.noiseModel());
+  x.st_cal.push_back(p.calibration().get());
+  if (p.body_P_sensor()) { x.st_sen.push_back((int32_t)(x.sensor.size() / 12)); packPose(*p.body_P_sensor(), Extract::grow(x.sensor, 12)); }
+  else x.st_sen.push_back(-1);
 }
 void addSmart(Extract& x, const SmartFactor& sf, const std::vector<Key>& keys) {
   x.fac_map.emplace_back(-2, (int64_t)x.sm_prm.size() / 8);   // (no Jacobian record: its linearisation is a Hessian factor)
@@ -412,6 +428,7 @@ void addFactor(Extract& x, const NonlinearFactor* f, const std::vector<Key>& key
   if (auto s = dynamic_cast<const SfmFactor*>(f)) addSfm(x, *s, keys);
   else if (auto p = dynamic_cast<const ProjFactor*>(f)) addProjection(x, *p, keys);
   else if (auto pd = dynamic_cast<const ProjFactorDS2*>(f)) addProjection(x, *pd, keys);
+  else if (auto st = dynamic_cast<const StereoFactor*>(f)) addStereo(x, *st, keys);
   else if (auto sf = dynamic_cast<const SmartFactor*>(f)) addSmart(x, *sf, keys);
   else if (auto bb = dynamic_cast<const BetweenFactor<Pose3>*>(f)) addBetween(x, *bb, keys);
   else if (auto b2 = dynamic_cast<const BetweenFactor<Pose2>*>(f)) addBetween(x, *b2, keys);
@@ -421,7 +438,7 @@ void addFactor(Extract& x, const NonlinearFactor* f, const std::vector<Key>& key
   else if (auto p3 = dynamic_cast<const PriorFactor<Point3>*>(f)) addPrior(x, *p3, keys);
   else throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: factor type outside the GPU hot path "   // (anything else is a hard error)
                                    "(supported: GeneralSFMFactor<SfmCamera,Point3>, GenericProjectionFactor<Pose3,Point3,Cal3_S2|Cal3DS2>, "
-                                   "SmartProjectionFactor<SfmCamera>, BetweenFactor<Pose3|Pose2>, PriorFactor<Pose3|Pose2|SfmCamera|Point3>)");
+                                   "GenericStereoFactor<Pose3,Point3>, SmartProjectionFactor<SfmCamera>, BetweenFactor<Pose3|Pose2>, PriorFactor<Pose3|Pose2|SfmCamera|Point3>)");
 }
 // The factors [b, e) of `graph` into x, each pointer also copied into `graphCopy`; the chunk stops at its first offending factor and keeps what that threw.
 void extractChunk(Extract& x, const NonlinearFactorGraph& graph, NonlinearFactorGraph& graphCopy, const std::vector<Key>& keys, size_t b, size_t e) {
@@ -450,16 +467,17 @@ template <class T> struct Raw {
   T* data() const { return p.get(); } size_t size() const { return n; }
 };
 typedef Raw<int32_t> RawI; typedef Raw<double> RawD;
-struct Place { int64_t o_sfm, o_pj, o_bt, o_pr, o_sm; std::vector<std::pair<int64_t, int32_t>> sfm_rows; };   // per chunk: offsets of its tables, (count, noise row) of its GeneralSFM runs
+struct Place { int64_t o_sfm, o_pj, o_st, o_bt, o_pr, o_sm; std::vector<std::pair<int64_t, int32_t>> sfm_rows; };   // per chunk: offsets of its tables, (count, noise row) of its GeneralSFM runs
 struct HostProblem {
   NoiseTable nt;
   RawI sfm_cam, sfm_pt, sfm_nz;
   RawD sfm_z;
-  std::vector<int32_t> pj_pose, pj_pt, pj_nz, pj_cal, pj_sen, bt_1, bt_2, bt_nz, pr_var, pr_nz, sm_cam, sm_nz;
-  std::vector<double> pj_z, calib, sensor, bt_z, pr_data, sm_z, sm_prm;
+  std::vector<int32_t> pj_pose, pj_pt, pj_nz, pj_cal, pj_sen, st_pose, st_pt, st_nz, st_cal, st_sen, bt_1, bt_2, bt_nz, pr_var, pr_nz, sm_cam, sm_nz;
+  std::vector<double> pj_z, st_z, calib, sensor, bt_z, pr_data, sm_z, sm_prm;
   std::vector<int64_t> pr_off, sm_ptr{0};    // (smart factors: one track each)
   std::map<const void*, int32_t> calib_id;   // shared calibration objects (Cal3_S2 or Cal3DS2) -> row of the calibration table
   std::vector<double> calib_dist;            // k1 k2 p1 p2 per row (zero for a Cal3_S2)
+  std::vector<double> calib_base;            // baseline per row (zero unless the row is a Cal3_S2Stereo)
   bool any_distortion = false;
   template <class CAL> void pinhole(const CAL* K) { calib.insert(calib.end(), {K->fx(), K->fy(), K->skew(), K->px(), K->py()}); }
   int32_t calibRow(const void* object, int distorted) {
@@ -469,6 +487,14 @@ struct HostProblem {
     const Cal3DS2* D = distorted ? static_cast<const Cal3DS2*>(object) : nullptr;
     if (D) { pinhole(D); calib_dist.insert(calib_dist.end(), {D->k1(), D->k2(), D->p1(), D->p2()}); any_distortion = true; }
     else { pinhole(static_cast<const Cal3_S2*>(object)); calib_dist.insert(calib_dist.end(), {0.0, 0.0, 0.0, 0.0}); }
+    calib_base.push_back(0.0);
+    return it->second;
+  }
+  int32_t stereoCalibRow(const Cal3_S2Stereo* K) {
+    auto it = calib_id.find(K);
+    if (it != calib_id.end()) return it->second;
+    it = calib_id.emplace(K, (int32_t)(calib.size() / 5)).first;
+    pinhole(K); calib_dist.insert(calib_dist.end(), {0.0, 0.0, 0.0, 0.0}); calib_base.push_back(K->baseline());
     return it->second;
   }
   gtg_problem view(const std::vector<int32_t>& var_type) const {   // (pointers into this object and into var_type: both outlive the upload)
@@ -482,6 +508,9 @@ struct HostProblem {
     pb.proj_noise = pj_nz.data(); pb.proj_calib = pj_cal.data(); pb.proj_sensor = pj_sen.data();
     pb.n_calib = (int32_t)(calib.size() / 5); pb.calib = calib.data(); pb.calib_distortion = any_distortion ? calib_dist.data() : nullptr;
     pb.n_sensor = (int32_t)(sensor.size() / 12); pb.sensor = sensor.data();
+    pb.n_stereo = (int64_t)st_pose.size(); pb.stereo_pose = st_pose.data(); pb.stereo_point = st_pt.data(); pb.stereo_z = st_z.data();
+    pb.stereo_noise = st_nz.data(); pb.stereo_calib = st_cal.data(); pb.stereo_sensor = st_sen.data();
+    pb.calib_baseline = pb.n_stereo ? calib_base.data() : nullptr;
     pb.n_between = (int64_t)bt_1.size(); pb.between_v1 = bt_1.data(); pb.between_v2 = bt_2.data(); pb.between_z = bt_z.data(); pb.between_noise = bt_nz.data();
     pb.n_smart = (int64_t)sm_nz.size(); pb.smart_ptr = sm_ptr.data(); pb.smart_cam = sm_cam.data(); pb.smart_z = sm_z.data();
     pb.smart_noise = sm_nz.data(); pb.smart_params = sm_prm.data();
@@ -567,6 +596,7 @@ HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap
     size_t at = 0;
     for (const auto& r : runs) { dst.insert(dst.end(), (size_t)r.first, hp.nt.add(r.second, expect_dim ? (size_t)(*expect_dim)[at] : 2)); at += (size_t)r.first; }
   };
+  auto rows3 = [&hp](std::vector<int32_t>& dst, const Extract::Runs& runs) { for (const auto& r : runs) dst.insert(dst.end(), (size_t)r.first, hp.nt.add(r.second, 3)); };
   size_t n_sfm = 0, n_pj = 0, n_bt = 0;
   for (const Extract& x : part) { n_sfm += x.sfm_cam.size(); n_pj += x.pj_pose.size(); n_bt += x.bt_1.size(); }
   hp.sfm_cam.alloc(n_sfm); hp.sfm_pt.alloc(n_sfm); hp.sfm_nz.alloc(n_sfm); hp.sfm_z.alloc(2 * n_sfm);
@@ -578,7 +608,7 @@ HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap
   for (size_t pi = 0; pi < part.size(); pi++) {
     const Extract& x = part[pi];
     const int64_t o_sen = (int64_t)(hp.sensor.size() / 12), o_prd = (int64_t)hp.pr_data.size(), o_smc = (int64_t)hp.sm_cam.size();
-    place[pi].o_sfm = o_sfm_next; place[pi].o_pj = (int64_t)hp.pj_pose.size(); place[pi].o_bt = (int64_t)hp.bt_1.size();
+    place[pi].o_sfm = o_sfm_next; place[pi].o_pj = (int64_t)hp.pj_pose.size(); place[pi].o_st = (int64_t)hp.st_pose.size(); place[pi].o_bt = (int64_t)hp.bt_1.size();
     place[pi].o_pr = (int64_t)hp.pr_var.size(); place[pi].o_sm = (int64_t)hp.sm_nz.size();
     o_sfm_next += (int64_t)x.sfm_cam.size();
     for (const auto& r : x.sfm_nz) place[pi].sfm_rows.emplace_back(r.first, hp.nt.add(r.second, 2));
@@ -587,6 +617,10 @@ HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap
     for (int32_t sidx : x.pj_sen) hp.pj_sen.push_back(sidx < 0 ? -1 : (int32_t)(sidx + o_sen));
     cat(hp.sensor, x.sensor);
     for (const auto& kc : x.pj_cal) hp.pj_cal.push_back(hp.calibRow(kc.first, kc.second));
+    cat(hp.st_pose, x.st_pose); cat(hp.st_pt, x.st_pt); cat(hp.st_z, x.st_z);
+    rows3(hp.st_nz, x.st_nz);
+    for (int32_t sidx : x.st_sen) hp.st_sen.push_back(sidx < 0 ? -1 : (int32_t)(sidx + o_sen));
+    for (const Cal3_S2Stereo* K : x.st_cal) hp.st_cal.push_back(hp.stereoCalibRow(K));
     cat(hp.bt_1, x.bt_1); cat(hp.bt_2, x.bt_2); cat(hp.bt_z, x.bt_z);
     rows(hp.bt_nz, x.bt_nz, &x.bt_dim);
     cat(hp.pr_var, x.pr_var); cat(hp.pr_data, x.pr_data);
@@ -609,7 +643,7 @@ HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap
     }
     auto* fm_out = fac_map->data() + cut(nfac, part.size(), pi);     // (the chunk's factors: the range extractFactors gave it)
     for (const auto& fm : x.fac_map)
-      *fm_out++ = {fm.first, fm.second + (fm.first == GTG_FAC_GENERAL_SFM ? pl.o_sfm : fm.first == GTG_FAC_PROJECTION ? pl.o_pj :
+      *fm_out++ = {fm.first, fm.second + (fm.first == GTG_FAC_GENERAL_SFM ? pl.o_sfm : fm.first == GTG_FAC_PROJECTION ? pl.o_pj : fm.first == GTG_FAC_STEREO ? pl.o_st :
                                            fm.first == GTG_FAC_BETWEEN_POSE3 ? pl.o_bt : fm.first == GTG_FAC_PRIOR ? pl.o_pr : fm.first == -2 ? pl.o_sm : 0)};
   });
   return hp;

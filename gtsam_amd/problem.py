@@ -14,7 +14,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 VAR_POSE3, VAR_SFM_CAMERA, VAR_POINT3, VAR_POSE2 = 0, 1, 2, 3
-FAC_GENERAL_SFM, FAC_PROJECTION, FAC_BETWEEN_POSE3, FAC_PRIOR = 0, 1, 2, 3
+FAC_GENERAL_SFM, FAC_PROJECTION, FAC_BETWEEN_POSE3, FAC_PRIOR, FAC_STEREO = 0, 1, 2, 3, 4
 NOISE_UNIT, NOISE_ISOTROPIC, NOISE_DIAGONAL, NOISE_GAUSSIAN = 0, 1, 2, 3
 ROBUST_NONE, ROBUST_FAIR, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY, ROBUST_WELSCH, ROBUST_GEMANMCCLURE, ROBUST_DCS, ROBUST_L2WITHDEADZONE = range(9)
 
@@ -40,6 +40,8 @@ class gtg_problem(C.Structure):
         ("calib_distortion", _f64p),
         ("n_smart", C.c_int64), ("smart_ptr", _i64p), ("smart_cam", _i32p), ("smart_z", _f64p), ("smart_noise", _i32p),
         ("smart_params", _f64p),
+        ("n_stereo", C.c_int64), ("stereo_pose", _i32p), ("stereo_point", _i32p), ("stereo_z", _f64p), ("stereo_noise", _i32p),
+        ("stereo_calib", _i32p), ("stereo_sensor", _i32p), ("calib_baseline", _f64p),
     ]
 
 
@@ -75,6 +77,14 @@ class Problem:
     smart_z: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float64))
     smart_noise: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     smart_params: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float64))
+    # GenericStereoFactor<Pose3, Point3>: measurement (uL, uR, v), calibration = an entry of `calib` plus its `calib_baseline`
+    stereo_pose: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    stereo_point: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    stereo_z: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float64))
+    stereo_noise: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    stereo_calib: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    stereo_sensor: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    calib_baseline: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float64))   # [n_calib] or empty (no stereo factors)
     sensor: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float64))
     between_v1: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     between_v2: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
@@ -96,7 +106,10 @@ class Problem:
                          ("between_v1", np.int32), ("between_v2", np.int32),
                          ("between_z", np.float64), ("between_noise", np.int32),
                          ("prior_var", np.int32), ("prior_off", np.int64),
-                         ("prior_data", np.float64), ("prior_noise", np.int32)):
+                         ("prior_data", np.float64), ("prior_noise", np.int32),
+                         ("stereo_pose", np.int32), ("stereo_point", np.int32), ("stereo_z", np.float64),
+                         ("stereo_noise", np.int32), ("stereo_calib", np.int32), ("stereo_sensor", np.int32),
+                         ("calib_baseline", np.float64)):
             setattr(self, name, _a(getattr(self, name), dt))
 
     # ---- sizes -------------------------------------------------------------------------------
@@ -106,6 +119,8 @@ class Problem:
     def n_sfm(self): return int(self.sfm_cam.size)
     @property
     def n_proj(self): return int(self.proj_pose.size)
+    @property
+    def n_stereo(self): return int(self.stereo_pose.size)
     @property
     def n_between(self): return int(self.between_v1.size)
     @property
@@ -203,6 +218,20 @@ class Problem:
         p.smart_z = ptr(self.smart_z, C.c_double)
         p.smart_noise = ptr(self.smart_noise, C.c_int32)
         p.smart_params = ptr(self.smart_params, C.c_double)
+        p.n_stereo = self.n_stereo
+        if self.n_stereo:
+            if self.stereo_sensor.size == 0:
+                self.stereo_sensor = np.full(self.n_stereo, -1, np.int32)
+            if self.stereo_z.size != 3 * self.n_stereo or self.calib_baseline.size != p.n_calib or \
+               any(a.size != self.n_stereo for a in (self.stereo_point, self.stereo_noise, self.stereo_calib, self.stereo_sensor)):
+                raise ValueError("inconsistent stereo factor tables (calib_baseline holds one baseline per calibration)")
+        p.stereo_pose = ptr(self.stereo_pose, C.c_int32)
+        p.stereo_point = ptr(self.stereo_point, C.c_int32)
+        p.stereo_z = ptr(self.stereo_z, C.c_double)
+        p.stereo_noise = ptr(self.stereo_noise, C.c_int32)
+        p.stereo_calib = ptr(self.stereo_calib, C.c_int32)
+        p.stereo_sensor = ptr(self.stereo_sensor, C.c_int32)
+        p.calib_baseline = ptr(self.calib_baseline, C.c_double)
         p._keep = keep
         return p
 

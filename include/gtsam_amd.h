@@ -45,7 +45,13 @@ enum { GTG_FAC_GENERAL_SFM = 0,   /* GeneralSFMFactor<PinholeCamera<Cal3Bundler>
        GTG_FAC_PROJECTION = 1,    /* GenericProjectionFactor<Pose3,Point3,Cal3_S2>        slam/ProjectionFactor.h:138-166 */
        GTG_FAC_BETWEEN_POSE3 = 2, /* BetweenFactor<Pose3>, or BetweenFactor<Pose2> when its  slam/BetweenFactor.h:111-124
                                      two variables are POSE2 (same table, see between_z)                                  */
-       GTG_FAC_PRIOR = 3 };       /* PriorFactor<T>                                        nonlinear/PriorFactor.h:98-102 */
+       GTG_FAC_PRIOR = 3,         /* PriorFactor<T>                                        nonlinear/PriorFactor.h:98-102 */
+       GTG_FAC_STEREO = 4 };      /* GenericStereoFactor<Pose3,Point3>                     slam/StereoFactor.h:126-154:
+                                     residual h(x) - z with THREE rows (uL, uR, v), h = StereoCamera::project2
+                                     (geometry/StereoCamera.cpp:37-79) with a Cal3_S2Stereo (fx, fy, u0, v0 and a baseline; the skew is
+                                     stored and not used, as there); body_P_sensor: H1 = H1 * H0 of pose.compose(sensor, H0) (:129-135);
+                                     q.z <= 0 (StereoCheiralityException, throwCheirality_ = false): both Jacobians zero, residual
+                                     Vector3::Constant(2 fx) (:144-153).  Its landmark is eliminated like a projection factor's. */
 
 /* Noise models (linear/NoiseModel.cpp).  whiten(v) is
  *   UNIT v ; ISOTROPIC v*invsigma (:641-663) ; DIAGONAL v.*invsigmas (:311-325) ; GAUSSIAN R*v (:163-181)
@@ -139,6 +145,18 @@ typedef struct gtg_problem {
                                      linearize() / error() -- the point at infinity behind one of the track's cameras
                                      or the enableEPI refinement linearising behind a camera (CheiralityException),
                                      Cal3Bundler::calibrate not converging -- the call returns an error */
+
+  /* GTG_FAC_STEREO: GenericStereoFactor<Pose3, Point3> (slam/StereoFactor.h), the factor of examples/StereoVOExample*.cpp.  NULL / 0: no
+   * stereo factors.  (Appended after the smart tables: a caller built against the older struct must be recompiled.) */
+  int64_t n_stereo;
+  const int32_t* stereo_pose;     /* [n_stereo] variable id of the POSE3 */
+  const int32_t* stereo_point;    /* [n_stereo] variable id of the POINT3 */
+  const double* stereo_z;         /* [n_stereo*3] measured StereoPoint2: uL, uR, v */
+  const int32_t* stereo_noise;    /* [n_stereo] index into the noise table (dim 3) */
+  const int32_t* stereo_calib;    /* [n_stereo] index into the calib table above (fx, fy, s, u0, v0 of the Cal3_S2Stereo) */
+  const int32_t* stereo_sensor;   /* [n_stereo] index into the sensor table or -1; NULL: no factor has a body_P_sensor */
+  const double* calib_baseline;   /* [n_calib] Cal3_S2Stereo::baseline(); read only for the entries a stereo factor refers to; must be
+                                     non-NULL when n_stereo > 0 */
 } gtg_problem;
 
 /* ---- lifetime -------------------------------------------------------------------------------- */
@@ -154,7 +172,7 @@ const char* gtg_version(void);
 /* One-time symbolic analysis + upload.  Replaces what the reference redoes on EVERY lambda try:
  * VariableIndex (inference/VariableIndex-inl.h:27-49), EliminationTree
  * (EliminationTree-inst.h:77-155), JunctionTree (JunctionTree-inst.h:63-151), Scatter
- * (linear/Scatter.cpp:39-73).  Landmarks (POINT3 touched only by projection factors / priors) are
+ * (linear/Scatter.cpp:39-73).  Landmarks (POINT3 touched only by projection / stereo factors / priors) are
  * eliminated first -- the Schur ordering of timing/timeSFMBAL.h:74-83 -- the remaining variables
  * form the reduced system.  shard/n_shards: this handle owns landmark-factors with
  * (landmark rank) % n_shards == shard and other factors with (factor index) % n_shards == shard
@@ -230,7 +248,9 @@ int gtg_get_gradient(gtg_handle h, double* g, int64_t n);             /* J^T b, 
 int gtg_get_hessian_diagonal(gtg_handle h, double* d, int64_t n);     /* GaussianFactorGraph::hessianDiagonal */
 /* whitened Jacobian blocks + rhs of factor type `factor_type` after gtg_linearize():
  * row-major per factor: SFM [A1 2x9 | A2 2x3 | b 2], PROJECTION [2x6 | 2x3 | 2],
- * BETWEEN [6x6 | 6x6 | 6], PRIOR [d x d | d] padded to d=9 (81+9). n = doubles available in out. */
+ * BETWEEN [6x6 | 6x6 | 6], PRIOR [d x d | d] padded to d=9 (81+9), STEREO [A1 3x6 | A2 3x3 | b 3] (30 doubles, the caller's stereo
+ * factors in the caller's order; PROJECTION keeps returning the 20-double records of the monocular factors alone).
+ * n = doubles available in out. */
 int gtg_get_jacobians(gtg_handle h, int factor_type, double* out, int64_t n);
 int64_t gtg_reduced_dim(gtg_handle h);
 /* dense damped reduced system of the last try: S (n x n row-major, lower triangle valid; after the
