@@ -289,6 +289,21 @@ class SmartProjectionFactorPinholeCameraCal3Bundler:
         self.zs.append(np.asarray(measured, np.float64)); self.keys_.append(key)
 
 
+class SmartProjectionPose3Factor:
+    """SmartProjectionPoseFactor<Cal3_S2> under the name of GTSAM's Python wrapper (slam/slam.i; examples/SFMExample_SmartFactor.cpp):
+    the keys are Pose3 variables, K is shared and fixed, body_P_sensor optional; add(measured, poseKey) per view."""
+
+    def __init__(self, sharedNoiseModel, K: Cal3_S2, body_P_sensor: Pose3 | None = None, params: SmartProjectionParams | None = None):
+        self.model, self.K, self.sensor, self.params = sharedNoiseModel, K, body_P_sensor, params or SmartProjectionParams()
+        self.keys_, self.zs = [], []
+
+    def add(self, measured, poseKey):
+        self.zs.append(np.asarray(measured, np.float64)); self.keys_.append(poseKey)
+
+    def calibration(self): return self.K
+    def body_P_sensor(self): return self.sensor or Pose3()
+
+
 class BetweenFactorPose3:
     def __init__(self, key1, key2, measured: Pose3, model):
         self.keys_, self.z, self.model = (key1, key2), measured, model
@@ -383,6 +398,7 @@ def extract(graph: NonlinearFactorGraph, values: Values):
 
     sfm, proj, btw, stereo = [], [], [], []
     calibs, sensors = {}, []
+    smart_sensors = {}      # pose-type smart factors share their sensor rows (one body_P_sensor for a whole front end)
     for f in graph.factors:
         if isinstance(f, GeneralSFMFactorCal3Bundler):
             sfm.append((vid(f.keys_[0]), vid(f.keys_[1]), f.z, nid(f.model, 2)))
@@ -406,6 +422,20 @@ def extract(graph: NonlinearFactorGraph, values: Values):
             sp = f.params
             p.add_smart([vid(k) for k in f.keys_], np.concatenate(f.zs), nid(f.model, 2), sp.rankTolerance, sp.landmarkDistanceThreshold,
                         sp.dynamicOutlierRejectionThreshold, sp.retriangulationThreshold, sp.degeneracyMode, sp.linearizationMode, sp.enableEPI)
+        elif isinstance(f, SmartProjectionPose3Factor):
+            ck = f.K.v.tobytes()
+            if ck not in calibs:
+                calibs[ck] = (len(calibs), f.K.v)
+            si = -1
+            if f.sensor is not None:
+                sk = f.sensor.packed().tobytes()
+                if sk not in smart_sensors:
+                    smart_sensors[sk] = len(sensors); sensors.append(f.sensor.packed())
+                si = smart_sensors[sk]
+            sp = f.params
+            p.add_smart([vid(k) for k in f.keys_], np.concatenate(f.zs), nid(f.model, 2), sp.rankTolerance, sp.landmarkDistanceThreshold,
+                        sp.dynamicOutlierRejectionThreshold, sp.retriangulationThreshold, sp.degeneracyMode, sp.linearizationMode, sp.enableEPI,
+                        calib=calibs[ck][0], sensor=si)
         elif isinstance(f, BetweenFactorPose3):
             btw.append((vid(f.keys_[0]), vid(f.keys_[1]), f.z.packed(), nid(f.model, 6)))
         elif isinstance(f, BetweenFactorPose2):   # same table: the measurement sits in the first 3 of the 12 doubles
@@ -429,7 +459,7 @@ def extract(graph: NonlinearFactorGraph, values: Values):
         p.stereo_pose = np.array([s[0] for s in stereo], np.int32); p.stereo_point = np.array([s[1] for s in stereo], np.int32)
         p.stereo_z = np.concatenate([s[2] for s in stereo]); p.stereo_noise = np.array([s[3] for s in stereo], np.int32)
         p.stereo_calib = np.array([s[4] for s in stereo], np.int32); p.stereo_sensor = np.array([s[5] for s in stereo], np.int32)
-    if proj or stereo:
+    if proj or stereo or calibs:
         rows = [c[1] for c in sorted(calibs.values(), key=lambda c: c[0])]
         p.calib = np.concatenate([r[:5] for r in rows])
         if any(r.size == 9 for r in rows):      # Cal3DS2 entries: k1, k2, p1, p2 per calibration (zero rows for a Cal3_S2)

@@ -536,8 +536,8 @@ int gtg_get_jacobians(gtg_handle c, int type, double* out, int64_t n) {
   DeviceGuard on_device(c->device);
   const double* src; int64_t cnt;
   switch (type) {
-    case GTG_FAC_GENERAL_SFM: src = c->f.sfm_J.p; cnt = (c->n_smart ? c->smart_obs0 : c->f.n_sfm) * kSfmRec; break;   // (not the observations of smart factors)
-    case GTG_FAC_PROJECTION: src = c->f.proj_J.p; cnt = c->f.n_mono * kProjRec; break;
+    case GTG_FAC_GENERAL_SFM: src = c->f.sfm_J.p; cnt = (c->n_smart && !c->smart_pose ? c->smart_obs0 : c->f.n_sfm) * kSfmRec; break;   // (not the observations of smart factors)
+    case GTG_FAC_PROJECTION: src = c->f.proj_J.p; cnt = (c->smart_pose ? c->smart_obs0 : c->f.n_mono) * kProjRec; break;   // (not the observations of pose-type smart factors)
     case GTG_FAC_BETWEEN_POSE3: src = c->f.between_J.p; cnt = c->f.n_between * kBetweenRec; break;
     case GTG_FAC_PRIOR: src = c->f.prior_J.p; cnt = c->f.n_prior * kPriorRec; break;
     case GTG_FAC_STEREO: src = c->f.proj_J.p + (int64_t)kStereoRec * c->f.n_mono; cnt = (c->f.n_proj - c->f.n_mono) * kStereoRec; break;

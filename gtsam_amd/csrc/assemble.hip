@@ -780,7 +780,8 @@ static inline double inv_sigma(double lambda) {
 // one lane per camera / pose subtracts the squared row norms of E_o = Jc^T Jp L^-T over its smart observations (in list order).
 __global__ __launch_bounds__(kBlock) void k_smart_hdiag(int32_t n_red_vars, const int64_t* __restrict__ inc_ptr, const int32_t* __restrict__ inc_kind,
     const int32_t* __restrict__ inc_idx, const int32_t* __restrict__ red_dim, const int64_t* __restrict__ red_off,
-    const int32_t* __restrict__ sfm_smart, const int32_t* __restrict__ status, const double* __restrict__ E, double* __restrict__ hdiag) {
+    const int32_t* __restrict__ obs_smart, const int32_t* __restrict__ status, const double* __restrict__ E, double* __restrict__ hdiag,
+    int kind, int64_t first_obs) {
   // one workgroup per camera / pose: the incidence list dealt round-robin to the lanes, partial sums combined in lane order
   // (a lane per camera took 50 ms per linearisation on a 150-camera scene with 1 500 measurements each)
   __shared__ double part[kBlock][9];
@@ -789,11 +790,13 @@ __global__ __launch_bounds__(kBlock) void k_smart_hdiag(int32_t n_red_vars, cons
   const int d = red_dim[r];
   double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int64_t k = inc_ptr[r] + threadIdx.x; k < inc_ptr[r + 1]; k += kBlock) {
-    if (inc_kind[k] != 0) continue;                      // GeneralSFM observations only
+    // the range the smart measurements live in: kind = INC_SFM (first_obs = 0: 9 rows for a camera) or, pose-type factors, INC_PROJ
+    // (first_obs = n_sfm, the projection observations' place among the E slots: 6 rows for a pose)
+    if (inc_kind[k] != kind) continue;
     const int64_t o = inc_idx[k];
-    const int sm = sfm_smart[o];
+    const int sm = obs_smart[o];
     if (sm < 0 || (status[sm] != 0 && !(status[sm] & kTriAtInfinity))) continue;
-    const double* Eo = E + kEStride * o;
+    const double* Eo = E + kEStride * (first_obs + o);
     for (int i = 0; i < d; i++) acc[i] += Eo[3 * i] * Eo[3 * i] + Eo[3 * i + 1] * Eo[3 * i + 1] + Eo[3 * i + 2] * Eo[3 * i + 2];
   }
   for (int i = 0; i < 9; i++) part[threadIdx.x][i] = acc[i];
@@ -830,7 +833,8 @@ __global__ __launch_bounds__(kBlock) void k_smart_lin1(int32_t n_lm, const int32
 void launch_smart_hdiag(gtg_context& c) {
   if (!c.n_smart) return;
   hipLaunchKernelGGL(k_smart_hdiag, dim3((unsigned)std::max(c.n_red_vars, 1)), dim3(kBlock), 0, c.stream, c.n_red_vars, c.red_inc_ptr.p, c.red_inc_kind.p,
-                     c.red_inc_idx.p, c.red_dim.p, c.red_off.p, c.sfm_smart.p, c.smart_lin_status.p, c.E.p, c.hdiag_red.p);
+                     c.red_inc_idx.p, c.red_dim.p, c.red_off.p, c.obs_smart.p, c.smart_lin_status.p, c.E.p, c.hdiag_red.p,
+                     c.smart_pose ? (int)INC_PROJ : (int)INC_SFM, c.smart_pose ? c.f.n_sfm : (int64_t)0);
   check_hip(hipGetLastError(), "smart_hdiag");
 }
 void launch_smart_lin1(gtg_context& c) {

@@ -203,7 +203,8 @@ struct gtg_context {
   int64_t val_size = 0, dim_size = 0;
   // Smart factors (SmartProjectionFactor): every factor owns a HIDDEN landmark variable (ids n_user_vars .. n_vars-1, appended
   // behind the caller's variables, so the caller's values / tangent vectors are prefixes of the device's) that is re-triangulated
-  // from the cameras instead of being optimised; its measurements are GeneralSFM observations smart_obs0 .. of the sfm tables.
+  // from the cameras instead of being optimised; its measurements are GeneralSFM observations smart_obs0 .. of the sfm tables
+  // (camera-type factors; pose-type factors: smart_pose below).
   int32_t n_user_vars = 0;
   int64_t user_val_size = 0, user_dim_size = 0;
   int64_t n_smart = 0, smart_obs0 = 0;
@@ -218,7 +219,10 @@ struct gtg_context {
   gt::DevBuf<int32_t> smart_cache_state;    // per factor: -1 nothing cached, else the cached status
   gt::DevBuf<double> smart_cache_pose;      // 12 per measurement: the camera poses of the cached triangulation
   gt::DevBuf<double> smart_cache_point;     // 3 per factor
-  gt::DevBuf<int32_t> sfm_smart, lm_smart;  // per sfm observation / per landmark: its smart factor or -1
+  // SmartProjectionPoseFactor<Cal3_S2> (gtg_problem.smart_calib >= 0): the measurements are PROJECTION observations smart_obs0 .. of
+  // the proj tables instead (keys POSE3, one shared Cal3_S2, optional body_P_sensor); a graph has smart factors of one kind only
+  bool smart_pose = false;
+  gt::DevBuf<int32_t> obs_smart, lm_smart;  // per observation of the range the smart measurements live in (GeneralSFM, or projection when smart_pose) / per landmark: its smart factor or -1
   gt::DevBuf<int32_t> var_type;
   gt::DevBuf<int64_t> val_off, dim_off;
   gt::DevBuf<double> values, trial, delta;

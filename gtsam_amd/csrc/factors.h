@@ -181,6 +181,62 @@ GT_HD double proj_error(const double* pose, const double* K, const double* senso
   return factor_loss(n, r[0] * r[0] + r[1] * r[1]);
 }
 
+// One measurement of a SmartProjectionPoseFactor<Cal3_S2> whose landmark is a point at infinity (SmartFactorBase::computeJacobians<Unit3>,
+// slam/SmartFactorBase.h:203-239, whitened by the isotropic model): the projection record with F = Dpose (rotation part only) times
+// the H of world_P_body.compose(body_P_sensor) when there is a sensor (:216-233), the landmark block 2 x 2 padded with a zero column.
+// false where the reference throws a CheiralityException (not caught by the smart factor).
+GT_HD bool proj_linearize_at_infinity(const double* pose, const double* K, const double* sensor, const double* dir,
+                                      const double* z, const NoiseRef& n, double* J) {
+  double pi[2];
+  bool ok;
+  if (sensor) {
+    double T[12], Dp[12], Si[12], H0[36];
+    pose_compose(pose, sensor, T);
+    ok = s2_project_at_infinity(T, K, dir, pi, Dp, J + 12);
+    if (ok) {
+      pose_inverse(sensor, Si);
+      pose_adjoint(Si, H0);
+      for (int r = 0; r < 2; r++)
+        for (int c = 0; c < 6; c++) {
+          double acc = 0.0;
+          for (int k = 0; k < 6; k++) acc += Dp[6 * r + k] * H0[6 * k + c];
+          J[6 * r + c] = acc;
+        }
+    }
+  } else {
+    ok = s2_project_at_infinity(pose, K, dir, pi, J, J + 12);
+  }
+  if (!ok) {
+    for (int i = 0; i < kProjRec; i++) J[i] = 0.0;
+    return false;
+  }
+  J[18] = z[0] - pi[0];
+  J[19] = z[1] - pi[1];
+  whiten_cols<2>(n.kind, n.data, J, 6);
+  whiten_cols<2>(n.kind, n.data, J + 12, 3);
+  whiten_cols<2>(n.kind, n.data, J + 18, 1);
+  return true;
+}
+// its share of SmartFactorBase::totalReprojectionError<Unit3> (SmartFactorBase.h:296-303): 0.5 |whitened (h - z)|^2
+GT_HD bool proj_error_at_infinity(const double* pose, const double* K, const double* sensor, const double* dir,
+                                  const double* z, const NoiseRef& n, double* e) {
+  double pi[2];
+  bool ok;
+  *e = 0.0;
+  if (sensor) {
+    double T[12];
+    pose_compose(pose, sensor, T);
+    ok = s2_project_at_infinity(T, K, dir, pi, nullptr, nullptr);
+  } else {
+    ok = s2_project_at_infinity(pose, K, dir, pi, nullptr, nullptr);
+  }
+  if (!ok) return false;
+  double r[2] = {pi[0] - z[0], pi[1] - z[1]};
+  whiten_cols<2>(n.kind, n.data, r, 1);
+  *e = 0.5 * (r[0] * r[0] + r[1] * r[1]);
+  return true;
+}
+
 // ---- GenericStereoFactor<Pose3,Point3> ---------------------------------------------------------
 // Three residual rows (uL, uR, v) where the monocular factor has two; K = the calib table entry (skew unused), bl = its baseline.
 GT_HD void stereo_linearize(const double* pose, const double* K, double bl, const double* sensor, const double* pt,

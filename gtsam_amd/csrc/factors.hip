@@ -104,6 +104,43 @@ __global__ __launch_bounds__(kBlock) void k_lin_proj(int64_t n, const int32_t* _
   }
 }
 
+// The same kernel for a projection range that holds the measurements of pose-type smart factors (SmartProjectionPoseFactor<Cal3_S2>,
+// smart_of[i] >= 0): one whose track is not VALID at the linearisation point contributes nothing -- its record is zeroed
+// (k_lin_smart_pose_at_infinity then writes the records of the tracks that became points at infinity).  A kernel of its own, so that
+// k_lin_proj above stays the code every other graph ran before, instruction for instruction (one force-inlined body behind both kernels
+// had the same register counts and another rounding of the records: the step of projection_small was no longer bit-equal to its recording).
+__global__ __launch_bounds__(kBlock) void k_lin_proj_smart(int64_t n, const int32_t* __restrict__ pose,
+    const int32_t* __restrict__ pt, const double* __restrict__ z, const int32_t* __restrict__ nz,
+    const int32_t* __restrict__ calib_idx, const int32_t* __restrict__ sensor_idx,
+    const double* __restrict__ calib, const double* __restrict__ sensor,
+    const double* __restrict__ values, const int64_t* __restrict__ val_off, NoiseTab nt,
+    double* __restrict__ J, const int32_t* __restrict__ smart_of, const int32_t* __restrict__ smart_status) {
+  typedef RecIO<kProjRec> IO;
+  __shared__ double img[kBlock / 64][IO::LDS_DOUBLES];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double* my = img[wave];
+  const int64_t nchunks = (n + 63) / 64, stride = (int64_t)gridDim.x * (kBlock / 64);
+  for (int64_t ch = blockIdx.x * (int64_t)(kBlock / 64) + wave; ch < nchunks; ch += stride) {
+    const int64_t i = ch * 64 + lane;
+    if (i < n) {
+      double T[12], p[3], zz[2], K[kCalibStride], S[12];
+      const double* tp = values + val_off[pose[i]];
+      const double* pp = values + val_off[pt[i]];
+      for (int k = 0; k < 12; k++) T[k] = tp[k];
+      for (int k = 0; k < 3; k++) p[k] = pp[k];
+      for (int k = 0; k < kCalibStride; k++) K[k] = calib[kCalibStride * calib_idx[i] + k];
+      const int si = sensor_idx[i];
+      if (si >= 0) for (int k = 0; k < 12; k++) S[k] = sensor[12 * si + k];
+      zz[0] = z[2 * i]; zz[1] = z[2 * i + 1];
+      proj_linearize(T, K, si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]), my + lane * IO::PITCH);   // in place in the LDS image (see k_lin_sfm)
+      if (smart_of[i] >= 0 && smart_status[smart_of[i]] != kTriValid)
+        for (int k = 0; k < kProjRec; k++) my[lane * IO::PITCH + k] = 0.0;
+    }
+    const int64_t left = n - ch * 64;
+    IO::store(my, J + (int64_t)kProjRec * ch * 64, left < 64 ? (int)left : 64, lane);
+  }
+}
+
 // The projection range of a graph WITH stereo factors: observations [0, n_mono) are monocular, [n_mono, n) GenericStereoFactors; every
 // record has three rows (kStereoRec, the monocular ones a zero third row) and every measurement three entries.  Records in place in the
 // LDS image as above.
@@ -179,11 +216,11 @@ struct ErrArgs {
   const int32_t *bt_v1, *bt_v2, *bt_nz; const double* bt_z;
   const int32_t *pr_var, *pr_nz; const int64_t* pr_off; const double* pr_data;
   const int32_t* var_type; const int64_t* val_off;
-  const int32_t *smart_of, *smart_status;   // smart factors: the factor of an sfm observation (or -1) and its triangulation status
+  const int32_t *smart_of, *smart_status;   // smart factors: the factor of an observation of their range (or -1) and its triangulation status
 };
 
 // Block b handles a fixed slice, so the summation order is fixed.  TYPES: bit 0 -- the GeneralSFM factors, bit 1 -- the other three
-// types.  (One kernel for all four types -- rounds 1-4 -- needed 256 registers + scratch for the union of their evaluators: one
+// types, bit 2 (with bit 1) -- the projection range holds the measurements of pose-type smart factors, a.smart_of is its map.  (One kernel for all four types -- rounds 1-4 -- needed 256 registers + scratch for the union of their evaluators: one
 // wavefront per SIMD, 32 us for the 0.68 M factors of the L1723 shape, a gather-and-evaluate kernel that lives on occupancy.)
 template <int TYPES>
 __global__ __launch_bounds__(kBlock) void k_error(ErrArgs a, const double* __restrict__ values, NoiseTab nt,
@@ -214,6 +251,9 @@ __global__ __launch_bounds__(kBlock) void k_error(ErrArgs a, const double* __res
     if (si >= 0) for (int k = 0; k < 12; k++) S[k] = a.sensor[12 * si + k];
     zz[0] = a.proj_z[2 * i]; zz[1] = a.proj_z[2 * i + 1];
     const int ni = a.proj_nz[i];
+    if constexpr ((TYPES & 4) != 0) {   // (a smart factor whose landmark did not triangulate has error 0, SmartProjectionFactor.h:407-427)
+      if (a.smart_of[i] >= 0 && a.smart_status[a.smart_of[i]] != kTriValid) continue;
+    }
     acc += proj_error(T, K, si >= 0 ? S : nullptr, p, zz, nt.ref(ni));
   }
   for (int64_t i = tid; i < a.n_between; i += stride) {
@@ -402,9 +442,18 @@ __device__ __forceinline__ void raise_unsupported(double* scalars, double code) 
 }
 struct SmartArgs {
   int64_t n, obs0;
-  const int64_t* ptr; const int32_t *sfm_cam, *sfm_point; const double* sfm_z; const int64_t* val_off; const double* params;
+  // the observation range the measurements live in: GeneralSFM (cam = SFM_CAMERA ids) or, POSE, projection (cam = POSE3 ids with the
+  // range's calibration / sensor tables)
+  const int64_t* ptr; const int32_t *cam, *point; const double* z; const int64_t* val_off; const double* params;
   int32_t *status, *cache_state; double *cache_pose, *cache_point;
+  const int32_t *calib_idx, *sensor_idx; const double *calib, *sensor;
 };
+template <bool POSE>
+__device__ __forceinline__ auto smart_cams(const SmartArgs& a, const double* values, int64_t o0) {
+  if constexpr (POSE) return PoseCams{a.cam + o0, a.calib_idx + o0, a.sensor_idx + o0, a.calib, a.sensor, a.val_off, values};
+  else return BundlerCams{a.cam + o0, a.val_off, values};
+}
+template <bool POSE>
 __global__ __launch_bounds__(kBlock) void k_smart_triangulate(SmartArgs a, double* __restrict__ values, const double* __restrict__ gate,
                                                               double* __restrict__ scalars, int for_linearize) {
   // (a try whose factorisation timed out is repeated, api.hip: its garbage trial point must not touch the triangulation cache)
@@ -415,6 +464,7 @@ __global__ __launch_bounds__(kBlock) void k_smart_triangulate(SmartArgs a, doubl
     if (m == 0) continue;                                // a factor of another shard (every factor has a measurement: gtg_upload_problem)
     const double* prm = a.params + 8 * sf;
     const double thr = prm[3];
+    const auto cs = smart_cams<POSE>(a, values, o0);     // "the camera's pose" = the composed world_P_sensor for a pose-type factor
     int st;
     double pt[3] = {0.0, 0.0, 0.0};
     if (m < 2) {
@@ -422,16 +472,19 @@ __global__ __launch_bounds__(kBlock) void k_smart_triangulate(SmartArgs a, doubl
     } else {
       bool again = a.cache_state[sf] < 0;
       for (int k = 0; k < m && !again; k++) {
-        const double* pose = values + a.val_off[a.sfm_cam[o0 + k]];
+        double pose[12];
+        cs.pose(k, pose);
         const double* old = a.cache_pose + 12 * (k0 + k);
         for (int e = 0; e < 12; e++) again = again || fabs(pose[e] - old[e]) > thr;
       }
       if (again) {
         for (int k = 0; k < m; k++) {
-          const double* pose = values + a.val_off[a.sfm_cam[o0 + k]];
+          double pose[12];
+          cs.pose(k, pose);
           for (int e = 0; e < 12; e++) a.cache_pose[12 * (k0 + k) + e] = pose[e];
         }
-        st = smart_triangulate(m, a.sfm_cam + o0, a.val_off, values, a.sfm_z + 2 * o0, prm[0], prm[1], prm[2], pt, prm[6] != 0.0);
+        if constexpr (POSE) st = smart_triangulate(m, cs, a.z + 2 * o0, prm[0], prm[1], prm[2], pt);   // (enableEPI is refused at upload)
+        else st = smart_triangulate(m, a.cam + o0, a.val_off, values, a.z + 2 * o0, prm[0], prm[1], prm[2], pt, prm[6] != 0.0);
         a.cache_state[sf] = st;
         for (int e = 0; e < 3; e++) a.cache_point[3 * sf + e] = pt[e];
       } else {
@@ -447,9 +500,17 @@ __global__ __launch_bounds__(kBlock) void k_smart_triangulate(SmartArgs a, doubl
     // The direction is taken from the cameras of THIS call (it is not part of the cached triangulation).
     const int mode = (int)prm[4], lin_mode = (int)prm[5];
     bool at_infinity = st != kTriValid && st != kTriNoConvergence && st != kTriCheiralityThrown && (for_linearize ? (mode != 1 && lin_mode == 0) : mode == 2);
-    if (at_infinity && !sfm_backproject_at_infinity(values + a.val_off[a.sfm_cam[o0]], a.sfm_z + 2 * o0, pt)) { st = kTriNoConvergence; at_infinity = false; }
+    if constexpr (POSE) {
+      if (at_infinity) {
+        double T[12], K[5];
+        cs.pose(0, T); cs.pinhole(0, K);
+        s2_backproject_at_infinity(T, K, a.z + 2 * o0, pt);
+      }
+    } else {
+      if (at_infinity && !sfm_backproject_at_infinity(values + a.val_off[a.cam[o0]], a.z + 2 * o0, pt)) { st = kTriNoConvergence; at_infinity = false; }
+    }
     a.status[sf] = st | (at_infinity ? kTriAtInfinity : 0);
-    double* slot = values + a.val_off[a.sfm_point[o0]];
+    double* slot = values + a.val_off[a.point[o0]];
     for (int e = 0; e < 3; e++) slot[e] = (st == kTriValid || at_infinity) ? pt[e] : 0.0;
     if (st == kTriNoConvergence) raise_unsupported(scalars, 1.0);      // Cal3Bundler::calibrate throws in the reference
     if (st == kTriCheiralityThrown) raise_unsupported(scalars, kUnsupportedCheirality);   // enableEPI: geom.h::triangulate_refine
@@ -500,12 +561,73 @@ __global__ __launch_bounds__(kBlock) void k_error_smart_at_infinity(int64_t n_me
   if (threadIdx.x == 0) scalars[slot] += s;
 }
 
+// The same two kernels for pose-type smart factors (SmartProjectionPoseFactor<Cal3_S2>): their measurements are projection
+// observations (k_lin_proj_smart has zeroed the records of the failed tracks).  The record is built in place in LDS, one slot per
+// lane (pitch 21 doubles: odd, so the lanes' slots start in different banks), not in a local array (see k_lin_sfm).
+struct SmartProjTabs {
+  const int32_t *pose, *pt, *nz, *calib_idx, *sensor_idx; const double *z, *calib, *sensor; const int64_t* val_off;
+  const int32_t *smart_of, *status;
+};
+__device__ __forceinline__ void load_smart_proj(const SmartProjTabs& t, const double* values, int64_t o, double* T, double* d, double* zz, double* K, double* S) {
+  const double* tp = values + t.val_off[t.pose[o]];
+  const double* dp = values + t.val_off[t.pt[o]];
+  for (int e = 0; e < 12; e++) T[e] = tp[e];
+  for (int e = 0; e < 3; e++) d[e] = dp[e];
+  for (int e = 0; e < kCalibStride; e++) K[e] = t.calib[kCalibStride * t.calib_idx[o] + e];
+  const int si = t.sensor_idx[o];
+  if (si >= 0) for (int e = 0; e < 12; e++) S[e] = t.sensor[12 * si + e];
+  zz[0] = t.z[2 * o]; zz[1] = t.z[2 * o + 1];
+}
+__global__ __launch_bounds__(kBlock) void k_lin_smart_pose_at_infinity(int64_t n_meas, int64_t obs0, SmartProjTabs t, const double* __restrict__ values,
+    NoiseTab nt, double* __restrict__ J, double* __restrict__ scalars) {
+  constexpr int kPitch = kProjRec + 1;
+  __shared__ double img[kBlock * kPitch];
+  double* rec = img + threadIdx.x * kPitch;
+  for (int64_t k = blockIdx.x * (int64_t)kBlock + threadIdx.x; k < n_meas; k += (int64_t)gridDim.x * kBlock) {
+    const int64_t o = obs0 + k;
+    if (!(t.status[t.smart_of[o]] & kTriAtInfinity)) continue;
+    double T[12], d[3], zz[2], K[kCalibStride], S[12];
+    load_smart_proj(t, values, o, T, d, zz, K, S);
+    if (!proj_linearize_at_infinity(T, K, t.sensor_idx[o] >= 0 ? S : nullptr, d, zz, nt.ref(t.nz[o]), rec)) raise_unsupported(scalars, kUnsupportedCheirality);
+    for (int e = 0; e < kProjRec; e++) J[(int64_t)kProjRec * o + e] = rec[e];
+  }
+}
+__global__ __launch_bounds__(kBlock) void k_error_smart_pose_at_infinity(int64_t n_meas, int64_t obs0, SmartProjTabs t, const double* __restrict__ values,
+    NoiseTab nt, const double* __restrict__ gate, double* __restrict__ scalars, int slot) {
+  if (gate && (gate[SC_TIMEOUT] != 0.0 || !(gate[SC_LIN0] - gate[SC_LIN1] >= 0))) return;      // (the triangulation of this trial point was skipped: see k_smart_triangulate)
+  double acc = 0.0;
+  for (int64_t k = threadIdx.x; k < n_meas; k += kBlock) {
+    const int64_t o = obs0 + k;
+    if (!(t.status[t.smart_of[o]] & kTriAtInfinity)) continue;
+    double T[12], d[3], zz[2], K[kCalibStride], S[12], e;
+    load_smart_proj(t, values, o, T, d, zz, K, S);
+    if (!proj_error_at_infinity(T, K, t.sensor_idx[o] >= 0 ? S : nullptr, d, zz, nt.ref(t.nz[o]), &e)) raise_unsupported(scalars, kUnsupportedCheirality);
+    acc += e;
+  }
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) scalars[slot] += s;
+}
+static SmartProjTabs smart_proj_tabs(gtg_context& c, const int32_t* status) {
+  auto& f = c.f;
+  return SmartProjTabs{f.proj_pose.p, f.proj_point.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.proj_z.p, f.calib.p, f.sensor.p, c.val_off.p,
+                       c.obs_smart.p, status};
+}
+
 void launch_smart_triangulate(gtg_context& c, double* values, const double* gate, bool for_linearize) {
   if (!c.n_smart) return;
-  SmartArgs a{c.n_smart, c.smart_obs0, c.smart_ptr.p, c.f.sfm_cam.p, c.f.sfm_point.p, c.f.sfm_z.p, c.val_off.p, c.smart_params.p,
-              for_linearize ? c.smart_lin_status.p : c.smart_status.p, c.smart_cache_state.p, c.smart_cache_pose.p, c.smart_cache_point.p};
-  hipLaunchKernelGGL(k_smart_triangulate, dim3(grid_for(c.n_smart)), dim3(kBlock), 0, c.stream, a, values, gate, c.scalars.p,
-                     for_linearize ? 1 : 0);
+  auto& f = c.f;
+  int32_t* status = for_linearize ? c.smart_lin_status.p : c.smart_status.p;
+  if (c.smart_pose) {
+    SmartArgs a{c.n_smart, c.smart_obs0, c.smart_ptr.p, f.proj_pose.p, f.proj_point.p, f.proj_z.p, c.val_off.p, c.smart_params.p,
+                status, c.smart_cache_state.p, c.smart_cache_pose.p, c.smart_cache_point.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.sensor.p};
+    hipLaunchKernelGGL(k_smart_triangulate<true>, dim3(grid_for(c.n_smart)), dim3(kBlock), 0, c.stream, a, values, gate, c.scalars.p,
+                       for_linearize ? 1 : 0);
+  } else {
+    SmartArgs a{c.n_smart, c.smart_obs0, c.smart_ptr.p, f.sfm_cam.p, f.sfm_point.p, f.sfm_z.p, c.val_off.p, c.smart_params.p,
+                status, c.smart_cache_state.p, c.smart_cache_pose.p, c.smart_cache_point.p, nullptr, nullptr, nullptr, nullptr};
+    hipLaunchKernelGGL(k_smart_triangulate<false>, dim3(grid_for(c.n_smart)), dim3(kBlock), 0, c.stream, a, values, gate, c.scalars.p,
+                       for_linearize ? 1 : 0);
+  }
   check_hip(hipGetLastError(), "smart_triangulate");
 }
 
@@ -515,16 +637,23 @@ void launch_linearize(gtg_context& c) {
   if (f.n_sfm && !c.fused_sfm)     // (fused: nobody reads stored records of these factors, fused.h)
     hipLaunchKernelGGL(k_lin_sfm, dim3(grid_for(f.n_sfm)), dim3(kBlock), 0, c.stream, f.n_sfm, f.sfm_cam.p,
                        f.sfm_point.p, f.sfm_z.p, f.sfm_noise.p, c.values.p, c.val_off.p, nt, f.sfm_J.p,
-                       c.n_smart ? c.sfm_smart.p : nullptr, c.smart_lin_status.p);
-  if (c.n_smart)
+                       c.n_smart && !c.smart_pose ? c.obs_smart.p : nullptr, c.smart_lin_status.p);
+  if (c.n_smart && !c.smart_pose)
     hipLaunchKernelGGL(k_lin_smart_at_infinity, dim3(grid_for(f.n_sfm - c.smart_obs0)), dim3(kBlock), 0, c.stream, f.n_sfm - c.smart_obs0, c.smart_obs0,
-                       f.sfm_cam.p, f.sfm_point.p, f.sfm_z.p, f.sfm_noise.p, c.values.p, c.val_off.p, nt, f.sfm_J.p, c.sfm_smart.p,
+                       f.sfm_cam.p, f.sfm_point.p, f.sfm_z.p, f.sfm_noise.p, c.values.p, c.val_off.p, nt, f.sfm_J.p, c.obs_smart.p,
                        c.smart_lin_status.p, c.scalars.p);
   if (f.n_proj && f.stereo)
     hipLaunchKernelGGL(k_lin_stereo, dim3(grid_for(f.n_proj)), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.proj_pose.p,
                        f.proj_point.p, f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_baseline.p,
                        f.sensor.p, c.values.p, c.val_off.p, nt, f.proj_J.p);
-  else if (f.n_proj)
+  else if (f.n_proj && c.smart_pose) {   // (the smart measurements of this shard may be none: the smart form all the same)
+    hipLaunchKernelGGL(k_lin_proj_smart, dim3(grid_for(f.n_proj)), dim3(kBlock), 0, c.stream, f.n_proj, f.proj_pose.p,
+                       f.proj_point.p, f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p,
+                       f.sensor.p, c.values.p, c.val_off.p, nt, f.proj_J.p, c.obs_smart.p, c.smart_lin_status.p);
+    if (f.n_proj > c.smart_obs0)
+      hipLaunchKernelGGL(k_lin_smart_pose_at_infinity, dim3(grid_for(f.n_proj - c.smart_obs0)), dim3(kBlock), 0, c.stream, f.n_proj - c.smart_obs0,
+                         c.smart_obs0, smart_proj_tabs(c, c.smart_lin_status.p), c.values.p, nt, f.proj_J.p, c.scalars.p);
+  } else if (f.n_proj)
     hipLaunchKernelGGL(k_lin_proj, dim3(grid_for(f.n_proj)), dim3(kBlock), 0, c.stream, f.n_proj, f.proj_pose.p,
                        f.proj_point.p, f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p,
                        f.sensor.p, c.values.p, c.val_off.p, nt, f.proj_J.p);
@@ -573,21 +702,27 @@ void launch_error(gtg_context& c, const double* values, int slot, const double* 
             f.proj_pose.p, f.proj_point.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.proj_z.p, f.calib.p, f.sensor.p,
             f.between_v1.p, f.between_v2.p, f.between_noise.p, f.between_z.p,
             f.prior_var.p, f.prior_noise.p, f.prior_off.p, f.prior_data.p,
-            c.var_type.p, c.val_off.p, c.n_smart ? c.sfm_smart.p : nullptr, c.smart_status.p};
+            c.var_type.p, c.val_off.p, c.n_smart ? c.obs_smart.p : nullptr, c.smart_status.p};   // (smart_of: the map of the range the smart measurements live in)
+  ErrArgs a_sfm = a;
+  if (c.smart_pose) a_sfm.smart_of = nullptr;
   // the GeneralSFM factors and the other types in a kernel each, their block partials one behind the other
   const int64_t nrest = std::max(a.n_proj, std::max(f.n_between, f.n_prior));
   const int gmax = f.stereo ? kMaxBlocks / 4 : kMaxBlocks / 2;
   const int g1 = f.n_sfm ? std::min(grid_for(f.n_sfm), gmax) : 0, g2 = (nrest || !g1) ? std::min(grid_for(nrest), gmax) : 0;
   const int g3 = f.stereo && f.n_proj ? std::min(grid_for(f.n_proj), gmax) : 0;
-  if (g1) hipLaunchKernelGGL(k_error<1>, dim3(g1), dim3(kBlock), 0, c.stream, a, values, noise_tab(c), c.partials.p);
-  if (g2) hipLaunchKernelGGL(k_error<2>, dim3(g2), dim3(kBlock), 0, c.stream, a, values, noise_tab(c), c.partials.p + g1);
+  if (g1) hipLaunchKernelGGL(k_error<1>, dim3(g1), dim3(kBlock), 0, c.stream, a_sfm, values, noise_tab(c), c.partials.p);
+  if (g2 && c.smart_pose) hipLaunchKernelGGL(k_error<6>, dim3(g2), dim3(kBlock), 0, c.stream, a, values, noise_tab(c), c.partials.p + g1);
+  else if (g2) hipLaunchKernelGGL(k_error<2>, dim3(g2), dim3(kBlock), 0, c.stream, a, values, noise_tab(c), c.partials.p + g1);
   if (g3) hipLaunchKernelGGL(k_error_stereo, dim3(g3), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.proj_pose.p, f.proj_point.p, f.proj_z.p,
                              f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_baseline.p, f.sensor.p, values, c.val_off.p,
                              noise_tab(c), c.partials.p + g1 + g2);
   hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(kBlock), 0, c.stream, c.partials.p, g1 + g2 + g3, 1, c.scalars.p, slot);
-  if (c.n_smart)
+  if (c.n_smart && c.smart_pose)
+    hipLaunchKernelGGL(k_error_smart_pose_at_infinity, dim3(1), dim3(kBlock), 0, c.stream, f.n_proj - c.smart_obs0, c.smart_obs0,
+                       smart_proj_tabs(c, c.smart_status.p), values, noise_tab(c), gate, c.scalars.p, slot);
+  else if (c.n_smart)
     hipLaunchKernelGGL(k_error_smart_at_infinity, dim3(1), dim3(kBlock), 0, c.stream, f.n_sfm - c.smart_obs0, c.smart_obs0, f.sfm_cam.p, f.sfm_point.p,
-                       f.sfm_z.p, f.sfm_noise.p, values, c.val_off.p, noise_tab(c), c.sfm_smart.p, c.smart_status.p,
+                       f.sfm_z.p, f.sfm_noise.p, values, c.val_off.p, noise_tab(c), c.obs_smart.p, c.smart_status.p,
                        gate, c.scalars.p, slot);
   check_hip(hipGetLastError(), "error");
 }
@@ -623,8 +758,10 @@ namespace {
 void prewarm_factors(int) {
   gt::prewarm_kernels({(const void*)gt::k_lin_sfm, (const void*)gt::k_lin_proj, (const void*)gt::k_lin_between, (const void*)gt::k_lin_prior,
                        (const void*)gt::k_error<1>, (const void*)gt::k_error<2>, (const void*)gt::k_final_sum, (const void*)gt::k_linear_error<true, 2>,
-                       (const void*)gt::k_linear_error<false, 2>, (const void*)gt::k_linear_error<false, 3>, (const void*)gt::k_lin_stereo, (const void*)gt::k_error_stereo, (const void*)gt::k_retract, (const void*)gt::k_sumsq, (const void*)gt::k_smart_triangulate,
-                       (const void*)gt::k_lin_smart_at_infinity, (const void*)gt::k_error_smart_at_infinity, (const void*)gt::k_sfm_value_offsets});
+                       (const void*)gt::k_linear_error<false, 2>, (const void*)gt::k_linear_error<false, 3>, (const void*)gt::k_lin_stereo, (const void*)gt::k_error_stereo, (const void*)gt::k_retract, (const void*)gt::k_sumsq, (const void*)gt::k_smart_triangulate<false>,
+                       (const void*)gt::k_lin_smart_at_infinity, (const void*)gt::k_error_smart_at_infinity, (const void*)gt::k_sfm_value_offsets,
+                       (const void*)gt::k_smart_triangulate<true>, (const void*)gt::k_lin_proj_smart, (const void*)gt::k_error<6>,
+                       (const void*)gt::k_lin_smart_pose_at_infinity, (const void*)gt::k_error_smart_pose_at_infinity});
 }
 gt::PrewarmUnit prewarm_factors_registered(prewarm_factors);
 }  // namespace

@@ -494,20 +494,44 @@ GT_HD bool triangulate_refine(int m, const int32_t* cams, const int64_t* val_off
 //   of the smallest singular value, rank = singular values above rank_tol -- here from the eigen-decomposition of A^T A),
 //   rank < 3 -> DEGENERATE, a camera with the point not in front -> BEHIND_CAMERA (:536-541), then per camera the distance
 //   threshold (FAR_POINT) and the largest reprojection error against the outlier threshold (OUTLIER).
-// cams[k] -> values + val_off[cams[k]] = pose (R row-major, t), f, k1, k2, u0, v0; z = 2 per measurement.
-GT_HD int smart_triangulate(int m, const int32_t* cams, const int64_t* val_off, const double* values, const double* z,
-                            double rank_tol, double dist_thr, double outlier_thr, double* point, bool enable_epi = false) {
+// One code for both smart factors: the camera model comes in through an accessor.  z = 2 per measurement.
+// The cameras of one track as the triangulation sees them -- pose, pinhole K, "undistort this pixel", "project":
+//   BundlerCams  PinholeCamera<Cal3Bundler> variables (17 doubles: pose, f, k1, k2, u0, v0), SmartProjectionFactor<PinholeCamera<Cal3Bundler>>;
+//   PoseCams     (behind s2_project) PinholePose<Cal3_S2>(pose * body_P_sensor, K), SmartProjectionPoseFactor<Cal3_S2>.
+struct BundlerCams {
+  const int32_t* cams; const int64_t* val_off; const double* values;
+  static constexpr bool kSkew = false;                            // K = [f 0 u0; 0 f v0; 0 0 1]
+  GT_HD const double* cam(int k) const { return values + val_off[cams[k]]; }
+  GT_HD void pose(int k, double* T) const { const double* c = cam(k); for (int i = 0; i < 12; i++) T[i] = c[i]; }
+  GT_HD void pinhole(int k, double* K) const { const double* c = cam(k); K[0] = c[12]; K[1] = c[12]; K[2] = 0.0; K[3] = c[15]; K[4] = c[16]; }
+  // calibrate with the camera's Cal3Bundler, uncalibrate with Cal3_S2(f, f, 0, u0, v0); false: calibrate did not converge
+  GT_HD bool undistort(int k, const double* z, double* zu) const {
+    const double* c = cam(k);
+    const double f = c[12], u0 = c[15], v0 = c[16];
+    double pn[2];
+    if (!bundler_calibrate(f, c[13], c[14], u0, v0, z, pn)) return false;
+    zu[0] = f * pn[0] + u0; zu[1] = f * pn[1] + v0;
+    return true;
+  }
+  GT_HD bool project(int k, const double* pw, double* pi) const {
+    const double* c = cam(k);
+    double cc[17];
+    for (int j = 0; j < 17; j++) cc[j] = c[j];
+    return sfm_project(cc, pw, pi, nullptr, nullptr);
+  }
+};
+
+template <class Cams>
+GT_HD int triangulate_dlt(int m, const Cams& cs, const double* z, double rank_tol, double* point) {
   point[0] = point[1] = point[2] = 0.0;
   if (m < 2) return kTriDegenerate;
   double M[4][4], V[4][4];
   _Pragma("unroll") for (int i = 0; i < 4; i++) _Pragma("unroll") for (int j = 0; j < 4; j++) M[i][j] = 0.0;
   for (int k = 0; k < m; k++) {
-    const double* c = values + val_off[cams[k]];
-    const double f = c[12], k1 = c[13], k2 = c[14], u0 = c[15], v0 = c[16];
-    double pn[2];
-    if (!bundler_calibrate(f, k1, k2, u0, v0, z + 2 * k, pn)) return kTriNoConvergence;
-    const double zu[2] = {f * pn[0] + u0, f * pn[1] + v0};        // Cal3_S2(f, f, 0, u0, v0).uncalibrate
-    // [R | t]^-1 = [R^T | -R^T t]; P = K [R^T | -R^T t], K = [f 0 u0; 0 f v0; 0 0 1]
+    double c[12], K[5], zu[2];
+    cs.pose(k, c); cs.pinhole(k, K);
+    if (!cs.undistort(k, z + 2 * k, zu)) return kTriNoConvergence;
+    // [R | t]^-1 = [R^T | -R^T t]; P = K [R^T | -R^T t], K = [fx s u0; 0 fy v0; 0 0 1]
     double W[3][4];
     _Pragma("unroll") for (int i = 0; i < 3; i++) {
       W[i][0] = c[0 + i]; W[i][1] = c[3 + i]; W[i][2] = c[6 + i];   // R^T(i, j) = R(j, i)
@@ -515,7 +539,8 @@ GT_HD int smart_triangulate(int m, const int32_t* cams, const int64_t* val_off, 
     }
     double r0[4], r1[4];
     _Pragma("unroll") for (int j = 0; j < 4; j++) {
-      const double P0 = f * W[0][j] + u0 * W[2][j], P1 = f * W[1][j] + v0 * W[2][j], P2 = W[2][j];
+      const double P0 = Cams::kSkew ? K[0] * W[0][j] + K[2] * W[1][j] + K[3] * W[2][j] : K[0] * W[0][j] + K[3] * W[2][j];
+      const double P1 = K[1] * W[1][j] + K[4] * W[2][j], P2 = W[2][j];
       r0[j] = zu[0] * P2 - P0; r1[j] = zu[1] * P2 - P1;
     }
     _Pragma("unroll") for (int i = 0; i < 4; i++) _Pragma("unroll") for (int j = 0; j < 4; j++) M[i][j] += r0[i] * r0[j] + r1[i] * r1[j];
@@ -531,9 +556,14 @@ GT_HD int smart_triangulate(int m, const int32_t* cams, const int64_t* val_off, 
   double v[4] = {0, 0, 0, 0};
   _Pragma("unroll") for (int j = 0; j < 4; j++) if (j == smallest) { v[0] = V[0][j]; v[1] = V[1][j]; v[2] = V[2][j]; v[3] = V[3][j]; }
   point[0] = v[0] / v[3]; point[1] = v[1] / v[3]; point[2] = v[2] / v[3];
-  if (enable_epi && !triangulate_refine(m, cams, val_off, values, z, point)) return kTriCheiralityThrown;   // (triangulation.h:531-534)
+  return kTriValid;
+}
+// ... and the checks behind the linear triangulation (and behind the enableEPI refinement, where there is one)
+template <class Cams>
+GT_HD int smart_triangulate_checks(int m, const Cams& cs, const double* z, double dist_thr, double outlier_thr, const double* point) {
   for (int k = 0; k < m; k++) {       // triangulatePoint3's cheirality check: every camera first
-    const double* c = values + val_off[cams[k]];
+    double c[12];
+    cs.pose(k, c);
     const double dx[3] = {point[0] - c[9], point[1] - c[10], point[2] - c[11]};
     double q[3];
     mat3_tvec(c, dx, q);
@@ -541,15 +571,15 @@ GT_HD int smart_triangulate(int m, const int32_t* cams, const int64_t* val_off, 
   }
   double max_err = 0.0;
   for (int k = 0; k < m; k++) {
-    const double* c = values + val_off[cams[k]];
     if (dist_thr > 0) {
+      double c[12];
+      cs.pose(k, c);
       const double dx = point[0] - c[9], dy = point[1] - c[10], dz = point[2] - c[11];
       if (sqrt(dx * dx + dy * dy + dz * dz) > dist_thr) return kTriFarPoint;
     }
     if (outlier_thr > 0) {
-      double cam[17], pi[2];
-      for (int j = 0; j < 17; j++) cam[j] = c[j];
-      if (sfm_project(cam, point, pi, nullptr, nullptr)) {
+      double pi[2];
+      if (cs.project(k, point, pi)) {
         const double eu = pi[0] - z[2 * k], ev = pi[1] - z[2 * k + 1], e = sqrt(eu * eu + ev * ev);
         max_err = e > max_err ? e : max_err;
       }
@@ -557,6 +587,20 @@ GT_HD int smart_triangulate(int m, const int32_t* cams, const int64_t* val_off, 
   }
   if (outlier_thr > 0 && max_err > outlier_thr) return kTriOutlier;
   return kTriValid;
+}
+template <class Cams>
+GT_HD int smart_triangulate(int m, const Cams& cs, const double* z, double rank_tol, double dist_thr, double outlier_thr, double* point) {
+  const int st = triangulate_dlt(m, cs, z, rank_tol, point);
+  return st != kTriValid ? st : smart_triangulate_checks(m, cs, z, dist_thr, outlier_thr, point);
+}
+// PinholeCamera<Cal3Bundler> cameras: cams[k] -> values + val_off[cams[k]]; enable_epi: the DLT point refined (triangulate_refine)
+GT_HD int smart_triangulate(int m, const int32_t* cams, const int64_t* val_off, const double* values, const double* z,
+                            double rank_tol, double dist_thr, double outlier_thr, double* point, bool enable_epi = false) {
+  const BundlerCams cs{cams, val_off, values};
+  const int st = triangulate_dlt(m, cs, z, rank_tol, point);
+  if (st != kTriValid) return st;
+  if (enable_epi && !triangulate_refine(m, cams, val_off, values, z, point)) return kTriCheiralityThrown;   // (triangulation.h:531-534)
+  return smart_triangulate_checks(m, cs, z, dist_thr, outlier_thr, point);
 }
 
 // PinholeCamera<Cal3_S2>(pose, K).project (PinholePose.h:89-109) + Cal3_S2::uncalibrate (geometry/Cal3_S2.cpp:44-50), or, when the
@@ -604,6 +648,99 @@ GT_HD bool s2_project(const double* T, const double* K, const double* pw, double
       Dpoint[j] = d00 * Dpt[j] + d01 * Dpt[3 + j];
       Dpoint[3 + j] = d10 * Dpt[j] + d11 * Dpt[3 + j];
     }
+  return true;
+}
+
+// ---- SmartProjectionPoseFactor<Cal3_S2>: cameras PinholePose<Cal3_S2>(pose * body_P_sensor, K) (slam/SmartProjectionPoseFactor.h:138-147) ----
+// Cal3_S2::calibrate (geometry/Cal3_S2.cpp:53-69) and ::uncalibrate (:44-50); K = fx, fy, s, u0, v0
+GT_HD void s2_calibrate(const double* K, const double* pi, double* pn) {
+  const double delta_u = pi[0] - K[3], delta_v = pi[1] - K[4];
+  const double inv_fx = 1 / K[0], inv_fy = 1 / K[1];
+  const double inv_fy_delta_v = inv_fy * delta_v;
+  pn[0] = inv_fx * (delta_u - K[2] * inv_fy_delta_v); pn[1] = inv_fy_delta_v;
+}
+GT_HD void s2_uncalibrate(const double* K, const double* pn, double* pi) {
+  pi[0] = K[0] * pn[0] + K[2] * pn[1] + K[3];
+  pi[1] = K[1] * pn[1] + K[4];
+}
+// The cameras of one pose-type track: measurement k looks through pose variable pose_var[k], calibration calib_idx[k], sensor
+// sensor_idx[k] (or -1).  "The camera's pose" is the composed world_P_sensor everywhere (cache, DLT, cheirality, distance).
+// CameraSet<PinholePose<Cal3_S2>> does not hit the "do nothing" specialisations of undistortMeasurements (triangulation.h:297-302,
+// :332-338 are for PinholeCamera<Cal3_S2>): every pixel goes through calibrate and uncalibrate of the same K (:315-330 -> :260-268),
+// which is not the identity in floating point.  There is no "did not converge" for a Cal3_S2.
+struct PoseCams {
+  const int32_t *pose_var, *calib_idx, *sensor_idx; const double *calib, *sensor; const int64_t* val_off; const double* values;
+  static constexpr bool kSkew = true;
+  GT_HD void pose(int k, double* T) const {
+    const double* p = values + val_off[pose_var[k]];
+    const int si = sensor_idx[k];
+    if (si >= 0) pose_compose(p, sensor + 12 * si, T);
+    else for (int i = 0; i < 12; i++) T[i] = p[i];
+  }
+  GT_HD void pinhole(int k, double* K) const { const double* c = calib + kCalibStride * calib_idx[k]; for (int i = 0; i < 5; i++) K[i] = c[i]; }
+  GT_HD bool undistort(int k, const double* z, double* zu) const {
+    double K[5], pn[2];
+    pinhole(k, K);
+    s2_calibrate(K, z, pn);
+    s2_uncalibrate(K, pn, zu);
+    return true;
+  }
+  GT_HD bool project(int k, const double* pw, double* pi) const {
+    double T[12], K[kCalibStride];
+    pose(k, T);
+    const double* c = calib + kCalibStride * calib_idx[k];
+    for (int i = 0; i < kCalibStride; i++) K[i] = c[i];
+    return s2_project(T, K, pw, pi, nullptr, nullptr);
+  }
+};
+// PinholeBaseK::backprojectPointAtInfinity (PinholePose.h:164-168) with Cal3_S2::calibrate: T = the composed camera pose
+GT_HD void s2_backproject_at_infinity(const double* T, const double* K, const double* z, double* dir) {
+  double pn[2];
+  s2_calibrate(K, z, pn);
+  const double l = sqrt(pn[0] * pn[0] + pn[1] * pn[1] + 1.0);
+  const double pc[3] = {pn[0] / l, pn[1] / l, 1.0 / l};
+  double w[3];
+  mat3_vec(T, pc, w);
+  const double lw = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+  dir[0] = w[0] / lw; dir[1] = w[1] / lw; dir[2] = w[2] / lw;
+}
+// PinholePose<Cal3_S2>::project2(Unit3) (CalibratedCamera.cpp:138-165, then Cal3_S2::uncalibrate): as sfm_project_at_infinity with
+// Dcal = [fx s; 0 fy].  Dpose 2x6 = [Dcal Duv [q]x | 0] (zero on the translation), Ddir 2x3 = [Dcal Duv R^T B_d | 0].
+// false on a CheiralityException (q_z <= 0).
+GT_HD bool s2_project_at_infinity(const double* T, const double* K, const double* dir, double* pi, double* Dpose, double* Ddir) {
+  double q[3];
+  mat3_tvec(T, dir, q);
+  const double lq = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
+  q[0] /= lq; q[1] /= lq; q[2] /= lq;
+  if (q[2] <= 0) return false;
+  const double d = 1.0 / q[2];
+  const double pn[2] = {q[0] * d, q[1] * d};
+  s2_uncalibrate(K, pn, pi);
+  if (Dpose || Ddir) {
+    const double fx = K[0], fy = K[1], s = K[2];
+    const double Duv[6] = {d, 0.0, -pn[0] * d, 0.0, d, -pn[1] * d};
+    if (Dpose) {
+      double S[9];
+      skew3(q[0], q[1], q[2], S);
+      for (int j = 0; j < 3; j++) {
+        const double r0 = Duv[0] * S[j] + Duv[1] * S[3 + j] + Duv[2] * S[6 + j];
+        const double r1 = Duv[3] * S[j] + Duv[4] * S[3 + j] + Duv[5] * S[6 + j];
+        Dpose[j] = fx * r0 + s * r1; Dpose[6 + j] = fy * r1;
+        Dpose[3 + j] = 0.0; Dpose[9 + j] = 0.0;
+      }
+    }
+    if (Ddir) {
+      double B[2][3];
+      unit3_basis(dir, B[0], B[1]);
+      for (int j = 0; j < 2; j++) {
+        double t[3];
+        mat3_tvec(T, B[j], t);                                         // R^T b_j
+        const double r0 = Duv[0] * t[0] + Duv[2] * t[2], r1 = Duv[4] * t[1] + Duv[5] * t[2];
+        Ddir[j] = fx * r0 + s * r1; Ddir[3 + j] = fy * r1;
+      }
+      Ddir[2] = 0.0; Ddir[5] = 0.0;
+    }
+  }
   return true;
 }
 

@@ -20,17 +20,22 @@ namespace gt {
 namespace {
 
 // Smart factors become what the rest of the library already knows: a hidden POINT3 variable per factor behind the caller's
-// variables and one GeneralSFM observation per measurement behind the caller's; every table is built from problem().  Without smart
-// factors that is the caller's struct and nothing is owned.  Pure host code.
+// variables and one observation per measurement behind the caller's -- a GeneralSFM observation for a camera-type factor
+// (SmartProjectionFactor<PinholeCamera<Cal3Bundler>>), a projection observation for a pose-type factor (SmartProjectionPoseFactor<Cal3_S2>:
+// smart_calib >= 0); every table is built from problem().  Without smart factors that is the caller's struct and nothing is owned.
+// Pure host code.
 struct SmartView {
-  std::vector<int32_t> var_type, sfm_cam, sfm_point, sfm_noise;
-  std::vector<int32_t> of_obs;   // per observation of problem(): its smart factor, -1 for the caller's own GeneralSFM factors
-  std::vector<double> sfm_z;
+  std::vector<int32_t> var_type, sfm_cam, sfm_point, sfm_noise, proj_pose, proj_point, proj_noise, proj_calib, proj_sensor;
+  std::vector<int32_t> of_obs;   // per observation of the range the measurements joined in problem(): its smart factor, -1 for the caller's own factors
+  std::vector<double> sfm_z, proj_z;
+  bool pose = false;             // the range is the projection range
   explicit SmartView(const gtg_problem& user);
   SmartView(const SmartView&) = delete;   // (p may point at q)
   const gtg_problem& problem() const { return *p; }
  private:
   gtg_problem q; const gtg_problem* p;
+  void expand_cameras(const gtg_problem& user, int64_t n_smart);
+  void expand_poses(const gtg_problem& user, int64_t n_smart);
 };
 
 SmartView::SmartView(const gtg_problem& user) : q(user), p(&user) {
@@ -39,10 +44,14 @@ SmartView::SmartView(const gtg_problem& user) : q(user), p(&user) {
   if (!user.smart_ptr || !user.smart_cam || !user.smart_z || !user.smart_noise || !user.smart_params)
     throw std::invalid_argument("smart factor tables missing");
   const int64_t n_meas = user.smart_ptr[n_smart];
+  int64_t n_pose = 0;
+  if (user.smart_calib) for (int64_t i = 0; i < n_smart; i++) n_pose += user.smart_calib[i] >= 0;
+  if (n_pose != 0 && n_pose != n_smart)
+    throw std::invalid_argument("smart factors: a graph that mixes camera-type (smart_calib -1) and pose-type (smart_calib >= 0) smart factors is not supported");
+  pose = n_pose > 0;
+  if (pose && user.n_stereo > 0)
+    throw std::invalid_argument("smart factors: pose-type smart factors together with GenericStereoFactors (three-row records) are not supported");
   var_type.assign(user.var_type, user.var_type + user.n_vars); var_type.resize((size_t)user.n_vars + n_smart, GTG_VAR_POINT3);
-  sfm_cam.assign(user.sfm_cam, user.sfm_cam + user.n_sfm); sfm_point.assign(user.sfm_point, user.sfm_point + user.n_sfm);
-  sfm_noise.assign(user.sfm_noise, user.sfm_noise + user.n_sfm); sfm_z.assign(user.sfm_z, user.sfm_z + 2 * user.n_sfm);
-  of_obs.assign((size_t)user.n_sfm, -1);
   // the device addresses a factor's measurements as smart_obs0 + smart_ptr[i] while the expanded observations are appended one
   // after the other: the offsets must start at 0 and be strictly increasing
   if (user.smart_ptr[0] != 0) throw std::invalid_argument("smart factors: smart_ptr[0] must be 0");
@@ -64,7 +73,18 @@ SmartView::SmartView(const gtg_problem& user) : q(user), p(&user) {
     if (nz < 0 || nz >= user.n_noise || user.noise_dim[nz] != 2 ||
         !(user.noise_kind[nz] == GTG_NOISE_UNIT || user.noise_kind[nz] == GTG_NOISE_ISOTROPIC))
       throw std::invalid_argument("smart factor: smart_noise must index a dim-2 Unit or Isotropic noise model");
-    for (int64_t k = k0; k < k1; k++) {
+  }
+  if (pose) expand_poses(user, n_smart); else expand_cameras(user, n_smart);
+  q.n_vars = (int32_t)var_type.size(); q.var_type = var_type.data();
+  p = &q;
+}
+
+void SmartView::expand_cameras(const gtg_problem& user, int64_t n_smart) {
+  sfm_cam.assign(user.sfm_cam, user.sfm_cam + user.n_sfm); sfm_point.assign(user.sfm_point, user.sfm_point + user.n_sfm);
+  sfm_noise.assign(user.sfm_noise, user.sfm_noise + user.n_sfm); sfm_z.assign(user.sfm_z, user.sfm_z + 2 * user.n_sfm);
+  of_obs.assign((size_t)user.n_sfm, -1);
+  for (int64_t i = 0; i < n_smart; i++)
+    for (int64_t k = user.smart_ptr[i]; k < user.smart_ptr[i + 1]; k++) {
       const int cam = user.smart_cam[k];
       if (cam < 0 || cam >= user.n_vars || user.var_type[cam] != GTG_VAR_SFM_CAMERA)
         throw std::invalid_argument("smart factor: its keys must be SFM_CAMERA variables");
@@ -72,19 +92,50 @@ SmartView::SmartView(const gtg_problem& user) : q(user), p(&user) {
       sfm_z.push_back(user.smart_z[2 * k]); sfm_z.push_back(user.smart_z[2 * k + 1]);
       of_obs.push_back((int32_t)i);
     }
-  }
-  q.n_vars = (int32_t)var_type.size(); q.var_type = var_type.data();
   q.n_sfm = (int64_t)sfm_cam.size(); q.sfm_cam = sfm_cam.data(); q.sfm_point = sfm_point.data();
   q.sfm_noise = sfm_noise.data(); q.sfm_z = sfm_z.data();
-  p = &q;
 }
 
-// per smart factor: parameters, an empty triangulation cache, cleared status words (smart_ptr and sfm_smart follow the shard
+// pose-type: one projection observation per measurement behind the caller's own GTG_FAC_PROJECTION observations, the way the stereo
+// factors joined that range
+void SmartView::expand_poses(const gtg_problem& user, int64_t n_smart) {
+  if (user.n_proj > 0 && (!user.proj_pose || !user.proj_point || !user.proj_z || !user.proj_noise || !user.proj_calib))
+    throw std::invalid_argument("projection factor tables missing");
+  proj_pose.assign(user.proj_pose, user.proj_pose + user.n_proj); proj_point.assign(user.proj_point, user.proj_point + user.n_proj);
+  proj_noise.assign(user.proj_noise, user.proj_noise + user.n_proj); proj_calib.assign(user.proj_calib, user.proj_calib + user.n_proj);
+  if (user.proj_sensor) proj_sensor.assign(user.proj_sensor, user.proj_sensor + user.n_proj); else proj_sensor.assign((size_t)user.n_proj, -1);
+  proj_z.assign(user.proj_z, user.proj_z + 2 * user.n_proj);
+  of_obs.assign((size_t)user.n_proj, -1);
+  for (int64_t i = 0; i < n_smart; i++) {
+    const int32_t ci = user.smart_calib[i], si = user.smart_sensor ? user.smart_sensor[i] : -1;
+    if (ci >= user.n_calib || !user.calib) throw std::invalid_argument("smart factor: smart_calib index out of range");
+    if (si < -1 || si >= user.n_sensor || (si >= 0 && !user.sensor)) throw std::invalid_argument("smart factor: smart_sensor index out of range");
+    if (user.calib_distortion)
+      for (int j = 0; j < 4; j++)
+        if (user.calib_distortion[4 * (size_t)ci + j] != 0.0)
+          throw std::invalid_argument("smart factor: a calibration with Cal3DS2 distortion is not supported by a pose-type smart factor (SmartProjectionPoseFactor<Cal3_S2> only)");
+    if (user.smart_params[8 * i + 6] != 0.0)
+      throw std::invalid_argument("smart factor: enableEPI is not supported on a pose-type smart factor (the refinement is written for Cal3Bundler cameras)");
+    for (int64_t k = user.smart_ptr[i]; k < user.smart_ptr[i + 1]; k++) {
+      const int v = user.smart_cam[k];
+      if (v < 0 || v >= user.n_vars || user.var_type[v] != GTG_VAR_POSE3)
+        throw std::invalid_argument("smart factor: the keys of a pose-type smart factor must be POSE3 variables");
+      proj_pose.push_back(v); proj_point.push_back((int32_t)(user.n_vars + i)); proj_noise.push_back(user.smart_noise[i]);
+      proj_calib.push_back(ci); proj_sensor.push_back(si);
+      proj_z.push_back(user.smart_z[2 * k]); proj_z.push_back(user.smart_z[2 * k + 1]);
+      of_obs.push_back((int32_t)i);
+    }
+  }
+  q.n_proj = (int64_t)proj_pose.size(); q.proj_pose = proj_pose.data(); q.proj_point = proj_point.data(); q.proj_noise = proj_noise.data();
+  q.proj_calib = proj_calib.data(); q.proj_sensor = proj_sensor.data(); q.proj_z = proj_z.data();
+}
+
+// per smart factor: parameters, an empty triangulation cache, cleared status words (smart_ptr and obs_smart follow the shard
 // filter of the observation table: upload_smart_tracks); a handle without smart factors gives the buffers of an earlier problem back
 void upload_smart_state(gtg_context& c, const gtg_problem& user) {
   const int64_t n_smart = c.n_smart;
   if (!n_smart) {
-    c.smart_ptr.free(); c.smart_params.free(); c.sfm_smart.free(); c.lm_smart.free(); c.smart_status.free(); c.smart_lin_status.free();
+    c.smart_ptr.free(); c.smart_params.free(); c.obs_smart.free(); c.lm_smart.free(); c.smart_status.free(); c.smart_lin_status.free();
     c.smart_cache_state.free(); c.smart_cache_pose.free(); c.smart_cache_point.free();
     return;
   }
@@ -211,12 +262,13 @@ class SideUpload {
 // Sharded, a smart factor follows its hidden landmark like any landmark factor: this shard holds the measurements of the
 // tracks it owns, in the order of the whole table.  The per-factor arrays keep the GLOBAL factor index (parameters, status,
 // cache); a factor of another shard has no measurements here (smart_ptr[i + 1] == smart_ptr[i]) and is skipped.
-void upload_smart_tracks(gtg_context& c, const gtg_problem& p, const std::vector<int32_t>& of_obs, const ShardFilter& own) {
+// (n, point): the observation range the measurements joined -- GeneralSFM, or projection for pose-type factors.
+void upload_smart_tracks(gtg_context& c, int64_t n, const int32_t* point, const std::vector<int32_t>& of_obs, const ShardFilter& own) {
   std::vector<int64_t> rel((size_t)c.n_smart + 1, 0);
   std::vector<int32_t> of_local;
   int64_t obs0 = 0;
-  for (int64_t i = 0; i < p.n_sfm; i++) {
-    if (own.n_shards > 1 && !own.owns_landmark(p.sfm_point[i])) continue;
+  for (int64_t i = 0; i < n; i++) {
+    if (own.n_shards > 1 && !own.owns_landmark(point[i])) continue;
     const int32_t sf = of_obs[(size_t)i];
     of_local.push_back(sf);
     if (sf < 0) obs0++; else rel[(size_t)sf + 1]++;
@@ -224,7 +276,7 @@ void upload_smart_tracks(gtg_context& c, const gtg_problem& p, const std::vector
   for (int64_t i = 0; i < c.n_smart; i++) rel[(size_t)i + 1] += rel[(size_t)i];
   c.smart_obs0 = obs0;
   up(c.smart_ptr, rel, c.stream);
-  up(c.sfm_smart, of_local, c.stream);
+  up(c.obs_smart, of_local, c.stream);
 }
 
 void upload_sfm(gtg_context& c, HostIndex& hi, const gtg_problem& p, const std::vector<int32_t>& of_obs, const ShardFilter& own, SideUpload& side) {
@@ -241,7 +293,7 @@ void upload_sfm(gtg_context& c, HostIndex& hi, const gtg_problem& p, const std::
       z.push_back(p.sfm_z[2 * i]); z.push_back(p.sfm_z[2 * i + 1]);
     }
   }
-  if (c.n_smart) upload_smart_tracks(c, p, of_obs, own);
+  if (c.n_smart && !c.smart_pose) upload_smart_tracks(c, p.n_sfm, p.sfm_point, of_obs, own);
   f.n_sfm = (int64_t)cam.size();
   up(f.sfm_cam, cam, c.stream); up(f.sfm_point, pt, c.stream);
   if (whole) side.start(c, p.sfm_noise, p.sfm_z, (size_t)p.n_sfm);
@@ -253,7 +305,7 @@ void upload_sfm(gtg_context& c, HostIndex& hi, const gtg_problem& p, const std::
   hi.sfm_cam = std::move(cam); hi.sfm_point = std::move(pt);
 }
 
-void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, const ShardFilter& own) {
+void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, const std::vector<int32_t>& of_obs, const ShardFilter& own) {
   auto& f = c.f;
   std::vector<int32_t> pose, pt, nz, cal, sen; std::vector<double> z;
   const int64_t n_stereo = p.n_stereo > 0 ? p.n_stereo : 0;
@@ -271,6 +323,7 @@ void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, cons
     if (f.stereo) z.push_back(0.0);
   }
   f.n_mono = (int64_t)pose.size();
+  if (c.smart_pose) upload_smart_tracks(c, p.n_proj, p.proj_point, of_obs, own);   // (their measurements are part of the range above)
   // the stereo factors join the observation range behind the monocular ones: the symbolic analysis, the incidence lists, the E slots,
   // the Schur terms, PCG and the shard filter see more projection observations and nothing else
   if (f.stereo) {
@@ -360,13 +413,14 @@ void upload_problem(gtg_context& c, const gtg_problem& user, int shard, int n_sh
   c.uploaded = false; c.linearized = false; c.have_trial = false;
   StageClock clk;
   c.shard = shard; c.n_shards = n_shards;
-  c.n_smart = user.n_smart > 0 ? user.n_smart : 0; c.n_user_vars = user.n_vars; c.smart_obs0 = user.n_sfm;
+  c.n_smart = user.n_smart > 0 ? user.n_smart : 0; c.n_user_vars = user.n_vars;
   // GeneralSFM records recomputed where they are needed instead of stored (fused.h) -- not with smart factors, whose measurements'
   // records depend on the factor's triangulation status, and not beside stereo factors, whose three-row records only the
   // stored-record kernels read
   c.fused_sfm = GTG_FUSED_SFM != 0 && c.n_smart == 0 && !(user.n_stereo > 0);
   const SmartView view(user);
   const gtg_problem& p = view.problem();
+  c.smart_pose = view.pose; c.smart_obs0 = view.pose ? user.n_proj : user.n_sfm;
   upload_smart_state(c, user);
   layout_variables(c, p);
   upload_noise_table(c, p);
@@ -375,7 +429,7 @@ void upload_problem(gtg_context& c, const gtg_problem& user, int shard, int n_sh
   keep_whole_graph_keys(hi, p, n_shards);
   SideUpload side;   // started by upload_sfm for a whole, non-empty table
   upload_sfm(c, hi, p, view.of_obs, own, side);
-  upload_projection(c, hi, p, own);
+  upload_projection(c, hi, p, view.of_obs, own);
   upload_between(c, hi, p, own);
   upload_priors(c, hi, p, own);
   clk.lap("factor tables (shard filter + upload)");

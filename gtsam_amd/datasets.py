@@ -481,3 +481,143 @@ def stereo_vo_graph(calibration_path, poses_path, factors_path):
             initial.insert(L(l), poses[x].R @ np.array([px, py, pz]) + poses[x].t)
     graph.addPriorPose3(X(1), poses[1], A.noiseModel.Isotropic.Sigma(6, 1e-6))
     return graph, initial
+
+
+def smart_pose_graph(n_poses=8, n_tracks=8, seed=0, arc=np.pi, radius=25.0, box=(8.0, 8.0, 8.0), K=(50.0, 50.0, 0.0, 50.0, 50.0), sigma=1.0,
+                     pixel_noise=0.05, see=1.0, params=None, sensor=None, single_tracks=0, far_tracks=0, far_distance=(1500.0, 4000.0),
+                     outlier_tracks=0, outlier_shift=150.0, explicit_landmarks=0, between_chain=False, priors=(0, 1),
+                     init_delta=None, init_noise=(0.01, 0.05)):
+    """A visual-odometry scene whose landmarks live inside SmartProjectionPose3Factors (SmartProjectionPoseFactor<Cal3_S2>), built through
+    the API mirror the way user code would: `n_poses` cameras on an arc of half opening `arc` (pi: a full circle) of radius `radius`
+    looking inward at `n_tracks` points in a box, one shared Cal3_S2 `K`, Isotropic::Sigma(2, sigma), pixel noise; every track is seen by
+    a camera with probability `see` (at least by two).  `sensor` (an api.Pose3): every smart factor has this body_P_sensor and the
+    variables are the BODY poses (camera = body * sensor).  Bad tracks, in this order behind the good ones: `single_tracks` with one
+    measurement (DEGENERATE), `far_tracks` points `far_distance` away along the arc's axis (FAR_POINT under a landmarkDistanceThreshold),
+    `outlier_tracks` with one measurement moved by `outlier_shift` pixels (OUTLIER under a dynamicOutlierRejectionThreshold).
+    `explicit_landmarks`: that many further points are Point3 variables with GenericProjectionFactors (same K and sensor);
+    `between_chain`: BetweenFactor<Pose3> along the arc; `priors`: the poses with a Diagonal prior.  Initial poses: the truth composed
+    with the fixed Pose3 `init_delta` (an api.Pose3), or perturbed by `init_noise` (rotation, translation).
+    Graph order: smart factors, projection factors, between factors, priors.  Returns (graph, initial values, info) with
+    info["kind"][t] = 0 good, 1 single, 2 far, 3 outlier for every smart factor."""
+    from . import api as A
+    rng = np.random.default_rng(seed)
+    full = arc >= np.pi
+    ang = np.linspace(-arc, arc, n_poses, endpoint=not full)
+    centers = np.stack([radius * np.sin(ang), 0.02 * radius * rng.normal(size=n_poses), -radius * np.cos(ang)], 1)
+    Rc = _rodrigues(np.stack([0.02 * rng.normal(size=n_poses), -ang, 0.02 * rng.normal(size=n_poses)], 1))   # looks at the origin (+z)
+    n_all = n_tracks + explicit_landmarks
+    pts = np.stack([rng.uniform(-b, b, n_all) for b in box], 1)
+    kind = np.zeros(n_tracks, np.int64)
+    n_bad = single_tracks + far_tracks + outlier_tracks
+    if n_bad > n_tracks:
+        raise ValueError("more bad tracks than tracks")
+    kind[n_tracks - n_bad:n_tracks - n_bad + single_tracks] = 1
+    kind[n_tracks - far_tracks - outlier_tracks:n_tracks - outlier_tracks] = 2
+    kind[n_tracks - outlier_tracks:] = 3
+    if far_tracks:
+        dist = rng.uniform(far_distance[0], far_distance[1], far_tracks)
+        pts[np.flatnonzero(kind == 2)] = np.stack([dist * rng.uniform(-0.15, 0.15, far_tracks), dist * rng.uniform(-0.12, 0.12, far_tracks), dist], 1)
+    Kc = A.Cal3_S2(*K)
+    fx, fy, s, u0, v0 = Kc.v
+    model = A.noiseModel.Isotropic.Sigma(2, sigma)
+    X, L = A.symbol_shorthand.X, A.symbol_shorthand.L
+
+    def pixel(i, pt):
+        q = Rc[i].T @ (pt - centers[i])
+        u, v = q[0] / q[2], q[1] / q[2]
+        return np.array([fx * u + s * v + u0, fy * v + v0]) + pixel_noise * rng.normal(size=2)
+
+    # the variables are body poses: camera = body * sensor
+    if sensor is not None:
+        Rs, ts = sensor.R, sensor.t
+        Rb = Rc @ Rs.T
+        tb = centers - np.einsum("nij,j->ni", Rb, ts)
+    else:
+        Rb, tb = Rc, centers
+    graph, initial = A.NonlinearFactorGraph(), A.Values()
+    seen = rng.uniform(size=(n_all, n_poses)) < see
+    for t in range(n_tracks):
+        views = np.flatnonzero(seen[t])
+        if views.size < 2:
+            views = np.sort(rng.choice(n_poses, 2, replace=False))
+        if kind[t] == 1:
+            views = views[:1]
+        f = A.SmartProjectionPose3Factor(model, Kc, sensor, params)
+        for n, i in enumerate(views):
+            z = pixel(i, pts[t])
+            if kind[t] == 3 and n == views.size - 1:
+                z = z + outlier_shift * np.array([0.8, -0.6])
+            f.add(z, X(int(i)))
+        graph.add(f)
+    for j in range(explicit_landmarks):
+        views = np.flatnonzero(seen[n_tracks + j])
+        if views.size < 2:
+            views = np.arange(2)
+        for i in views:
+            graph.add(A.GenericProjectionFactorCal3_S2(pixel(i, pts[n_tracks + j]), model, X(int(i)), L(j), Kc, sensor))
+    nm = A.noiseModel
+    if between_chain:
+        n6b = nm.Diagonal.Sigmas([0.02, 0.02, 0.03, 0.1, 0.1, 0.15])
+        for i in range(n_poses - 1):
+            Rz = Rb[i].T @ Rb[i + 1]; tz = Rb[i].T @ (tb[i + 1] - tb[i])
+            graph.add(A.BetweenFactorPose3(X(i), X(i + 1), A.Pose3(A.Rot3(Rz @ _rodrigues(rng.normal(0, 0.005, (1, 3)))[0]), tz + rng.normal(0, 0.02, 3)), n6b))
+    n6 = nm.Diagonal.Sigmas([0.1] * 3 + [0.3] * 3)
+    for i in priors:
+        graph.addPriorPose3(X(i), A.Pose3(A.Rot3(Rb[i]), tb[i]), n6)
+    if init_delta is not None:
+        Ri = Rb @ init_delta.R
+        ti = tb + np.einsum("nij,j->ni", Rb, init_delta.t)
+    else:
+        Ri = Rb @ _rodrigues(rng.normal(0, init_noise[0], (n_poses, 3)))
+        ti = tb + rng.normal(0, init_noise[1], tb.shape)
+    for i in range(n_poses):
+        initial.insert(X(i), A.Pose3(A.Rot3(Ri[i]), ti[i]))
+    for j in range(explicit_landmarks):
+        initial.insert(L(j), pts[n_tracks + j] + rng.normal(0, 0.05, 3))
+    return graph, initial, {"kind": kind, "points": pts[:n_tracks]}
+
+
+# The pose-type smart scenes the fixtures of tests/golden/make_golden_smart_pose.py are recorded on (name -> keyword arguments of
+# smart_pose_graph + the SmartProjectionParams fields).  A seed is part of the fixture: the generator checks on the CPU that the
+# reference's LM takes the same accept / reject sequence under the reversed ordering and moves to the next seed otherwise.
+SMART_POSE_SCENES = {
+    # the protocol of examples/SFMExample_SmartFactor.cpp on a scene of this project's own
+    "smart_pose_example": dict(scene=dict(n_poses=8, n_tracks=8, K=(50.0, 50.0, 0.0, 50.0, 50.0), sigma=1.0, pixel_noise=0.05,
+                                          init_delta=((-0.1, 0.2, 0.25), (0.05, -0.10, 0.20))), params=dict()),
+    "smart_pose_mixed": dict(scene=dict(n_poses=12, n_tracks=291, arc=0.5, radius=8.0, box=(2.0, 1.5, 2.0), K=(520.0, 515.0, 0.3, 320.0, 240.0),
+                                        sigma=1.5, pixel_noise=0.7, see=0.6, single_tracks=9, far_tracks=11, outlier_tracks=7, explicit_landmarks=6,
+                                        between_chain=True, priors=(0,), sensor=((0.02, -0.03, 0.01), (0.1, -0.05, 0.2)),
+                                        init_noise=(0.004, 0.02)),
+                             params=dict(degeneracyMode=1, landmarkDistanceThreshold=100.0, dynamicOutlierRejectionThreshold=40.0)),
+    "smart_pose_far_ignore": dict(scene=dict(n_poses=8, n_tracks=70, arc=0.45, radius=8.0, box=(2.0, 1.5, 2.0), K=(600.0, 600.0, 0.0, 320.0, 240.0),
+                                             sigma=1.0, pixel_noise=0.5, see=0.7, single_tracks=3, far_tracks=8),
+                                  params=dict(degeneracyMode=0, linearizationMode=0, landmarkDistanceThreshold=100.0)),
+    "smart_pose_far_infinity": dict(scene=dict(n_poses=8, n_tracks=70, arc=0.45, radius=8.0, box=(2.0, 1.5, 2.0), K=(600.0, 600.0, 0.0, 320.0, 240.0),
+                                               sigma=1.0, pixel_noise=0.5, see=0.7, single_tracks=3, far_tracks=8),
+                                    params=dict(degeneracyMode=2, linearizationMode=0, landmarkDistanceThreshold=100.0)),
+    "smart_pose_far_jacobian_q": dict(scene=dict(n_poses=8, n_tracks=70, arc=0.45, radius=8.0, box=(2.0, 1.5, 2.0), K=(600.0, 600.0, 0.0, 320.0, 240.0),
+                                                 sigma=1.0, pixel_noise=0.5, see=0.7, single_tracks=3, far_tracks=8),
+                                      params=dict(degeneracyMode=0, linearizationMode=2, landmarkDistanceThreshold=100.0)),
+}
+
+
+# The far scenes on a WIDE arc with a landmarkDistanceThreshold that fails the near tracks too: the direction of such a track's first
+# measurement, seen from the first camera, lies behind the cameras at the other end of the arc, where the reference throws a
+# CheiralityException (tests/test_gpu_smart_pose.py)
+SMART_POSE_WIDE_ARC = dict(scene=dict(arc=0.9), params=dict(landmarkDistanceThreshold=8.0))
+
+
+def smart_pose_scene(name, seed=0, scene=None, params=None):
+    """(graph, initial values, info) of one of SMART_POSE_SCENES; `scene` / `params`: keyword arguments of smart_pose_graph /
+    SmartProjectionParams fields to replace."""
+    from . import api as A
+    spec = SMART_POSE_SCENES[name]
+    prm = A.SmartProjectionParams()
+    for k, v in {**spec["params"], **(params or {})}.items():
+        setattr(prm, k, v)
+    scene = {**spec["scene"], **(scene or {})}
+    for key in ("sensor", "init_delta"):
+        if scene.get(key) is not None:
+            w, t = scene[key]
+            scene[key] = A.Pose3(A.Rot3(_rodrigues(np.array([w]))[0]), np.array(t))
+    return smart_pose_graph(seed=seed, params=prm, **scene)

@@ -19,6 +19,7 @@
 #include <gtsam/slam/GeneralSFMFactor.h>
 #include <gtsam/slam/ProjectionFactor.h>
 #include <gtsam/slam/SmartProjectionFactor.h>
+#include <gtsam/slam/SmartProjectionPoseFactor.h>
 #include <gtsam/slam/StereoFactor.h>
 
 #include <gtsam/config.h>
@@ -57,6 +58,7 @@
 #include <new>
 #include <stdexcept>
 #include <thread>
+#include <array>
 #include <type_traits>
 #include <typeinfo>
 
@@ -76,6 +78,15 @@ typedef SmartProjectionFactor<SfmCamera> SmartFactor;   // the factor of timing/
 struct SmartAccess : SmartFactor {
   static SharedIsotropic SmartFactorBase<SfmCamera>::* noise() { return &SmartAccess::noiseModel_; }
   static SmartProjectionParams SmartFactor::* params() { return &SmartAccess::params_; }
+};
+// SmartProjectionPoseFactor<Cal3_S2> (wrapped as SmartProjectionPose3Factor; examples/SFMExample_SmartFactor.cpp): K through
+// calibration(); noise model, parameters and the optional body_P_sensor the same way
+typedef PinholePose<Cal3_S2> PoseCamera;
+typedef SmartProjectionPoseFactor<Cal3_S2> SmartPoseFactor;
+struct SmartPoseAccess : SmartPoseFactor {
+  static SharedIsotropic SmartFactorBase<PoseCamera>::* noise() { return &SmartPoseAccess::noiseModel_; }
+  static SmartProjectionParams SmartProjectionFactor<PoseCamera>::* params() { return &SmartPoseAccess::params_; }
+  static std::optional<Pose3> SmartFactorBase<PoseCamera>::* sensor() { return &SmartPoseAccess::body_P_sensor_; }
 };
 typedef internal::LevenbergMarquardtState State;
 
@@ -358,6 +369,9 @@ struct Extract {
   std::vector<int32_t> bt_dim, pr_dim;                                      // expected noise dimension per between / prior factor
   std::vector<std::pair<const void*, int>> pj_cal;                          // calibration object per projection factor, 1 = Cal3DS2
   std::vector<const Cal3_S2Stereo*> st_cal;                                 // calibration object per stereo factor
+  std::vector<const Cal3_S2*> sm_cal;                                       // per smart factor: the shared K of a pose-type factor, null for a camera-type one
+  std::vector<int32_t> sm_sen;                                              // per smart factor: row of `sensor` (this chunk's) or -1
+  std::vector<uint8_t> sensor_shared;                                       // per row of `sensor`: 1 = a smart factor's body_P_sensor, shared by value (mergeTables)
   std::exception_ptr err;                                                   // what the chunk's first offending factor threw
   static void run(Runs& r, const SharedNoiseModel& nm) { if (!r.empty() && r.back().second.get() == nm.get()) r.back().first++; else r.emplace_back(1, nm); }
   static double* grow(std::vector<double>& v, size_t n) { v.resize(v.size() + n); return v.data() + v.size() - n; }   // n more doubles, zero-filled
@@ -376,7 +390,7 @@ template <class CAL> void addProjection(Extract& x, const GenericProjectionFacto
   x.pj_z.push_back(p.measured().x()); x.pj_z.push_back(p.measured().y());
   Extract::run(x.pj_nz, p.noiseModel());
   x.pj_cal.emplace_back(p.calibration().get(), std::is_same<CAL, Cal3DS2>::value ? 1 : 0);
-  if (p.body_P_sensor()) { x.pj_sen.push_back((int32_t)(x.sensor.size() / 12)); packPose(*p.body_P_sensor(), Extract::grow(x.sensor, 12)); }
+  if (p.body_P_sensor()) { x.pj_sen.push_back((int32_t)(x.sensor.size() / 12)); packPose(*p.body_P_sensor(), Extract::grow(x.sensor, 12)); x.sensor_shared.push_back(0); }
   else x.pj_sen.push_back(-1);
 }
 // GenericStereoFactor<Pose3, Point3> (slam/StereoFactor.h): measurement (uL, uR, v), shared Cal3_S2Stereo, optional body_P_sensor in the
@@ -388,28 +402,44 @@ void addStereo(Extract& x, const StereoFactor& p, const std::vector<Key>& keys) 
   x.st_z.push_back(p.measured().uL()); x.st_z.push_back(p.measured().uR()); x.st_z.push_back(p.measured().v());
   Extract::run(x.st_nz, p.noiseModel());
   x.st_cal.push_back(p.calibration().get());
-  if (p.body_P_sensor()) { x.st_sen.push_back((int32_t)(x.sensor.size() / 12)); packPose(*p.body_P_sensor(), Extract::grow(x.sensor, 12)); }
+  if (p.body_P_sensor()) { x.st_sen.push_back((int32_t)(x.sensor.size() / 12)); packPose(*p.body_P_sensor(), Extract::grow(x.sensor, 12)); x.sensor_shared.push_back(0); }
   else x.st_sen.push_back(-1);
 }
-void addSmart(Extract& x, const SmartFactor& sf, const std::vector<Key>& keys) {
+// the rows every smart factor has, whatever its camera type: parameters, noise model, keys and measurements
+template <class FACTOR>
+void addSmartRows(Extract& x, const FACTOR& sf, const SmartProjectionParams& sp, const SharedIsotropic& iso, const std::vector<Key>& keys, const char* what) {
   x.fac_map.emplace_back(-2, (int64_t)x.sm_prm.size() / 8);   // (no Jacobian record: its linearisation is a Hessian factor)
-  const SmartProjectionParams& sp = sf.*SmartAccess::params();
   const TriangulationParameters& tp = sp.triangulation;
   // HESSIAN, JACOBIAN_Q and JACOBIAN_SVD are the same normal equations (the device never forms the factor itself); an
-  // IMPLICIT_SCHUR factor cannot be eliminated by the reference's direct solvers either.  (throwCheirality / verboseCheirality
-  // are read by the pose-only smart factors, not by SmartProjectionFactor<CAMERA>.)
-  if (sp.linearizationMode == IMPLICIT_SCHUR) throw std::invalid_argument("SmartProjectionFactor: the IMPLICIT_SCHUR linearisation is not supported");
-  if (tp.useLOST) throw std::invalid_argument("SmartProjectionFactor: useLOST is not supported");
-  if (tp.enableEPI && tp.noiseModel) throw std::invalid_argument("SmartProjectionFactor: enableEPI with a noise model in the triangulation parameters is not supported");
-  const SharedIsotropic& iso = sf.*SmartAccess::noise();
+  // IMPLICIT_SCHUR factor cannot be eliminated by the reference's direct solvers either.
+  if (sp.linearizationMode == IMPLICIT_SCHUR) throw std::invalid_argument(std::string(what) + ": the IMPLICIT_SCHUR linearisation is not supported");
+  if (tp.useLOST) throw std::invalid_argument(std::string(what) + ": useLOST is not supported");
+  if (tp.enableEPI && tp.noiseModel) throw std::invalid_argument(std::string(what) + ": enableEPI with a noise model in the triangulation parameters is not supported");
   Extract::run(x.sm_nz, iso);
   const auto& zs = sf.measured();
-  if (zs.size() != sf.keys().size() || zs.empty()) throw std::invalid_argument("SmartProjectionFactor: measurements and keys do not match");
+  if (zs.size() != sf.keys().size() || zs.empty()) throw std::invalid_argument(std::string(what) + ": measurements and keys do not match");
   for (size_t k = 0; k < zs.size(); k++) { x.sm_cam.push_back(idOf(keys, sf.keys()[k])); x.sm_z.push_back(zs[k].x()); x.sm_z.push_back(zs[k].y()); }
   x.sm_ptr.push_back((int64_t)x.sm_cam.size());
   x.sm_prm.insert(x.sm_prm.end(), {tp.rankTolerance, tp.landmarkDistanceThreshold, tp.dynamicOutlierRejectionThreshold, sp.retriangulationThreshold,
                                    sp.degeneracyMode == ZERO_ON_DEGENERACY ? 1.0 : (sp.degeneracyMode == HANDLE_INFINITY ? 2.0 : 0.0),
                                    sp.linearizationMode == JACOBIAN_Q ? 2.0 : (sp.linearizationMode == JACOBIAN_SVD ? 3.0 : 0.0), tp.enableEPI ? 1.0 : 0.0, 0.0});
+}
+// SmartProjectionFactor<SfmCamera>.  (throwCheirality / verboseCheirality are read by the pose-only smart factors, not by
+// SmartProjectionFactor<CAMERA>.)
+void addSmart(Extract& x, const SmartFactor& sf, const std::vector<Key>& keys) {
+  addSmartRows(x, sf, sf.*SmartAccess::params(), sf.*SmartAccess::noise(), keys, "SmartProjectionFactor");
+  x.sm_cal.push_back(nullptr); x.sm_sen.push_back(-1);
+}
+// SmartProjectionPoseFactor<Cal3_S2>: the keys are Pose3 variables, one shared K (a row of the calib table) and an optional
+// body_P_sensor (a row of the sensor table, shared by value among the smart factors)
+void addSmartPose(Extract& x, const SmartPoseFactor& sf, const std::vector<Key>& keys) {
+  if (!sf.calibration()) throw std::invalid_argument("SmartProjectionPoseFactor: no calibration");
+  if ((sf.*SmartPoseAccess::params()).triangulation.enableEPI) throw std::invalid_argument("SmartProjectionPoseFactor: enableEPI is not supported");
+  addSmartRows(x, sf, sf.*SmartPoseAccess::params(), sf.*SmartPoseAccess::noise(), keys, "SmartProjectionPoseFactor");
+  x.sm_cal.push_back(sf.calibration().get());
+  const std::optional<Pose3>& bs = sf.*SmartPoseAccess::sensor();
+  if (bs) { x.sm_sen.push_back((int32_t)(x.sensor.size() / 12)); packPose(*bs, Extract::grow(x.sensor, 12)); x.sensor_shared.push_back(1); }
+  else x.sm_sen.push_back(-1);
 }
 // BetweenFactor<Pose3>, and <Pose2> in the same table: the factor's type follows from its variables', (x, y, theta) in the first 3 of the 12 doubles
 template <class T> void addBetween(Extract& x, const BetweenFactor<T>& b, const std::vector<Key>& keys) {
@@ -430,6 +460,7 @@ void addFactor(Extract& x, const NonlinearFactor* f, const std::vector<Key>& key
   else if (auto pd = dynamic_cast<const ProjFactorDS2*>(f)) addProjection(x, *pd, keys);
   else if (auto st = dynamic_cast<const StereoFactor*>(f)) addStereo(x, *st, keys);
   else if (auto sf = dynamic_cast<const SmartFactor*>(f)) addSmart(x, *sf, keys);
+  else if (auto sp = dynamic_cast<const SmartPoseFactor*>(f)) addSmartPose(x, *sp, keys);
   else if (auto bb = dynamic_cast<const BetweenFactor<Pose3>*>(f)) addBetween(x, *bb, keys);
   else if (auto b2 = dynamic_cast<const BetweenFactor<Pose2>*>(f)) addBetween(x, *b2, keys);
   else if (auto q2 = dynamic_cast<const PriorFactor<Pose2>*>(f)) addPrior(x, *q2, keys);
@@ -438,7 +469,7 @@ void addFactor(Extract& x, const NonlinearFactor* f, const std::vector<Key>& key
   else if (auto p3 = dynamic_cast<const PriorFactor<Point3>*>(f)) addPrior(x, *p3, keys);
   else throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: factor type outside the GPU hot path "   // (anything else is a hard error)
                                    "(supported: GeneralSFMFactor<SfmCamera,Point3>, GenericProjectionFactor<Pose3,Point3,Cal3_S2|Cal3DS2>, "
-                                   "GenericStereoFactor<Pose3,Point3>, SmartProjectionFactor<SfmCamera>, BetweenFactor<Pose3|Pose2>, PriorFactor<Pose3|Pose2|SfmCamera|Point3>)");
+                                   "GenericStereoFactor<Pose3,Point3>, SmartProjectionFactor<SfmCamera>, SmartProjectionPoseFactor<Cal3_S2>, BetweenFactor<Pose3|Pose2>, PriorFactor<Pose3|Pose2|SfmCamera|Point3>)");
 }
 // The factors [b, e) of `graph` into x, each pointer also copied into `graphCopy`; the chunk stops at its first offending factor and keeps what that threw.
 void extractChunk(Extract& x, const NonlinearFactorGraph& graph, NonlinearFactorGraph& graphCopy, const std::vector<Key>& keys, size_t b, size_t e) {
@@ -472,9 +503,11 @@ struct HostProblem {
   NoiseTable nt;
   RawI sfm_cam, sfm_pt, sfm_nz;
   RawD sfm_z;
-  std::vector<int32_t> pj_pose, pj_pt, pj_nz, pj_cal, pj_sen, st_pose, st_pt, st_nz, st_cal, st_sen, bt_1, bt_2, bt_nz, pr_var, pr_nz, sm_cam, sm_nz;
+  std::vector<int32_t> pj_pose, pj_pt, pj_nz, pj_cal, pj_sen, st_pose, st_pt, st_nz, st_cal, st_sen, bt_1, bt_2, bt_nz, pr_var, pr_nz, sm_cam, sm_nz, sm_cal, sm_sen;
   std::vector<double> pj_z, st_z, calib, sensor, bt_z, pr_data, sm_z, sm_prm;
   std::vector<int64_t> pr_off, sm_ptr{0};    // (smart factors: one track each)
+  bool any_smart_pose = false;               // a SmartProjectionPoseFactor: the smart_calib / smart_sensor tables go to the library
+  std::map<std::array<double, 12>, int32_t> shared_sensor;   // the body_P_sensor of smart factors -> row of the sensor table
   std::map<const void*, int32_t> calib_id;   // shared calibration objects (Cal3_S2 or Cal3DS2) -> row of the calibration table
   std::vector<double> calib_dist;            // k1 k2 p1 p2 per row (zero for a Cal3_S2)
   std::vector<double> calib_base;            // baseline per row (zero unless the row is a Cal3_S2Stereo)
@@ -514,6 +547,7 @@ struct HostProblem {
     pb.n_between = (int64_t)bt_1.size(); pb.between_v1 = bt_1.data(); pb.between_v2 = bt_2.data(); pb.between_z = bt_z.data(); pb.between_noise = bt_nz.data();
     pb.n_smart = (int64_t)sm_nz.size(); pb.smart_ptr = sm_ptr.data(); pb.smart_cam = sm_cam.data(); pb.smart_z = sm_z.data();
     pb.smart_noise = sm_nz.data(); pb.smart_params = sm_prm.data();
+    pb.smart_calib = any_smart_pose ? sm_cal.data() : nullptr; pb.smart_sensor = any_smart_pose ? sm_sen.data() : nullptr;
     pb.n_prior = (int64_t)pr_var.size(); pb.prior_var = pr_var.data(); pb.prior_off = pr_off.data(); pb.prior_data = pr_data.data(); pb.prior_noise = pr_nz.data();
     return pb;
   }
@@ -607,19 +641,32 @@ HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap
   int64_t o_sfm_next = 0;
   for (size_t pi = 0; pi < part.size(); pi++) {
     const Extract& x = part[pi];
-    const int64_t o_sen = (int64_t)(hp.sensor.size() / 12), o_prd = (int64_t)hp.pr_data.size(), o_smc = (int64_t)hp.sm_cam.size();
+    const int64_t o_prd = (int64_t)hp.pr_data.size(), o_smc = (int64_t)hp.sm_cam.size();
+    // the chunk's sensor rows into the table, in graph order: a projection / stereo factor's row as it is, a smart factor's shared
+    // by value with the rows other smart factors brought (one body_P_sensor for a whole front end) -- the rows of a one-thread pass
+    std::vector<int32_t> sen_row(x.sensor.size() / 12);
+    for (size_t r = 0; r < sen_row.size(); r++) {
+      const double* sp = x.sensor.data() + 12 * r;
+      if (x.sensor_shared[r]) {
+        std::array<double, 12> key; std::copy(sp, sp + 12, key.begin());
+        auto it = hp.shared_sensor.find(key);
+        if (it != hp.shared_sensor.end()) { sen_row[r] = it->second; continue; }
+        hp.shared_sensor.emplace(key, (int32_t)(hp.sensor.size() / 12));
+      }
+      sen_row[r] = (int32_t)(hp.sensor.size() / 12);
+      hp.sensor.insert(hp.sensor.end(), sp, sp + 12);
+    }
     place[pi].o_sfm = o_sfm_next; place[pi].o_pj = (int64_t)hp.pj_pose.size(); place[pi].o_st = (int64_t)hp.st_pose.size(); place[pi].o_bt = (int64_t)hp.bt_1.size();
     place[pi].o_pr = (int64_t)hp.pr_var.size(); place[pi].o_sm = (int64_t)hp.sm_nz.size();
     o_sfm_next += (int64_t)x.sfm_cam.size();
     for (const auto& r : x.sfm_nz) place[pi].sfm_rows.emplace_back(r.first, hp.nt.add(r.second, 2));
     cat(hp.pj_pose, x.pj_pose); cat(hp.pj_pt, x.pj_pt); cat(hp.pj_z, x.pj_z);
     rows(hp.pj_nz, x.pj_nz, nullptr);
-    for (int32_t sidx : x.pj_sen) hp.pj_sen.push_back(sidx < 0 ? -1 : (int32_t)(sidx + o_sen));
-    cat(hp.sensor, x.sensor);
+    for (int32_t sidx : x.pj_sen) hp.pj_sen.push_back(sidx < 0 ? -1 : sen_row[(size_t)sidx]);
     for (const auto& kc : x.pj_cal) hp.pj_cal.push_back(hp.calibRow(kc.first, kc.second));
     cat(hp.st_pose, x.st_pose); cat(hp.st_pt, x.st_pt); cat(hp.st_z, x.st_z);
     rows3(hp.st_nz, x.st_nz);
-    for (int32_t sidx : x.st_sen) hp.st_sen.push_back(sidx < 0 ? -1 : (int32_t)(sidx + o_sen));
+    for (int32_t sidx : x.st_sen) hp.st_sen.push_back(sidx < 0 ? -1 : sen_row[(size_t)sidx]);
     for (const Cal3_S2Stereo* K : x.st_cal) hp.st_cal.push_back(hp.stereoCalibRow(K));
     cat(hp.bt_1, x.bt_1); cat(hp.bt_2, x.bt_2); cat(hp.bt_z, x.bt_z);
     rows(hp.bt_nz, x.bt_nz, &x.bt_dim);
@@ -629,6 +676,8 @@ HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap
     cat(hp.sm_cam, x.sm_cam); cat(hp.sm_z, x.sm_z); cat(hp.sm_prm, x.sm_prm);
     for (size_t k = 1; k < x.sm_ptr.size(); k++) hp.sm_ptr.push_back(x.sm_ptr[k] + o_smc);
     rows(hp.sm_nz, x.sm_nz, nullptr);
+    for (const Cal3_S2* K : x.sm_cal) { hp.sm_cal.push_back(K ? hp.calibRow(K, 0) : -1); hp.any_smart_pose = hp.any_smart_pose || K; }
+    for (int32_t sidx : x.sm_sen) hp.sm_sen.push_back(sidx < 0 ? -1 : sen_row[(size_t)sidx]);
   }
   // the big tables, by threads, one chunk each, now that the offsets and the noise rows are handed out in graph order
   parallelRanges(part.size(), part.size(), [&](size_t pi, size_t, size_t) {

@@ -42,6 +42,7 @@ class gtg_problem(C.Structure):
         ("smart_params", _f64p),
         ("n_stereo", C.c_int64), ("stereo_pose", _i32p), ("stereo_point", _i32p), ("stereo_z", _f64p), ("stereo_noise", _i32p),
         ("stereo_calib", _i32p), ("stereo_sensor", _i32p), ("calib_baseline", _f64p),
+        ("smart_calib", _i32p), ("smart_sensor", _i32p),
     ]
 
 
@@ -77,6 +78,10 @@ class Problem:
     smart_z: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float64))
     smart_noise: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     smart_params: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float64))
+    # SmartProjectionPoseFactor<Cal3_S2>: per smart factor an entry of `calib` (-1: a camera-type factor) and of `sensor` (-1: none);
+    # empty = every factor is camera-type (the C ABI's NULL)
+    smart_calib: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    smart_sensor: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     # GenericStereoFactor<Pose3, Point3>: measurement (uL, uR, v), calibration = an entry of `calib` plus its `calib_baseline`
     stereo_pose: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     stereo_point: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
@@ -109,7 +114,7 @@ class Problem:
                          ("prior_data", np.float64), ("prior_noise", np.int32),
                          ("stereo_pose", np.int32), ("stereo_point", np.int32), ("stereo_z", np.float64),
                          ("stereo_noise", np.int32), ("stereo_calib", np.int32), ("stereo_sensor", np.int32),
-                         ("calib_baseline", np.float64)):
+                         ("calib_baseline", np.float64), ("smart_calib", np.int32), ("smart_sensor", np.int32)):
             setattr(self, name, _a(getattr(self, name), dt))
 
     # ---- sizes -------------------------------------------------------------------------------
@@ -213,11 +218,17 @@ class Problem:
             if self.smart_ptr.size != self.n_smart + 1 or self.smart_params.size != 8 * self.n_smart or \
                self.smart_cam.size != int(self.smart_ptr[-1]) or self.smart_z.size != 2 * self.smart_cam.size:
                 raise ValueError("inconsistent smart factor tables")
+            if self.smart_calib.size not in (0, self.n_smart) or self.smart_sensor.size not in (0, self.n_smart):
+                raise ValueError("inconsistent smart factor tables (smart_calib / smart_sensor hold one entry per smart factor, or none)")
+            if self.smart_sensor.size and not self.smart_calib.size:
+                raise ValueError("smart_sensor without smart_calib: only pose-type smart factors have a body_P_sensor")
         p.smart_ptr = ptr(np.ascontiguousarray(self.smart_ptr, np.int64), C.c_int64) if self.n_smart else C.cast(None, C.POINTER(C.c_int64))
         p.smart_cam = ptr(self.smart_cam, C.c_int32)
         p.smart_z = ptr(self.smart_z, C.c_double)
         p.smart_noise = ptr(self.smart_noise, C.c_int32)
         p.smart_params = ptr(self.smart_params, C.c_double)
+        p.smart_calib = ptr(self.smart_calib, C.c_int32)
+        p.smart_sensor = ptr(self.smart_sensor, C.c_int32)
         p.n_stereo = self.n_stereo
         if self.n_stereo:
             if self.stereo_sensor.size == 0:
@@ -238,8 +249,10 @@ class Problem:
     # ---- smart factors -----------------------------------------------------------------------
     def add_smart(self, cams, zs, noise_idx: int, rank_tolerance=1.0, landmark_distance_threshold=-1.0,
                   dynamic_outlier_rejection_threshold=-1.0, retriangulation_threshold=1e-5, degeneracy_mode=0,
-                  linearization_mode=0, enable_epi=False):
-        """One SmartProjectionFactor<PinholeCamera<Cal3Bundler>>: camera variable ids + their pixel measurements; defaults =
+                  linearization_mode=0, enable_epi=False, calib=-1, sensor=-1):
+        """One SmartProjectionFactor<PinholeCamera<Cal3Bundler>>: camera variable ids + their pixel measurements -- or, with calib >= 0
+        (an entry of the calib table; sensor: an entry of the sensor table or -1), one SmartProjectionPoseFactor<Cal3_S2>: POSE3
+        variable ids + their pixel measurements; defaults =
         SmartProjectionParams() / TriangulationParameters() (slam/SmartFactorParams.h:58-66, geometry/triangulation.h:583-600).
         degeneracy_mode 0 IGNORE_DEGENERACY, 1 ZERO_ON_DEGENERACY, 2 HANDLE_INFINITY; linearization_mode 0 HESSIAN, 2 JACOBIAN_Q,
         3 JACOBIAN_SVD (1 = IMPLICIT_SCHUR cannot be eliminated by the reference's direct solvers and is refused); enable_epi =
@@ -253,6 +266,11 @@ class Problem:
         self.smart_params = np.concatenate([self.smart_params, [rank_tolerance, landmark_distance_threshold,
                                                                 dynamic_outlier_rejection_threshold, retriangulation_threshold,
                                                                 float(degeneracy_mode), float(linearization_mode), 1.0 if enable_epi else 0.0, 0.0]])
+        if calib >= 0 or sensor >= 0 or self.smart_calib.size:      # the two tables exist once a pose-type factor does
+            n = self.smart_noise.size - 1
+            pad = lambda a: np.concatenate([a, np.full(n - a.size, -1, np.int32)])
+            self.smart_calib = np.append(pad(self.smart_calib), np.int32(calib))
+            self.smart_sensor = np.append(pad(self.smart_sensor), np.int32(sensor))
 
     # ---- priors ------------------------------------------------------------------------------
     def add_prior(self, var: int, value, noise_idx: int):

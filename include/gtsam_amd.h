@@ -123,14 +123,15 @@ typedef struct gtg_problem {
                                      every entry of the calib table is a plain Cal3_S2.  (Appended in round 2: a caller built
                                      against the older struct must be recompiled.) */
 
-  /* SmartProjectionFactor<PinholeCamera<Cal3Bundler>> (slam/SmartProjectionFactor.h, the factor of timing/timeSFMBALsmart.cpp):
+  /* SmartProjectionFactor<PinholeCamera<Cal3Bundler>> (slam/SmartProjectionFactor.h, the factor of timing/timeSFMBALsmart.cpp), or --
+   * with smart_calib at the end of this struct -- SmartProjectionPoseFactor<Cal3_S2>:
    * one factor = one track; its landmark is NOT a variable but re-triangulated from the cameras at every linearisation / error
    * evaluation (DLT, geometry/triangulation.cpp:27-57, checks of triangulateSafe triangulation.h:697-752, cached while no camera
    * pose moves by more than retriangulationThreshold, SmartProjectionFactor.h:127-183) and eliminated without damping (the Schur
    * complement of the point, :190-233; JacobianFactorQ / JacobianFactorSVD are the same normal equations).  NULL / 0: no smart factors. */
   int64_t n_smart;
   const int64_t* smart_ptr;       /* [n_smart+1] offsets of a factor's measurements in smart_cam / smart_z (>= 1 measurement each) */
-  const int32_t* smart_cam;       /* variable id (SFM_CAMERA) of every measurement */
+  const int32_t* smart_cam;       /* variable id (SFM_CAMERA; POSE3 for a pose-type factor) of every measurement */
   const double* smart_z;          /* 2 per measurement */
   const int32_t* smart_noise;     /* [n_smart] index into the noise table (dim 2, Unit or Isotropic as the reference requires) */
   const double* smart_params;     /* [n_smart*8] rankTolerance, landmarkDistanceThreshold, dynamicOutlierRejectionThreshold,
@@ -157,6 +158,16 @@ typedef struct gtg_problem {
   const int32_t* stereo_sensor;   /* [n_stereo] index into the sensor table or -1; NULL: no factor has a body_P_sensor */
   const double* calib_baseline;   /* [n_calib] Cal3_S2Stereo::baseline(); read only for the entries a stereo factor refers to; must be
                                      non-NULL when n_stereo > 0 */
+
+  /* SmartProjectionPoseFactor<Cal3_S2> (slam/SmartProjectionPoseFactor.h, wrapped as SmartProjectionPose3Factor; the factor of
+   * examples/SFMExample_SmartFactor.cpp and ISAM2Example_SmartFactor.cpp): a smart factor whose keys are POSE3 variables, with one shared
+   * fixed Cal3_S2 and an optional body_P_sensor; its cameras are PinholePose<Cal3_S2>(pose * body_P_sensor, K) (:138-147), the camera
+   * dimension is 6.  Such a factor uses the smart tables above -- smart_cam then holds POSE3 variable ids -- and says so here.
+   * Refused by gtg_upload_problem (out of scope, not computed as something else): camera-type and pose-type smart factors in one
+   * graph; pose-type smart factors beside GenericStereoFactors; a calib entry with Cal3DS2 distortion; enableEPI on a pose-type factor.
+   * (Appended after the stereo tables: a caller built against the older struct must be recompiled.) */
+  const int32_t* smart_calib;     /* [n_smart] index into the calib table, or -1 for a camera-type smart factor; NULL: all -1 */
+  const int32_t* smart_sensor;    /* [n_smart] index into the sensor table or -1 (no body_P_sensor); NULL: none */
 } gtg_problem;
 
 /* ---- lifetime -------------------------------------------------------------------------------- */
@@ -248,7 +259,7 @@ int gtg_get_gradient(gtg_handle h, double* g, int64_t n);             /* J^T b, 
 int gtg_get_hessian_diagonal(gtg_handle h, double* d, int64_t n);     /* GaussianFactorGraph::hessianDiagonal */
 /* whitened Jacobian blocks + rhs of factor type `factor_type` after gtg_linearize():
  * row-major per factor: SFM [A1 2x9 | A2 2x3 | b 2], PROJECTION [2x6 | 2x3 | 2],
- * BETWEEN [6x6 | 6x6 | 6], PRIOR [d x d | d] padded to d=9 (81+9), STEREO [A1 3x6 | A2 3x3 | b 3] (30 doubles, the caller's stereo
+ * (the caller's own factors: never the measurements of smart factors), BETWEEN [6x6 | 6x6 | 6], PRIOR [d x d | d] padded to d=9 (81+9), STEREO [A1 3x6 | A2 3x3 | b 3] (30 doubles, the caller's stereo
  * factors in the caller's order; PROJECTION keeps returning the 20-double records of the monocular factors alone).
  * n = doubles available in out. */
 int gtg_get_jacobians(gtg_handle h, int factor_type, double* out, int64_t n);
