@@ -101,13 +101,24 @@ def test_m_estimators_host_compile_vs_oracle(hm):
     """robust_weight / robust_loss of csrc/factors.h (the device code, compiled for the host) against the oracle's
     restatement of linear/LossFunctions.cpp, across the threshold of every estimator."""
     hm.hm_robust_weight.restype = C.c_double; hm.hm_robust_loss.restype = C.c_double
-    d = np.concatenate([np.linspace(0, 12, 97), [1e-12, 1.345, 4.6851, 1e3]])
-    for rk in range(1, 7):
+    d0 = np.concatenate([np.linspace(0, 12, 97), [1e-12, 1.345, 4.6851, 1e3]])
+    for rk in range(1, 9):
         for k in (0.5, 1.345, 4.6851):
+            d = d0
+            if rk >= 7:     # DCS compares the SQUARED distance with k, the dead zone's weight is 0 up to k: points that straddle d^2 = k and d = k
+                r = np.sqrt(k)
+                d = np.concatenate([d0, [r, np.nextafter(r, 0), np.nextafter(r, 9), r * (1 - 1e-9), r * (1 + 1e-9), r - 1e-3, r + 1e-3,
+                                         k, np.nextafter(k, 0), np.nextafter(k, 9), k * (1 - 1e-9), k * (1 + 1e-9), k - 1e-3, k + 1e-3]])
+                assert (d * d > k).any() and (d * d <= k).any() and (d <= k).any() and (d > k).any()
             w = np.array([hm.hm_robust_weight(C.c_int(rk), C.c_double(k), C.c_double(x)) for x in d])
             l = np.array([hm.hm_robust_loss(C.c_int(rk), C.c_double(k), C.c_double(x)) for x in d])
             assert np.allclose(w, O.robust_weight(rk, k, d), rtol=1e-14, atol=0)
             assert np.allclose(l, O.robust_loss(rk, k, d), rtol=1e-13, atol=1e-300)
+            if rk == 7:     # the thresholds sit where stated: weight 1 up to d^2 = k, below 1 beyond ...
+                assert np.all(w[d * d <= k] == 1.0) and np.all(w[d * d > k * (1 + 1e-8)] < 1.0)
+                continue    # (... and the reference's DCS loss is not the integral of d weight(d): the relation below is not its property)
+            if rk == 8:     # weight and loss 0 up to d = k, positive beyond
+                assert np.all(w[d <= k] == 0.0) and np.all(l[d <= k] == 0.0) and np.all(w[d > k] > 0.0)
             # loss'(d) = d * weight(d)   (the defining relation, LossFunctions.h:33-60)
             h = 1e-6; dd = d[(d > 0.01) & (np.abs(d - k) > 0.01)]
             num = (O.robust_loss(rk, k, dd + h) - O.robust_loss(rk, k, dd - h)) / (2 * h)
