@@ -18,8 +18,8 @@ import numpy as np
 
 from .optimizer import DeviceLevenbergMarquardt
 from .params import LevenbergMarquardtParams
-from .problem import (NOISE_DIAGONAL, NOISE_GAUSSIAN, NOISE_ISOTROPIC, NOISE_UNIT, STORAGE, TANGENT, VAR_POINT3, VAR_POSE2, VAR_POSE3,
-                      VAR_SFM_CAMERA, Problem)
+from .problem import (NOISE_DIAGONAL, NOISE_GAUSSIAN, NOISE_ISOTROPIC, NOISE_UNIT, SAM_BEARING, SAM_BEARING_RANGE, SAM_RANGE, STORAGE, TANGENT,
+                      VAR_POINT3, VAR_POSE2, VAR_POSE3, VAR_SFM_CAMERA, Problem)
 
 
 # ---- keys ---------------------------------------------------------------------------------------------------
@@ -52,6 +52,27 @@ def Point2(x=0.0, y=0.0):
 def StereoPoint2(uL=0.0, uR=0.0, v=0.0):
     """gtsam.StereoPoint2(uL, uR, v) (geometry/StereoPoint2.h); stored as its vector()."""
     return np.array([uL, uR, v], np.float64)
+
+
+class Unit3:
+    """gtsam.Unit3 (geometry/Unit3.h): a direction, stored as the unit vector p / |p| the constructor forms (Unit3.cpp:36-38)."""
+
+    def __init__(self, x=None, y=None, z=None):
+        p = np.array([1.0, 0.0, 0.0]) if x is None else np.asarray(x if y is None else [x, y, z], np.float64).reshape(3)
+        self.p = p / np.sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2])
+
+    def point3(self): return self.p.copy()
+    def unitVector(self): return self.p.copy()
+
+
+class BearingRange3D:
+    """gtsam.BearingRange3D = BearingRange<Pose3, Point3> (geometry/BearingRange.h): a Unit3 and a range."""
+
+    def __init__(self, b: Unit3, r: float):
+        self.b, self.r = b, float(r)
+
+    def bearing(self): return self.b
+    def range(self): return self.r
 
 
 class Pose3:
@@ -259,6 +280,36 @@ class GenericStereoFactor3D:
         self.z, self.model, self.keys_, self.K, self.sensor = np.asarray(measured, np.float64).reshape(3), model, (poseKey, landmarkKey), K, body_P_sensor
 
 
+class BearingRangeFactor3D:
+    """BearingRangeFactor<Pose3, Point3> under the name of GTSAM's Python wrapper (sam/sam.i)."""
+    kind = SAM_BEARING_RANGE
+
+    def __init__(self, poseKey, pointKey, measuredBearing: Unit3, measuredRange: float, noiseModel):
+        self.keys_, self.bearing, self.range, self.model = (poseKey, pointKey), measuredBearing, float(measuredRange), noiseModel
+
+    def measured(self): return BearingRange3D(self.bearing, self.range)
+
+
+class RangeFactor3D:
+    """RangeFactor<Pose3, Point3> (sam/sam.i)."""
+    kind = SAM_RANGE
+
+    def __init__(self, key1, key2, measured: float, noiseModel):
+        self.keys_, self.bearing, self.range, self.model = (key1, key2), None, float(measured), noiseModel
+
+    def measured(self): return self.range
+
+
+class BearingFactor3D:
+    """BearingFactor<Pose3, Point3, Unit3> (sam/sam.i)."""
+    kind = SAM_BEARING
+
+    def __init__(self, key1, key2, measured: Unit3, noiseModel):
+        self.keys_, self.bearing, self.range, self.model = (key1, key2), measured, None, noiseModel
+
+    def measured(self): return self.bearing
+
+
 class SmartProjectionParams:
     """slam/SmartFactorParams.h:42-66 + geometry/triangulation.h:558-600 (IMPLICIT_SCHUR is refused at upload)."""
     IGNORE_DEGENERACY, ZERO_ON_DEGENERACY, HANDLE_INFINITY = 0, 1, 2
@@ -418,6 +469,9 @@ def extract(graph: NonlinearFactorGraph, values: Values):
             if f.sensor is not None:
                 si = len(sensors); sensors.append(f.sensor.packed())
             stereo.append((vid(f.keys_[0]), vid(f.keys_[1]), f.z, nid(f.model, 3), calibs[ck][0], si))
+        elif isinstance(f, (BearingRangeFactor3D, RangeFactor3D, BearingFactor3D)):   # no calib or sensor entry
+            p.add_sam(f.kind, vid(f.keys_[0]), vid(f.keys_[1]), nid(f.model, {SAM_BEARING_RANGE: 3, SAM_RANGE: 1, SAM_BEARING: 2}[f.kind]),
+                      None if f.bearing is None else f.bearing.p, f.range)
         elif isinstance(f, SmartProjectionFactorPinholeCameraCal3Bundler):
             sp = f.params
             p.add_smart([vid(k) for k in f.keys_], np.concatenate(f.zs), nid(f.model, 2), sp.rankTolerance, sp.landmarkDistanceThreshold,

@@ -540,7 +540,8 @@ int gtg_get_jacobians(gtg_handle c, int type, double* out, int64_t n) {
     case GTG_FAC_PROJECTION: src = c->f.proj_J.p; cnt = (c->smart_pose ? c->smart_obs0 : c->f.n_mono) * kProjRec; break;   // (not the observations of pose-type smart factors)
     case GTG_FAC_BETWEEN_POSE3: src = c->f.between_J.p; cnt = c->f.n_between * kBetweenRec; break;
     case GTG_FAC_PRIOR: src = c->f.prior_J.p; cnt = c->f.n_prior * kPriorRec; break;
-    case GTG_FAC_STEREO: src = c->f.proj_J.p + (int64_t)kStereoRec * c->f.n_mono; cnt = (c->f.n_proj - c->f.n_mono) * kStereoRec; break;
+    case GTG_FAC_STEREO: src = c->f.proj_J.p + (int64_t)kStereoRec * c->f.n_mono; cnt = (c->f.n_cam - c->f.n_mono) * kStereoRec; break;
+    case GTG_FAC_SAM: src = c->f.proj_J.p + (int64_t)kStereoRec * c->f.n_cam; cnt = (c->f.n_proj - c->f.n_cam) * kStereoRec; break;
     default: throw std::invalid_argument("unknown factor type");
   }
   if (n != cnt) throw std::invalid_argument("gtg_get_jacobians: wrong output size");
@@ -551,7 +552,7 @@ int gtg_get_jacobians(gtg_handle c, int type, double* out, int64_t n) {
     check_hip(hipStreamSynchronize(c->stream), "sync");
     src = recomputed.p;
   }
-  if (type == GTG_FAC_PROJECTION && c->f.stereo && cnt) {
+  if (type == GTG_FAC_PROJECTION && c->f.rows3 && cnt) {
     // beside stereo factors the monocular records are stored with three rows, the third zero: give back the two-row records
     // [A1 2x6 | A2 2x3 | b 2] they hold
     std::vector<double> wide((size_t)c->f.n_mono * kStereoRec);

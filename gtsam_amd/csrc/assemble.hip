@@ -747,7 +747,7 @@ void launch_assemble(gtg_context& c) {
     if (c.f.n_proj + c.f.n_between + c.f.n_prior > 0)     // the other factor types' contributions on top
       hipLaunchKernelGGL(k_red_diag<2>, dim3(c.n_red_vars), dim3(64 * kRedWaves), 0, c.stream, c.n_red_vars, c.red_inc_ptr.p,
                          c.red_inc_kind.p, c.red_inc_idx.p, c.red_dim.p, c.red_off.p, t, c.Hd.p, c.gred0.p, c.hdiag_red.p, 1);
-  } else if (c.n_red_vars && c.f.stereo)     // (a graph with stereo factors is never fused: upload.hip)
+  } else if (c.n_red_vars && c.f.rows3)     // (a graph with stereo factors is never fused: upload.hip)
     hipLaunchKernelGGL(k_red_diag<3>, dim3(c.n_red_vars), dim3(64 * kRedWaves), 0, c.stream, c.n_red_vars, c.red_inc_ptr.p,
                        c.red_inc_kind.p, c.red_inc_idx.p, c.red_dim.p, c.red_off.p, t, c.Hd.p, c.gred0.p, c.hdiag_red.p, 0);
   else if (c.n_red_vars)
@@ -756,7 +756,7 @@ void launch_assemble(gtg_context& c) {
   if (c.n_lm && c.fused_sfm)
     hipLaunchKernelGGL(k_lm_fused, dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_obs_ptr.p, c.lm_obs.p,
                        c.lm_pri_ptr.p, c.lm_pri.p, t, sfm_tabs(c), c.V.p, c.gp.p);
-  else if (c.n_lm && c.f.stereo)
+  else if (c.n_lm && c.f.rows3)
     hipLaunchKernelGGL(k_lm_diag<3>, dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_obs_ptr.p, c.lm_obs.p,
                        c.lm_pri_ptr.p, c.lm_pri.p, t, c.V.p, c.gp.p);
   else if (c.n_lm)
@@ -855,7 +855,7 @@ void launch_point_eliminate(gtg_context& c, double lambda, int diag, double dmin
   else if (c.f.n_sfm)
     hipLaunchKernelGGL((k_obs_E<kSfmRec, 9, 2, false>), dim3(grid1(c.f.n_sfm / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_sfm, c.f.sfm_J.p, st,
                        c.obs_lm.p, c.Linv.p, c.ylm.p, c.E.p, c.wobs.p, c.obs_wpos.p);
-  if (c.f.n_proj && c.f.stereo)
+  if (c.f.n_proj && c.f.rows3)
     hipLaunchKernelGGL((k_obs_E<kStereoRec, 6, 3, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
                        c.f.proj_J.p, st, c.obs_lm.p + c.f.n_sfm, c.Linv.p, c.ylm.p, c.E.p + (int64_t)kEStride * c.f.n_sfm, c.wobs.p, c.obs_wpos.p + c.f.n_sfm);
   else if (c.f.n_proj)
@@ -895,7 +895,7 @@ void launch_back_substitute(gtg_context& c) {
   else if (c.f.n_sfm && c.n_lm)
     hipLaunchKernelGGL((k_obs_v<kSfmRec, 9, 2, false>), dim3(grid1(c.f.n_sfm / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_sfm, c.f.sfm_J.p, st,
                        c.obs_red.p, c.red_off.p, c.xred.p, c.vobs.p);
-  if (c.f.n_proj && c.n_lm && c.f.stereo)
+  if (c.f.n_proj && c.n_lm && c.f.rows3)
     hipLaunchKernelGGL((k_obs_v<kStereoRec, 6, 3, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
                        c.f.proj_J.p, st, c.obs_red.p + c.f.n_sfm, c.red_off.p, c.xred.p, c.vobs.p + 3 * c.f.n_sfm);
   else if (c.f.n_proj && c.n_lm)

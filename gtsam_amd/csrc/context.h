@@ -146,12 +146,20 @@ struct FactorTables {
   int64_t n_proj = 0;
   DevBuf<int32_t> proj_pose, proj_point, proj_noise, proj_calib, proj_sensor;
   DevBuf<double> proj_z, proj_J, calib, sensor;
-  // GenericStereoFactor<Pose3, Point3>: the stereo factors are the observations [n_mono, n_proj) of the projection range.  A graph
-  // with at least one (stereo, decided on the WHOLE graph, not on a shard's rows) keeps three-row records (kStereoRec) and three
+  // GenericStereoFactor<Pose3, Point3>: the stereo factors are the observations [n_mono, n_cam) of the projection range.  A graph
+  // with at least one (rows3, decided on the WHOLE graph, not on a shard's rows) keeps three-row records (kStereoRec) and three
   // measurement entries for every observation of the range, the monocular ones with a zero third row.
   int64_t n_mono = 0;
-  bool stereo = false;
+  bool rows3 = false;              // three-row records: the WHOLE graph has a stereo or a sam factor
   DevBuf<double> calib_baseline;   // [n_calib] Cal3_S2Stereo::baseline
+  // BearingRangeFactor / RangeFactor / BearingFactor <Pose3, Point3> (gtsam/sam): the observations [n_cam, n_proj) of the projection
+  // range, behind the stereo factors [n_mono, n_cam).  They read no calib or sensor entry (proj_calib / proj_sensor hold -1 for them) and
+  // keep their measurements in an array of their own: sam_z[4 (i - n_cam)] = the measured Unit3, then the range; sam_kind GTG_SAM_*.
+  // Without sam factors n_cam == n_proj and both buffers are empty.
+  int64_t n_cam = 0;
+  bool sam = false;                // the WHOLE graph has sam factors (a shard may own none of them)
+  DevBuf<int32_t> sam_kind;
+  DevBuf<double> sam_z;
   // between
   int64_t n_between = 0;
   DevBuf<int32_t> between_v1, between_v2, between_noise;

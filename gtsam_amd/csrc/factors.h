@@ -4,6 +4,7 @@
 //   GeneralSFMFactor::linearize / evaluateError      slam/GeneralSFMFactor.h:127-177
 //   GenericProjectionFactor::evaluateError           slam/ProjectionFactor.h:138-166
 //   GenericStereoFactor<Pose3,Point3>::evaluateError  slam/StereoFactor.h:126-154
+//   BearingRange / Range / BearingFactor<Pose3,Point3>  sam/*.h through nonlinear/ExpressionFactor.h:104-153
 //   BetweenFactor<Pose3>::evaluateError              slam/BetweenFactor.h:111-124
 //   PriorFactor<T>::evaluateError                    nonlinear/PriorFactor.h:98-102
 // followed by NoiseModelFactor::linearize's  b = -r, WhitenSystem(A, b)
@@ -63,7 +64,7 @@ GT_HD double reweight_factor(const NoiseRef& n, const double* b, int m) {
 // row lengths of the per-factor Jacobian records (doubles)
 constexpr int kSfmRec = 2 * 9 + 2 * 3 + 2;   // [A1 2x9 | A2 2x3 | b 2]
 constexpr int kProjRec = 2 * 6 + 2 * 3 + 2;  // [A1 2x6 | A2 2x3 | b 2]
-constexpr int kStereoRec = 3 * 6 + 3 * 3 + 3;  // [A1 3x6 | A2 3x3 | b 3]: every projection observation of a graph WITH stereo factors
+constexpr int kStereoRec = 3 * 6 + 3 * 3 + 3;  // [A1 3x6 | A2 3x3 | b 3]: every projection observation of a three-row graph (stereo or bearing / range factors)
 constexpr int kBetweenRec = 36 + 36 + 6;     // [A1 6x6 | A2 6x6 | b 6]
 constexpr int kPriorRec = 81 + 9;            // [A dxd packed | pad ... | b d at 81]
 
@@ -304,6 +305,85 @@ GT_HD void proj_linearize_rows3(const double* pose, const double* K, const doubl
   J[18] = a0; J[19] = a1; J[20] = a2; J[21] = a3; J[22] = a4; J[23] = a5;
   J[24] = 0.0; J[25] = 0.0; J[26] = 0.0;
   J[27] = b0; J[28] = b1; J[29] = 0.0;
+}
+
+// ---- BearingRangeFactor / RangeFactor / BearingFactor <Pose3,Point3> (gtsam/sam) ---------------
+// ExpressionFactorN (nonlinear/ExpressionFactor.h:104-153): h = Pose3::bearing / Pose3::range of the point (geometry/Pose3.cpp:399-439),
+// b = Local(h, z) -- [h_bearing.localCoordinates(z_bearing) ; z_range - h_range] (BearingRange.h:138-144), in the basis of the PREDICTED
+// direction -- the Jacobians those of h alone (the chart derivative of Local is not applied), then WhitenSystem on the whole system
+// (:147-150): a Robust model re-weights by sqrt(weight(|whitened b|)).  z: the measured Unit3's three doubles, then the range.
+// The record is the three-row one (kStereoRec): bearing rows 0-1 and range row 2; a range-only factor in row 0; unused rows exactly 0.
+// Contraction is off as in sfm_linearize: q - x p and 1 - x^2 of the bearing (geom.h unit3_local) cancel, so the record must not depend
+// on which kernel, or which compiler (the host compile of the CPU parity test), inlined this.
+enum { kSamBearingRange = 0, kSamRange = 1, kSamBearing = 2 };   // = GTG_SAM_*
+GT_HD int sam_rows(int kind) { return kind == kSamBearingRange ? 3 : kind == kSamRange ? 1 : 2; }
+// the unwhitened compact system [A1 ROWS x 6 | A2 ROWS x 3 | b ROWS] (A1 = nullptr: b alone)
+template <int KIND>
+GT_HD void sam_system(const double* pose, const double* pt, const double* z, double* A1, double* A2, double* b) {
+  _Pragma("clang fp contract(off)")
+  const double dp[3] = {pt[0] - pose[9], pt[1] - pose[10], pt[2] - pose[11]};
+  double q[3];
+  mat3_tvec(pose, dp, q);   // Pose3::transformTo
+  constexpr int r0 = KIND == kSamRange ? 0 : 2;   // the range's row
+  if (KIND != kSamRange) {
+    double h[3], b1[3], b2[3], D[6];
+    unit3_from_point(q, h, b1, b2, A1 ? D : nullptr);
+    if (A1) { local_chain_row(pose, q, D, A1, A2); local_chain_row(pose, q, D + 3, A1 + 6, A2 + 3); }
+    unit3_local(h, b1, b2, z, b);
+  }
+  if (KIND != kSamBearing) {
+    double D[3];
+    const double r = norm3_with_derivative(q, D);
+    if (A1) local_chain_row(pose, q, D, A1 + 6 * r0, A2 + 3 * r0);
+    b[r0] = z[3] - r;
+  }
+}
+template <int KIND>
+GT_HD void sam_linearize_kind(const double* pose, const double* pt, const double* z, const NoiseRef& n, double* J) {
+  _Pragma("clang fp contract(off)")
+  constexpr int R = KIND == kSamBearingRange ? 3 : KIND == kSamRange ? 1 : 2;
+  double A1[6 * R], A2[3 * R], b[R];
+  sam_system<KIND>(pose, pt, z, A1, A2, b);
+  whiten_cols<R>(n.kind, n.data, A1, 6);
+  whiten_cols<R>(n.kind, n.data, A2, 3);
+  whiten_cols<R>(n.kind, n.data, b, 1);
+  if (n.rkind) {
+    const double w = reweight_factor(n, b, R);
+    for (int i = 0; i < 6 * R; i++) A1[i] *= w;
+    for (int i = 0; i < 3 * R; i++) A2[i] *= w;
+    for (int i = 0; i < R; i++) b[i] *= w;
+  }
+  for (int i = 0; i < kStereoRec; i++) J[i] = 0.0;
+  for (int r = 0; r < R; r++) {
+    for (int k = 0; k < 6; k++) J[6 * r + k] = A1[6 * r + k];
+    for (int k = 0; k < 3; k++) J[18 + 3 * r + k] = A2[3 * r + k];
+    J[27 + r] = b[r];
+  }
+}
+GT_HD void sam_linearize(int kind, const double* pose, const double* pt, const double* z, const NoiseRef& n, double* J) {
+  if (kind == kSamBearingRange) sam_linearize_kind<kSamBearingRange>(pose, pt, z, n, J);
+  else if (kind == kSamRange) sam_linearize_kind<kSamRange>(pose, pt, z, n, J);
+  else sam_linearize_kind<kSamBearing>(pose, pt, z, n, J);
+}
+// the whitened residual -Local(h, z) of the factor in its first sam_rows(kind) places (what its error is the loss of)
+template <int KIND>
+GT_HD double sam_residual_kind(const double* pose, const double* pt, const double* z, const NoiseRef& n, double* r) {
+  constexpr int R = KIND == kSamBearingRange ? 3 : KIND == kSamRange ? 1 : 2;
+  sam_system<KIND>(pose, pt, z, nullptr, nullptr, r);
+  for (int i = 0; i < R; i++) r[i] = -r[i];
+  whiten_cols<R>(n.kind, n.data, r, 1);
+  double sq = 0.0;
+  for (int i = 0; i < R; i++) sq += r[i] * r[i];
+  return sq;
+}
+GT_HD double sam_residual(int kind, const double* pose, const double* pt, const double* z, const NoiseRef& n, double* r) {
+  if (kind == kSamBearingRange) return sam_residual_kind<kSamBearingRange>(pose, pt, z, n, r);
+  if (kind == kSamRange) return sam_residual_kind<kSamRange>(pose, pt, z, n, r);
+  return sam_residual_kind<kSamBearing>(pose, pt, z, n, r);
+}
+GT_HD double sam_error(int kind, const double* pose, const double* pt, const double* z, const NoiseRef& n) {
+  double r[3];
+  return factor_loss(n, sam_residual(kind, pose, pt, z, n, r));
 }
 
 // ---- BetweenFactor<Pose3> ---------------------------------------------------------------------

@@ -176,6 +176,50 @@ __global__ __launch_bounds__(kBlock) void k_lin_stereo(int64_t n, int64_t n_mono
   }
 }
 
+// The projection range of a graph WITH bearing / range factors (gtsam/sam): k_lin_stereo with a third sub-range.  Observations
+// [0, n_mono) are monocular, [n_mono, n_cam) GenericStereoFactors, [n_cam, n) sam factors of sam_kind[i - n_cam] with the measurement
+// sam_z[4 (i - n_cam)]; they read no calib or sensor entry.  The same three-row records, LDS image and store.
+__global__ __launch_bounds__(kBlock) void k_lin_obs3(int64_t n, int64_t n_mono, int64_t n_cam, const int32_t* __restrict__ pose,
+    const int32_t* __restrict__ pt, const double* __restrict__ z, const int32_t* __restrict__ nz,
+    const int32_t* __restrict__ calib_idx, const int32_t* __restrict__ sensor_idx,
+    const double* __restrict__ calib, const double* __restrict__ baseline, const double* __restrict__ sensor,
+    const int32_t* __restrict__ sam_kind, const double* __restrict__ sam_z,
+    const double* __restrict__ values, const int64_t* __restrict__ val_off, NoiseTab nt,
+    double* __restrict__ J) {
+  typedef RecIO<kStereoRec> IO;
+  __shared__ double img[kBlock / 64][IO::LDS_DOUBLES];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double* my = img[wave];
+  const int64_t nchunks = (n + 63) / 64, stride = (int64_t)gridDim.x * (kBlock / 64);
+  for (int64_t ch = blockIdx.x * (int64_t)(kBlock / 64) + wave; ch < nchunks; ch += stride) {
+    const int64_t i = ch * 64 + lane;
+    if (i < n) {
+      double T[12], p[3];
+      const double* tp = values + val_off[pose[i]];
+      const double* pp = values + val_off[pt[i]];
+      for (int k = 0; k < 12; k++) T[k] = tp[k];
+      for (int k = 0; k < 3; k++) p[k] = pp[k];
+      if (i >= n_cam) {
+        const int64_t s = i - n_cam;
+        double zz[4];
+        for (int k = 0; k < 4; k++) zz[k] = sam_z[4 * s + k];
+        sam_linearize(sam_kind[s], T, p, zz, nt.ref(nz[i]), my + lane * IO::PITCH);
+      } else {
+        double zz[3], K[kCalibStride], S[12];
+        const int ci = calib_idx[i];
+        for (int k = 0; k < kCalibStride; k++) K[k] = calib[kCalibStride * ci + k];
+        const int si = sensor_idx[i];
+        if (si >= 0) for (int k = 0; k < 12; k++) S[k] = sensor[12 * si + k];
+        for (int k = 0; k < 3; k++) zz[k] = z[3 * i + k];
+        if (i < n_mono) proj_linearize_rows3(T, K, si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]), my + lane * IO::PITCH);
+        else stereo_linearize(T, K, baseline[ci], si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]), my + lane * IO::PITCH);
+      }
+    }
+    const int64_t left = n - ch * 64;
+    IO::store(my, J + (int64_t)kStereoRec * ch * 64, left < 64 ? (int)left : 64, lane);
+  }
+}
+
 // BetweenFactor<Pose3> or BetweenFactor<Pose2>: decided by the type of the factor's variables (both of one type)
 __global__ __launch_bounds__(kBlock) void k_lin_between(int64_t n, const int32_t* __restrict__ v1,
     const int32_t* __restrict__ v2, const double* __restrict__ z, const int32_t* __restrict__ nz,
@@ -302,6 +346,41 @@ __global__ __launch_bounds__(kBlock) void k_error_stereo(int64_t n, int64_t n_mo
     for (int k = 0; k < 3; k++) zz[k] = z[3 * i + k];
     if (i < n_mono) acc += proj_error(T, K, si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]));
     else acc += stereo_error(T, K, baseline[ci], si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]));
+  }
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// k_error_stereo for the range of k_lin_obs3 (a graph with bearing / range factors)
+__global__ __launch_bounds__(kBlock) void k_error_obs3(int64_t n, int64_t n_mono, int64_t n_cam, const int32_t* __restrict__ pose,
+    const int32_t* __restrict__ pt, const double* __restrict__ z, const int32_t* __restrict__ nz,
+    const int32_t* __restrict__ calib_idx, const int32_t* __restrict__ sensor_idx,
+    const double* __restrict__ calib, const double* __restrict__ baseline, const double* __restrict__ sensor,
+    const int32_t* __restrict__ sam_kind, const double* __restrict__ sam_z,
+    const double* __restrict__ values, const int64_t* __restrict__ val_off, NoiseTab nt, double* __restrict__ partials) {
+  double acc = 0.0;
+  const int64_t tid = blockIdx.x * (int64_t)kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = tid; i < n; i += stride) {
+    double T[12], p[3];
+    const double* tp = values + val_off[pose[i]];
+    const double* pp = values + val_off[pt[i]];
+    for (int k = 0; k < 12; k++) T[k] = tp[k];
+    for (int k = 0; k < 3; k++) p[k] = pp[k];
+    if (i >= n_cam) {
+      const int64_t s = i - n_cam;
+      double zz[4];
+      for (int k = 0; k < 4; k++) zz[k] = sam_z[4 * s + k];
+      acc += sam_error(sam_kind[s], T, p, zz, nt.ref(nz[i]));
+    } else {
+      double zz[3], K[kCalibStride], S[12];
+      const int ci = calib_idx[i];
+      for (int k = 0; k < kCalibStride; k++) K[k] = calib[kCalibStride * ci + k];
+      const int si = sensor_idx[i];
+      if (si >= 0) for (int k = 0; k < 12; k++) S[k] = sensor[12 * si + k];
+      for (int k = 0; k < 3; k++) zz[k] = z[3 * i + k];
+      if (i < n_mono) acc += proj_error(T, K, si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]));
+      else acc += stereo_error(T, K, baseline[ci], si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]));
+    }
   }
   const double s = block_sum(acc);
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
@@ -642,7 +721,11 @@ void launch_linearize(gtg_context& c) {
     hipLaunchKernelGGL(k_lin_smart_at_infinity, dim3(grid_for(f.n_sfm - c.smart_obs0)), dim3(kBlock), 0, c.stream, f.n_sfm - c.smart_obs0, c.smart_obs0,
                        f.sfm_cam.p, f.sfm_point.p, f.sfm_z.p, f.sfm_noise.p, c.values.p, c.val_off.p, nt, f.sfm_J.p, c.obs_smart.p,
                        c.smart_lin_status.p, c.scalars.p);
-  if (f.n_proj && f.stereo)
+  if (f.n_proj && f.sam)
+    hipLaunchKernelGGL(k_lin_obs3, dim3(grid_for(f.n_proj)), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.n_cam, f.proj_pose.p,
+                       f.proj_point.p, f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_baseline.p,
+                       f.sensor.p, f.sam_kind.p, f.sam_z.p, c.values.p, c.val_off.p, nt, f.proj_J.p);
+  else if (f.n_proj && f.rows3)
     hipLaunchKernelGGL(k_lin_stereo, dim3(grid_for(f.n_proj)), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.proj_pose.p,
                        f.proj_point.p, f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_baseline.p,
                        f.sensor.p, c.values.p, c.val_off.p, nt, f.proj_J.p);
@@ -696,8 +779,8 @@ void launch_sfm_records(gtg_context& c, double* dst) {
 
 void launch_error(gtg_context& c, const double* values, int slot, const double* gate) {
   auto& f = c.f;
-  // (a graph with stereo factors: its projection range goes to k_error_stereo, the third group of block partials)
-  ErrArgs a{f.n_sfm, f.stereo ? 0 : f.n_proj, f.n_between, f.n_prior,
+  // (a three-row graph: its projection range goes to k_error_stereo -- k_error_obs3 with sam factors --, the third group of block partials)
+  ErrArgs a{f.n_sfm, f.rows3 ? 0 : f.n_proj, f.n_between, f.n_prior,
             f.sfm_cam.p, f.sfm_point.p, f.sfm_noise.p, f.sfm_z.p,
             f.proj_pose.p, f.proj_point.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.proj_z.p, f.calib.p, f.sensor.p,
             f.between_v1.p, f.between_v2.p, f.between_noise.p, f.between_z.p,
@@ -707,13 +790,16 @@ void launch_error(gtg_context& c, const double* values, int slot, const double* 
   if (c.smart_pose) a_sfm.smart_of = nullptr;
   // the GeneralSFM factors and the other types in a kernel each, their block partials one behind the other
   const int64_t nrest = std::max(a.n_proj, std::max(f.n_between, f.n_prior));
-  const int gmax = f.stereo ? kMaxBlocks / 4 : kMaxBlocks / 2;
+  const int gmax = f.rows3 ? kMaxBlocks / 4 : kMaxBlocks / 2;
   const int g1 = f.n_sfm ? std::min(grid_for(f.n_sfm), gmax) : 0, g2 = (nrest || !g1) ? std::min(grid_for(nrest), gmax) : 0;
-  const int g3 = f.stereo && f.n_proj ? std::min(grid_for(f.n_proj), gmax) : 0;
+  const int g3 = f.rows3 && f.n_proj ? std::min(grid_for(f.n_proj), gmax) : 0;
   if (g1) hipLaunchKernelGGL(k_error<1>, dim3(g1), dim3(kBlock), 0, c.stream, a_sfm, values, noise_tab(c), c.partials.p);
   if (g2 && c.smart_pose) hipLaunchKernelGGL(k_error<6>, dim3(g2), dim3(kBlock), 0, c.stream, a, values, noise_tab(c), c.partials.p + g1);
   else if (g2) hipLaunchKernelGGL(k_error<2>, dim3(g2), dim3(kBlock), 0, c.stream, a, values, noise_tab(c), c.partials.p + g1);
-  if (g3) hipLaunchKernelGGL(k_error_stereo, dim3(g3), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.proj_pose.p, f.proj_point.p, f.proj_z.p,
+  if (g3 && f.sam) hipLaunchKernelGGL(k_error_obs3, dim3(g3), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.n_cam, f.proj_pose.p, f.proj_point.p,
+                                      f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_baseline.p, f.sensor.p,
+                                      f.sam_kind.p, f.sam_z.p, values, c.val_off.p, noise_tab(c), c.partials.p + g1 + g2);
+  else if (g3) hipLaunchKernelGGL(k_error_stereo, dim3(g3), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.proj_pose.p, f.proj_point.p, f.proj_z.p,
                              f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_baseline.p, f.sensor.p, values, c.val_off.p,
                              noise_tab(c), c.partials.p + g1 + g2);
   hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(kBlock), 0, c.stream, c.partials.p, g1 + g2 + g3, 1, c.scalars.p, slot);
@@ -735,7 +821,7 @@ void launch_linear_error(gtg_context& c) {
   const int64_t nmax = std::max(std::max(f.n_sfm, f.n_proj), std::max(f.n_between, f.n_prior));
   const int g = grid_for(nmax);
   static_assert(kProjRec == 10 * 2 && kStereoRec == 10 * 3, "k_linear_error addresses a projection record by its row count");
-  if (f.stereo) hipLaunchKernelGGL((k_linear_error<false, 3>), dim3(g), dim3(kBlock), 0, c.stream, a, sfm_tabs(c), c.delta.p, c.partials.p);   // (stereo: never fused, upload.hip)
+  if (f.rows3) hipLaunchKernelGGL((k_linear_error<false, 3>), dim3(g), dim3(kBlock), 0, c.stream, a, sfm_tabs(c), c.delta.p, c.partials.p);   // (stereo: never fused, upload.hip)
   else if (c.fused_sfm) hipLaunchKernelGGL((k_linear_error<true, 2>), dim3(g), dim3(kBlock), 0, c.stream, a, sfm_tabs(c), c.delta.p, c.partials.p);
   else hipLaunchKernelGGL((k_linear_error<false, 2>), dim3(g), dim3(kBlock), 0, c.stream, a, sfm_tabs(c), c.delta.p, c.partials.p);
   hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(kBlock), 0, c.stream, c.partials.p, g, 2, c.scalars.p, (int)SC_LIN0);
@@ -758,7 +844,7 @@ namespace {
 void prewarm_factors(int) {
   gt::prewarm_kernels({(const void*)gt::k_lin_sfm, (const void*)gt::k_lin_proj, (const void*)gt::k_lin_between, (const void*)gt::k_lin_prior,
                        (const void*)gt::k_error<1>, (const void*)gt::k_error<2>, (const void*)gt::k_final_sum, (const void*)gt::k_linear_error<true, 2>,
-                       (const void*)gt::k_linear_error<false, 2>, (const void*)gt::k_linear_error<false, 3>, (const void*)gt::k_lin_stereo, (const void*)gt::k_error_stereo, (const void*)gt::k_retract, (const void*)gt::k_sumsq, (const void*)gt::k_smart_triangulate<false>,
+                       (const void*)gt::k_linear_error<false, 2>, (const void*)gt::k_linear_error<false, 3>, (const void*)gt::k_lin_stereo, (const void*)gt::k_error_stereo, (const void*)gt::k_lin_obs3, (const void*)gt::k_error_obs3, (const void*)gt::k_retract, (const void*)gt::k_sumsq, (const void*)gt::k_smart_triangulate<false>,
                        (const void*)gt::k_lin_smart_at_infinity, (const void*)gt::k_error_smart_at_infinity, (const void*)gt::k_sfm_value_offsets,
                        (const void*)gt::k_smart_triangulate<true>, (const void*)gt::k_lin_proj_smart, (const void*)gt::k_error<6>,
                        (const void*)gt::k_lin_smart_pose_at_infinity, (const void*)gt::k_error_smart_pose_at_infinity});

@@ -280,6 +280,7 @@ GT_HD bool bundler_calibrate(double f, double k1, double k2, double u0, double v
 // Unit3::basis (geometry/Unit3.cpp:73-135): b1 = normalize(n x axis), axis = the coordinate axis of the smallest |n_i| (ties: x, then
 // y), b2 = n x b1.
 GT_HD void unit3_basis(const double* n, double* b1, double* b2) {
+  _Pragma("clang fp contract(off)")   // the bearing factors (sam_linearize, factors.h) project differences of nearly equal vectors on it
   const double mx = fabs(n[0]), my = fabs(n[1]), mz = fabs(n[2]);
   double a[3] = {0.0, 0.0, 0.0};
   if (mx <= my && mx <= mz) a[0] = 1.0; else if (my <= mx && my <= mz) a[1] = 1.0; else a[2] = 1.0;
@@ -774,6 +775,61 @@ GT_HD bool stereo_project(const double* T, const double* K, double b, const doub
   }
   pi[0] = K[3] + uL; pi[1] = K[3] + uR; pi[2] = K[4] + v;
   return true;
+}
+
+// ---- bearing and range of a Point3 seen from a Pose3 (gtsam/sam factors) ------------------------
+// Contraction is off in all of them: q - x p and 1 - x^2 below cancel, and a multiply-add contracted in one kernel and not in
+// another (or not in the host compile of the CPU parity test) moves what is left by many ulps.
+// One row of a chain rule through Pose3::transformTo (geometry/Pose3.cpp:371-388): a (1x3, the derivative of a scalar by the local
+// point q) times D_local_pose = [[q]x | -I] and times D_local_point = R^T.
+GT_HD void local_chain_row(const double* T, const double* q, const double* a, double* Hpose, double* Hpoint) {
+  _Pragma("clang fp contract(off)")
+  Hpose[0] = a[1] * q[2] - a[2] * q[1]; Hpose[1] = a[2] * q[0] - a[0] * q[2]; Hpose[2] = a[0] * q[1] - a[1] * q[0];
+  Hpose[3] = -a[0]; Hpose[4] = -a[1]; Hpose[5] = -a[2];
+  for (int j = 0; j < 3; j++) Hpoint[j] = a[0] * T[3 * j] + a[1] * T[3 * j + 1] + a[2] * T[3 * j + 2];
+}
+// Pose3::range's norm3 (geometry/Point3.cpp:41-50): r and its derivative by q, which falls back to (1, 1, 1) when r <= 1e-10
+GT_HD double norm3_with_derivative(const double* q, double* D) {
+  _Pragma("clang fp contract(off)")
+  const double r = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
+  if (fabs(r) > 1e-10) { D[0] = q[0] / r; D[1] = q[1] / r; D[2] = q[2] / r; }
+  else { D[0] = 1.0; D[1] = 1.0; D[2] = 1.0; }
+  return r;
+}
+// Unit3::FromPoint3 (geometry/Unit3.cpp:44-52): h = normalize(q), its basis, and D 2x3 = basis^T * normalize's derivative
+// (Point3.cpp:52-62); D may be null
+GT_HD void unit3_from_point(const double* q, double* h, double* b1, double* b2, double* D) {
+  _Pragma("clang fp contract(off)")
+  const double x2 = q[0] * q[0], y2 = q[1] * q[1], z2 = q[2] * q[2];
+  const double nrm = sqrt(x2 + y2 + z2);
+  h[0] = q[0] / nrm; h[1] = q[1] / nrm; h[2] = q[2] / nrm;
+  unit3_basis(h, b1, b2);
+  if (!D) return;
+  const double xy = q[0] * q[1], xz = q[0] * q[2], yz = q[1] * q[2];
+  const double den = pow(x2 + y2 + z2, 1.5);
+  const double N[9] = {(y2 + z2) / den, -xy / den, -xz / den, -xy / den, (x2 + z2) / den, -yz / den, -xz / den, -yz / den, (x2 + y2) / den};
+  for (int j = 0; j < 3; j++) {
+    D[j] = b1[0] * N[j] + b1[1] * N[3 + j] + b1[2] * N[6 + j];
+    D[3 + j] = b2[0] * N[j] + b2[1] * N[3 + j] + b2[2] * N[6 + j];
+  }
+}
+// Unit3::localCoordinates (geometry/Unit3.cpp:285-303): the tangent vector at p (basis b1, b2 of p) that points to q.  Three branches:
+// the general one, the first-order form at x = 1, and the constant (pi, 0) at x = -1.
+GT_HD void unit3_local(const double* p, const double* b1, const double* b2, const double* q, double* v) {
+  _Pragma("clang fp contract(off)")
+  const double x = p[0] * q[0] + p[1] * q[1] + p[2] * q[2];
+  const double x2 = x * x;
+  const double z = 1 - x2;
+  double y;
+  if (z < 2.220446049250313e-16) {   // std::numeric_limits<double>::epsilon()
+    if (x > 0) y = 1.0 - (x - 1.0) / 3.0;
+    else { v[0] = 3.14159265358979323846; v[1] = 0.0; return; }
+  } else {
+    y = acos(x) / sqrt(z);
+  }
+  const double d[3] = {q[0] - x * p[0], q[1] - x * p[1], q[2] - x * p[2]};
+  v[0] = (b1[0] * y) * d[0] + (b1[1] * y) * d[1] + (b1[2] * y) * d[2];
+  v[1] = (b2[0] * y) * d[0] + (b2[1] * y) * d[1] + (b2[2] * y) * d[2];
 }
 
 // ---- noise models (linear/NoiseModel.cpp) ------------------------------------------------------

@@ -18,6 +18,7 @@
 #endif
 namespace gt {
 namespace {
+static_assert(kSamBearingRange == GTG_SAM_BEARING_RANGE && kSamRange == GTG_SAM_RANGE && kSamBearing == GTG_SAM_BEARING, "factors.h names the sam kinds of the C ABI");
 
 // Smart factors become what the rest of the library already knows: a hidden POINT3 variable per factor behind the caller's
 // variables and one observation per measurement behind the caller's -- a GeneralSFM observation for a camera-type factor
@@ -51,6 +52,8 @@ SmartView::SmartView(const gtg_problem& user) : q(user), p(&user) {
   pose = n_pose > 0;
   if (pose && user.n_stereo > 0)
     throw std::invalid_argument("smart factors: pose-type smart factors together with GenericStereoFactors (three-row records) are not supported");
+  if (pose && user.n_sam > 0)
+    throw std::invalid_argument("smart factors: pose-type smart factors together with bearing / range factors (three-row records) are not supported");
   var_type.assign(user.var_type, user.var_type + user.n_vars); var_type.resize((size_t)user.n_vars + n_smart, GTG_VAR_POINT3);
   // the device addresses a factor's measurements as smart_obs0 + smart_ptr[i] while the expanded observations are appended one
   // after the other: the offsets must start at 0 and be strictly increasing
@@ -227,11 +230,15 @@ void keep_whole_graph_keys(HostIndex& hi, const gtg_problem& p, int n_shards) {
   for (int64_t i = 0; i < p.n_proj; i++) { check_var(p, p.proj_pose[i]); check_var(p, p.proj_point[i]); }
   const int64_t n_stereo = p.n_stereo > 0 && p.stereo_pose && p.stereo_point ? p.n_stereo : 0;   // (the tables are checked by upload_projection)
   for (int64_t i = 0; i < n_stereo; i++) { check_var(p, p.stereo_pose[i]); check_var(p, p.stereo_point[i]); }
+  const int64_t n_sam = p.n_sam > 0 && p.sam_pose && p.sam_point ? p.n_sam : 0;
+  for (int64_t i = 0; i < n_sam; i++) { check_var(p, p.sam_pose[i]); check_var(p, p.sam_point[i]); }
   for (int64_t i = 0; i < p.n_between; i++) { check_var(p, p.between_v1[i]); check_var(p, p.between_v2[i]); }
   hi.all_obs_red_var.assign(p.sfm_cam, p.sfm_cam + p.n_sfm); hi.all_obs_red_var.insert(hi.all_obs_red_var.end(), p.proj_pose, p.proj_pose + p.n_proj);
   hi.all_obs_red_var.insert(hi.all_obs_red_var.end(), p.stereo_pose, p.stereo_pose + n_stereo);
+  hi.all_obs_red_var.insert(hi.all_obs_red_var.end(), p.sam_pose, p.sam_pose + n_sam);
   hi.all_obs_point.assign(p.sfm_point, p.sfm_point + p.n_sfm); hi.all_obs_point.insert(hi.all_obs_point.end(), p.proj_point, p.proj_point + p.n_proj);
   hi.all_obs_point.insert(hi.all_obs_point.end(), p.stereo_point, p.stereo_point + n_stereo);
+  hi.all_obs_point.insert(hi.all_obs_point.end(), p.sam_point, p.sam_point + n_sam);
   hi.all_between_v1.assign(p.between_v1, p.between_v1 + p.n_between); hi.all_between_v2.assign(p.between_v2, p.between_v2 + p.n_between);
 }
 
@@ -308,9 +315,8 @@ void upload_sfm(gtg_context& c, HostIndex& hi, const gtg_problem& p, const std::
 void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, const std::vector<int32_t>& of_obs, const ShardFilter& own) {
   auto& f = c.f;
   std::vector<int32_t> pose, pt, nz, cal, sen; std::vector<double> z;
-  const int64_t n_stereo = p.n_stereo > 0 ? p.n_stereo : 0;
-  f.stereo = n_stereo > 0;
-  const int zdim = f.stereo ? 3 : 2;   // a graph with stereo factors keeps three measurement entries per observation (context.h)
+  const int64_t n_stereo = p.n_stereo > 0 ? p.n_stereo : 0, n_sam = p.n_sam > 0 ? p.n_sam : 0;
+  f.rows3 = n_stereo > 0 || n_sam > 0;   // a three-row graph keeps three measurement entries per camera observation (context.h)
   for (int64_t i = 0; i < p.n_proj; i++) {
     check_var(p, p.proj_pose[i]); check_var(p, p.proj_point[i]); check_noise(p, p.proj_noise[i], 2, "GenericProjectionFactor");
     if (p.proj_calib[i] < 0 || p.proj_calib[i] >= p.n_calib) throw std::invalid_argument("bad calibration index");
@@ -320,13 +326,13 @@ void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, cons
     pose.push_back(p.proj_pose[i]); pt.push_back(p.proj_point[i]); nz.push_back(p.proj_noise[i]);
     cal.push_back(p.proj_calib[i]); sen.push_back(si);
     z.push_back(p.proj_z[2 * i]); z.push_back(p.proj_z[2 * i + 1]);
-    if (f.stereo) z.push_back(0.0);
+    if (f.rows3) z.push_back(0.0);
   }
   f.n_mono = (int64_t)pose.size();
   if (c.smart_pose) upload_smart_tracks(c, p.n_proj, p.proj_point, of_obs, own);   // (their measurements are part of the range above)
   // the stereo factors join the observation range behind the monocular ones: the symbolic analysis, the incidence lists, the E slots,
   // the Schur terms, PCG and the shard filter see more projection observations and nothing else
-  if (f.stereo) {
+  if (n_stereo) {
     if (!p.stereo_pose || !p.stereo_point || !p.stereo_z || !p.stereo_noise || !p.stereo_calib) throw std::invalid_argument("stereo factor tables missing");
     if (!p.calib_baseline) throw std::invalid_argument("GenericStereoFactor: calib_baseline is missing");
   }
@@ -342,7 +348,29 @@ void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, cons
     cal.push_back(p.stereo_calib[i]); sen.push_back(si < 0 ? -1 : si);
     for (int k = 0; k < 3; k++) z.push_back(p.stereo_z[3 * i + k]);
   }
+  f.n_cam = (int64_t)pose.size();
+  // the bearing / range factors (gtsam/sam) join the range behind the stereo factors the same way; they have no calib or sensor entry
+  // and their measurements (a Unit3 and a range) stay in an array of their own, so that proj_z is what it was
+  if (n_sam && (!p.sam_kind || !p.sam_pose || !p.sam_point || !p.sam_z || !p.sam_noise)) throw std::invalid_argument("bearing / range factor tables missing");
+  std::vector<int32_t> sam_kind; std::vector<double> sam_z;
+  for (int64_t i = 0; i < n_sam; i++) {
+    const int kind = p.sam_kind[i];
+    if (kind != GTG_SAM_BEARING_RANGE && kind != GTG_SAM_RANGE && kind != GTG_SAM_BEARING)
+      throw std::invalid_argument("bearing / range factor: unknown sam_kind (GTG_SAM_BEARING_RANGE, GTG_SAM_RANGE or GTG_SAM_BEARING)");
+    const char* what = kind == GTG_SAM_BEARING_RANGE ? "BearingRangeFactor" : kind == GTG_SAM_RANGE ? "RangeFactor" : "BearingFactor";
+    check_var(p, p.sam_pose[i]); check_var(p, p.sam_point[i]);
+    if (p.var_type[p.sam_pose[i]] != GTG_VAR_POSE3 || p.var_type[p.sam_point[i]] != GTG_VAR_POINT3)
+      throw std::invalid_argument(std::string(what) + " keys must be (POSE3, POINT3)");
+    check_noise(p, p.sam_noise[i], sam_rows(kind), what);
+    if (own.n_shards > 1 && !own.owns_landmark(p.sam_point[i])) continue;
+    pose.push_back(p.sam_pose[i]); pt.push_back(p.sam_point[i]); nz.push_back(p.sam_noise[i]);
+    cal.push_back(-1); sen.push_back(-1);
+    sam_kind.push_back(kind);
+    for (int k = 0; k < 4; k++) sam_z.push_back(p.sam_z[4 * i + k]);
+  }
   f.n_proj = (int64_t)pose.size();
+  f.sam = n_sam > 0;
+  if (n_sam) { up(f.sam_kind, sam_kind, c.stream); up(f.sam_z, sam_z, c.stream); } else { f.sam_kind.free(); f.sam_z.free(); }
   up(f.proj_pose, pose, c.stream); up(f.proj_point, pt, c.stream); up(f.proj_noise, nz, c.stream); up(f.proj_calib, cal, c.stream);
   up(f.proj_sensor, sen, c.stream); up(f.proj_z, z, c.stream);
   // device calibration table: 9 per entry, fx fy s u0 v0 k1 k2 p1 p2 (the distortion part zero for a Cal3_S2)
@@ -352,11 +380,11 @@ void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, cons
     if (p.calib_distortion) for (int j = 0; j < 4; j++) calib[kCalibStride * (size_t)k + 5 + j] = p.calib_distortion[4 * (size_t)k + j];
   }
   up(f.calib, calib, c.stream); up(f.sensor, sensor, c.stream);
-  if (f.stereo) {   // the baselines beside the table, so that the table and the kernels of a graph without stereo factors stay as they are
+  if (n_stereo) {   // the baselines beside the table, so that the table and the kernels of a graph without stereo factors stay as they are
     std::vector<double> bl(p.calib_baseline, p.calib_baseline + p.n_calib);
     up(f.calib_baseline, bl, c.stream);
   } else f.calib_baseline.free();
-  f.proj_J.alloc(std::max<size_t>((size_t)(f.stereo ? kStereoRec : kProjRec) * f.n_proj, 1));
+  f.proj_J.alloc(std::max<size_t>((size_t)(f.rows3 ? kStereoRec : kProjRec) * f.n_proj, 1));
   hi.proj_pose = pose; hi.proj_point = pt;
 }
 
@@ -415,9 +443,9 @@ void upload_problem(gtg_context& c, const gtg_problem& user, int shard, int n_sh
   c.shard = shard; c.n_shards = n_shards;
   c.n_smart = user.n_smart > 0 ? user.n_smart : 0; c.n_user_vars = user.n_vars;
   // GeneralSFM records recomputed where they are needed instead of stored (fused.h) -- not with smart factors, whose measurements'
-  // records depend on the factor's triangulation status, and not beside stereo factors, whose three-row records only the
-  // stored-record kernels read
-  c.fused_sfm = GTG_FUSED_SFM != 0 && c.n_smart == 0 && !(user.n_stereo > 0);
+  // records depend on the factor's triangulation status, and not beside stereo or bearing / range factors, whose three-row records
+  // only the stored-record kernels read
+  c.fused_sfm = GTG_FUSED_SFM != 0 && c.n_smart == 0 && !(user.n_stereo > 0) && !(user.n_sam > 0);
   const SmartView view(user);
   const gtg_problem& p = view.problem();
   c.smart_pose = view.pose; c.smart_obs0 = view.pose ? user.n_proj : user.n_sfm;

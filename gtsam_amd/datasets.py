@@ -621,3 +621,130 @@ def smart_pose_scene(name, seed=0, scene=None, params=None):
             w, t = scene[key]
             scene[key] = A.Pose3(A.Rot3(_rodrigues(np.array([w]))[0]), np.array(t))
     return smart_pose_graph(seed=seed, params=prm, **scene)
+
+
+def _noisy_bearing(rng, q, sigma):
+    """The direction of the local point q with a tangent-plane error of `sigma` radians, as a Unit3."""
+    from . import api as A
+    d = q / np.linalg.norm(q)
+    return A.Unit3(d + sigma * rng.normal(size=3))
+
+
+def _add_sam(graph, rng, kind, pose_key, point_key, q, model, bearing_sigma, range_sigma):
+    """One bearing / range factor of `kind` (0 bearing-range, 1 range, 2 bearing) with a noisy measurement of the local point q."""
+    from . import api as A
+    r = float(np.linalg.norm(q)) + range_sigma * rng.normal()
+    if kind == 0:
+        graph.add(A.BearingRangeFactor3D(pose_key, point_key, _noisy_bearing(rng, q, bearing_sigma), r, model))
+    elif kind == 1:
+        graph.add(A.RangeFactor3D(pose_key, point_key, r, model))
+    else:
+        graph.add(A.BearingFactor3D(pose_key, point_key, _noisy_bearing(rng, q, bearing_sigma), model))
+
+
+def sam3d_mixed_graph(n_poses=6, n_points=40, seed=3, bearing_sigma=0.004, range_sigma=0.02):
+    """A small graph that enters every branch of BearingRangeFactor / RangeFactor / BearingFactor <Pose3, Point3> on the device, built
+    through the API mirror: the arc of stereo_mixed_graph with monocular (Cal3_S2) and stereo factors on some landmarks and a
+    bearing / range factor of every kind on all of them; dim-3 / dim-1 / dim-2 Unit, Isotropic, Diagonal and full Gaussian noise, one
+    Robust(Huber) and one Robust(Cauchy); BetweenFactor<Pose3> along the arc and priors.  One more pose, X(n_poses), starts with the
+    identity rotation and a translation of binary fractions, so that the direction it predicts for three more landmarks is exact in
+    floating point: L(n_points) straight along +x with the measured bearing bit-equal to the predicted one (1 - x^2 < eps, x > 0),
+    L(n_points + 1) along +y with the measured bearing exactly opposite (the (pi, 0) branch; a wide noise model: it is an outlier),
+    L(n_points + 2) at (1, 1, 4): two equal smallest components (axis tie).  Graph order: projection, stereo, sam, between, prior.
+    Returns (graph, initial values, {branch name: index among the sam factors})."""
+    from . import api as A
+    rng = np.random.default_rng(seed)
+    ang = np.linspace(-0.5, 0.5, n_poses)
+    centers = np.stack([8 * np.sin(ang), 0.3 * rng.normal(size=n_poses), -8 * np.cos(ang)], 1)
+    R = _rodrigues(np.stack([0.02 * rng.normal(size=n_poses), -ang, 0.02 * rng.normal(size=n_poses)], 1))
+    pts = np.stack([rng.uniform(-2, 2, n_points), rng.uniform(-1.5, 1.5, n_points), rng.uniform(-2, 2, n_points)], 1)
+    t_id = np.array([0.5, -0.25, -9.0])                       # the identity-rotation pose
+    special0 = t_id + np.array([[2.0, 0.0, 0.0], [0.0, 3.0, 0.0], [1.0, 1.0, 4.0]])     # initial values of the three branch landmarks
+    special = special0 + rng.normal(0, 0.01, (3, 3))          # where they are
+    R = np.concatenate([R, np.eye(3)[None]]); centers = np.concatenate([centers, t_id[None]])
+    pts = np.concatenate([pts, special])
+    X, L = A.symbol_shorthand.X, A.symbol_shorthand.L
+    nm = A.noiseModel
+    K1 = A.Cal3_S2Stereo(720.0, 715.0, 0.0, 600.0, 170.0, 0.54)
+    Km = A.Cal3_S2(520.0, 515.0, 0.3, 320.0, 240.0)
+    R3 = np.array([[90.0, 12.0, -6.0], [0.0, 110.0, 9.0], [0.0, 0.0, 30.0]]); R2 = np.array([[120.0, 15.0], [0.0, 95.0]])
+    models = {0: [nm.Unit.Create(3), nm.Isotropic.Sigma(3, 0.02), nm.Diagonal.Sigmas([0.008, 0.01, 0.04]), nm.Gaussian.SqrtInformation(R3),
+                  nm.Robust.Create(nm.mEstimator.Huber.Create(1.345), nm.Diagonal.Sigmas([0.006, 0.006, 0.03]))],
+              1: [nm.Unit.Create(1), nm.Isotropic.Sigma(1, 0.03), nm.Diagonal.Sigmas([0.05], False), nm.Gaussian.SqrtInformation([[25.0]], False),
+                  nm.Robust.Create(nm.mEstimator.Cauchy.Create(0.8), nm.Isotropic.Sigma(1, 0.03))],
+              2: [nm.Unit.Create(2), nm.Isotropic.Sigma(2, 0.006), nm.Diagonal.Sigmas([0.005, 0.009]), nm.Gaussian.SqrtInformation(R2)]}
+    m2, m3 = nm.Isotropic.Sigma(2, 1.5), nm.Isotropic.Sigma(3, 1.2)
+    graph, initial = A.NonlinearFactorGraph(), A.Values()
+    for i in range(4):                                        # monocular factors on the first ten landmarks
+        for j in range(10):
+            q = R[i].T @ (pts[j] - centers[i]); u, v = q[0] / q[2], q[1] / q[2]
+            z = np.array([Km.v[0] * u + Km.v[2] * v + Km.v[3], Km.v[1] * v + Km.v[4]]) + rng.normal(0, 1.0, 2)
+            graph.add(A.GenericProjectionFactorCal3_S2(z, m2, X(i), L(j), Km))
+    for i in range(n_poses):                                  # stereo factors on landmarks 5..19
+        for j in range(5, 20):
+            q = R[i].T @ (pts[j] - centers[i]); fx, fy, _, u0, v0, b = K1.v
+            z = np.array([u0 + fx * q[0] / q[2], u0 + fx * (q[0] - b) / q[2], v0 + fy * q[1] / q[2]]) + rng.normal(0, 0.7, 3)
+            graph.add(A.GenericStereoFactor3D(z, m3, X(i), L(j), K1))
+    k, count = 0, {0: 0, 1: 0, 2: 0}
+    for i in range(n_poses + 1):                              # a bearing / range factor of every kind, interleaved
+        for j in range(n_points + 3):
+            if i == n_poses and j >= n_points:
+                continue                                      # (the identity pose's view of the branch landmarks: below)
+            kind = k % 3
+            _add_sam(graph, rng, kind, X(i), L(j), R[i].T @ (pts[j] - centers[i]), models[kind][count[kind] % len(models[kind])], bearing_sigma, range_sigma)
+            count[kind] += 1; k += 1
+    branch = {"same": k, "opposite": k + 1, "tie": k + 2}
+    graph.add(A.BearingRangeFactor3D(X(n_poses), L(n_points), A.Unit3(1.0, 0.0, 0.0), 2.0 + range_sigma * rng.normal(), models[0][2]))
+    graph.add(A.BearingFactor3D(X(n_poses), L(n_points + 1), A.Unit3(0.0, -1.0, 0.0), nm.Isotropic.Sigma(2, 40.0)))
+    graph.add(A.BearingRangeFactor3D(X(n_poses), L(n_points + 2), _noisy_bearing(rng, special[2] - t_id, bearing_sigma),
+                                     float(np.linalg.norm(special[2] - t_id)) + range_sigma * rng.normal(), models[0][3]))
+    n6 = nm.Diagonal.Sigmas([0.01] * 3 + [0.05] * 3); n6b = nm.Diagonal.Sigmas([0.02, 0.02, 0.03, 0.1, 0.1, 0.15])
+    for i in range(n_poses):
+        Rz = R[i].T @ R[i + 1]; tz = R[i].T @ (centers[i + 1] - centers[i])
+        graph.add(A.BetweenFactorPose3(X(i), X(i + 1), A.Pose3(A.Rot3(Rz @ _rodrigues(rng.normal(0, 0.005, (1, 3)))[0]), tz + rng.normal(0, 0.02, 3)), n6b))
+    graph.addPriorPose3(X(0), A.Pose3(A.Rot3(R[0]), centers[0]), n6)
+    graph.addPriorPose3(X(n_poses), A.Pose3(A.Rot3(np.eye(3)), t_id), n6)
+    graph.addPriorPoint3(L(0), pts[0], nm.Isotropic.Sigma(3, 0.1))
+    dR = _rodrigues(rng.normal(0, 0.01, (n_poses, 3)))
+    for i in range(n_poses):
+        initial.insert(X(i), A.Pose3(A.Rot3(R[i] @ dR[i]), centers[i] + rng.normal(0, 0.05, 3)))
+    initial.insert(X(n_poses), A.Pose3(A.Rot3(np.eye(3)), t_id))
+    for j in range(n_points):
+        initial.insert(L(j), pts[j] + rng.normal(0, 0.05, 3))
+    for j in range(3):
+        initial.insert(L(n_points + j), special0[j])
+    return graph, initial, branch
+
+
+def landmark_slam3d_graph(n_poses=40, n_points=300, seed=11, views=10, bearing_sigma=0.005, range_sigma=0.03):
+    """3-D landmark SLAM without a camera: a robot on a rising circle with odometry (BetweenFactorPose3) and a prior on its first
+    pose; every landmark is seen from its `views` nearest poses by a BearingRangeFactor3D, a RangeFactor3D or a BearingFactor3D in
+    turn (the first view of every landmark is a bearing-range one).  No calibration, no pixel: the graph of a lidar / sonar / UWB front
+    end.  Fixed seed.  Returns (graph, initial values)."""
+    from . import api as A
+    rng = np.random.default_rng(seed)
+    X, L = A.symbol_shorthand.X, A.symbol_shorthand.L
+    nm = A.noiseModel
+    th = np.linspace(0.0, 1.75 * np.pi, n_poses)
+    centers = np.stack([12 * np.cos(th), 12 * np.sin(th), 0.05 * np.arange(n_poses)], 1)
+    R = _rodrigues(np.stack([0.03 * rng.normal(size=n_poses), 0.03 * rng.normal(size=n_poses), th + np.pi / 2], 1))
+    rad = rng.uniform(6.0, 18.0, n_points); phi = rng.uniform(0.0, 1.75 * np.pi, n_points)
+    pts = np.stack([rad * np.cos(phi), rad * np.sin(phi), rng.uniform(-2.0, 4.0, n_points)], 1)
+    models = {0: nm.Diagonal.Sigmas([bearing_sigma, bearing_sigma, range_sigma]), 1: nm.Isotropic.Sigma(1, range_sigma),
+              2: nm.Isotropic.Sigma(2, bearing_sigma)}
+    odo = nm.Diagonal.Sigmas([0.01, 0.01, 0.01, 0.05, 0.05, 0.05])
+    graph, initial = A.NonlinearFactorGraph(), A.Values()
+    for j in range(n_points):
+        near = np.argsort(np.linalg.norm(centers - pts[j], axis=1))[:views]
+        for k, i in enumerate(sorted(int(i) for i in near)):
+            _add_sam(graph, rng, k % 3, X(i), L(j), R[i].T @ (pts[j] - centers[i]), models[k % 3], bearing_sigma, range_sigma)
+    for i in range(n_poses - 1):
+        Rz = R[i].T @ R[i + 1]; tz = R[i].T @ (centers[i + 1] - centers[i])
+        graph.add(A.BetweenFactorPose3(X(i), X(i + 1), A.Pose3(A.Rot3(Rz @ _rodrigues(rng.normal(0, 0.01, (1, 3)))[0]), tz + rng.normal(0, 0.05, 3)), odo))
+    graph.addPriorPose3(X(0), A.Pose3(A.Rot3(R[0]), centers[0]), nm.Diagonal.Sigmas([0.01] * 3 + [0.02] * 3))
+    dR = _rodrigues(rng.normal(0, 0.02, (n_poses, 3)))
+    for i in range(n_poses):
+        initial.insert(X(i), A.Pose3(A.Rot3(R[i] @ dR[i]), centers[i] + rng.normal(0, 0.1, 3)))
+    for j in range(n_points):
+        initial.insert(L(j), pts[j] + rng.normal(0, 0.2, 3))
+    return graph, initial

@@ -21,6 +21,9 @@
 #include <gtsam/slam/SmartProjectionFactor.h>
 #include <gtsam/slam/SmartProjectionPoseFactor.h>
 #include <gtsam/slam/StereoFactor.h>
+#include <gtsam/sam/BearingFactor.h>
+#include <gtsam/sam/BearingRangeFactor.h>
+#include <gtsam/sam/RangeFactor.h>
 
 #include <gtsam/config.h>
 
@@ -71,6 +74,9 @@ typedef GeneralSFMFactor<SfmCamera, Point3> SfmFactor;
 typedef GenericProjectionFactor<Pose3, Point3, Cal3_S2> ProjFactor;
 typedef GenericProjectionFactor<Pose3, Point3, Cal3DS2> ProjFactorDS2;
 typedef GenericStereoFactor<Pose3, Point3> StereoFactor;
+typedef BearingRangeFactor<Pose3, Point3> SamBearingRangeFactor;   // gtsam/sam: wrapped as BearingRangeFactor3D, RangeFactor3D, BearingFactor3D
+typedef RangeFactor<Pose3, Point3> SamRangeFactor;
+typedef BearingFactor<Pose3, Point3> SamBearingFactor;
 typedef SmartProjectionFactor<SfmCamera> SmartFactor;   // the factor of timing/timeSFMBALsmart.cpp
 // The smart factor keeps its noise model and its parameters protected and has no accessor for them; a class derived from it may
 // name them, and the pointers to member it forms are ordinary pointers to members of the factor (a maintainer binding this into
@@ -170,13 +176,14 @@ void unpack(int32_t t, const double* p, Value& v) {
 }
 // ---- Jacobian records (gtg_get_jacobians): one whitened [A1 | A2 | b] per factor, row-major blocks at fixed offsets; the record's width follows
 // the factor type, the block sizes the factor's first variable (Pose2: 3x3 blocks inside the record of the Pose3 factor)
-const int64_t kRecordWidth[5] = {26, 20, 78, 90, 30};   // by GTG_FAC_*
+const int64_t kRecordWidth[6] = {26, 20, 78, 90, 30, 30};   // by GTG_FAC_*
 struct RecordLayout { int rows, nblk, boff[2], bcols[2], rhs; int64_t width; };
 template <class F> RecordLayout recordLayout(int32_t fac, F&& firstVarType) {   // firstVarType(): GTG_VAR_* of the factor's first variable, asked only where the layout depends on it
   const int64_t w = kRecordWidth[fac];
   if (fac == GTG_FAC_GENERAL_SFM) return {2, 2, {0, 18}, {tangentDim(GTG_VAR_SFM_CAMERA), 3}, 24, w};
   if (fac == GTG_FAC_PROJECTION) return {2, 2, {0, 12}, {tangentDim(GTG_VAR_POSE3), 3}, 18, w};
   if (fac == GTG_FAC_STEREO) return {3, 2, {0, 18}, {tangentDim(GTG_VAR_POSE3), 3}, 27, w};
+  if (fac == GTG_FAC_SAM) return {3, 2, {0, 18}, {tangentDim(GTG_VAR_POSE3), 3}, 27, w};   // (rows: the caller puts the kind's 3, 1 or 2 -- Impl::layoutOf)
   const int d = tangentDim(firstVarType());
   if (fac == GTG_FAC_BETWEEN_POSE3) return {d, 2, {0, 36}, {d, d}, 72, w};
   return {d, 1, {0, 0}, {d, 0}, 81, w};
@@ -184,14 +191,14 @@ template <class F> RecordLayout recordLayout(int32_t fac, F&& firstVarType) {   
 typedef std::vector<std::pair<int32_t, int64_t>> FactorMap;   // factor of graph_ -> (GTG_FAC_*, index in that type's table); (-1, 0): null; (-2, i): smart factor i
 // The device's current records, one buffer per GTG_FAC_* (null and smart factors have none: a smart factor's linearisation is a Hessian factor the device never forms)
 struct Records {
-  std::vector<double> rec[5];
+  std::vector<double> rec[6];
   const double* of(const std::pair<int32_t, int64_t>& tf) const { return rec[tf.first].data() + tf.second * kRecordWidth[tf.first]; }
 };
 Records fetchRecords(gtg_handle h, const FactorMap& fac_map) {
   Records out;
-  int64_t count[5] = {0, 0, 0, 0, 0};
+  int64_t count[6] = {0, 0, 0, 0, 0, 0};
   for (const auto& tf : fac_map) if (tf.first >= 0) count[tf.first]++;
-  for (int t = 0; t < 5; t++) {
+  for (int t = 0; t < 6; t++) {
     if (!count[t]) continue;
     out.rec[t].resize((size_t)(count[t] * kRecordWidth[t]));
     check(gtg_get_jacobians(h, t, out.rec[t].data(), (int64_t)out.rec[t].size()), "gtg_get_jacobians");
@@ -259,7 +266,12 @@ struct GpuLevenbergMarquardtOptimizer::Impl {
   std::chrono::high_resolution_clock::time_point start = std::chrono::high_resolution_clock::now();   // logFile's seconds column
   ~Impl() { if (h) gtg_destroy(h); }
   void takeScalars(const State& s) { error = s.error; lambda = s.lambda; factor = s.currentFactor; iterations = s.iterations; inner = s.totalNumberInnerIterations; }
-  RecordLayout layoutOf(const std::pair<int32_t, int64_t>& tf, Key first) const { return recordLayout(tf.first, [&] { return var_type[idOf(keys, first)]; }); }
+  std::vector<int32_t> sam_kind;         // GTG_SAM_* by row of the sam table: a bearing / range record has its kind's 3, 1 or 2 rows
+  RecordLayout layoutOf(const std::pair<int32_t, int64_t>& tf, Key first) const {
+    RecordLayout lay = recordLayout(tf.first, [&] { return var_type[idOf(keys, first)]; });
+    if (tf.first == GTG_FAC_SAM) lay.rows = sam_kind[(size_t)tf.second] == GTG_SAM_BEARING_RANGE ? 3 : sam_kind[(size_t)tf.second] == GTG_SAM_RANGE ? 1 : 2;
+    return lay;
+  }
 };
 
 namespace {
@@ -360,13 +372,13 @@ namespace {
 // calibrations as (run length, object) -- rows of the shared tables are handed out afterwards, sequentially, in first-occurrence
 // order, so that the tables are those of a single-threaded pass whatever the thread count.
 struct Extract {
-  std::vector<int32_t> sfm_cam, sfm_pt, pj_pose, pj_pt, pj_sen, st_pose, st_pt, st_sen, bt_1, bt_2, pr_var, sm_cam;
-  std::vector<double> sfm_z, pj_z, st_z, sensor, bt_z, pr_data, sm_z, sm_prm;
+  std::vector<int32_t> sfm_cam, sfm_pt, pj_pose, pj_pt, pj_sen, st_pose, st_pt, st_sen, sam_kind, sam_pose, sam_pt, bt_1, bt_2, pr_var, sm_cam;
+  std::vector<double> sfm_z, pj_z, st_z, sam_z, sensor, bt_z, pr_data, sm_z, sm_prm;
   std::vector<int64_t> pr_off, sm_ptr;
   FactorMap fac_map;                                                        // (type, index in THIS chunk's table of that type)
   typedef std::vector<std::pair<int64_t, SharedNoiseModel>> Runs;
-  Runs sfm_nz, pj_nz, st_nz, bt_nz, pr_nz, sm_nz;
-  std::vector<int32_t> bt_dim, pr_dim;                                      // expected noise dimension per between / prior factor
+  Runs sfm_nz, pj_nz, st_nz, sam_nz, bt_nz, pr_nz, sm_nz;
+  std::vector<int32_t> bt_dim, pr_dim, sam_dim;                             // expected noise dimension per between / prior / sam factor
   std::vector<std::pair<const void*, int>> pj_cal;                          // calibration object per projection factor, 1 = Cal3DS2
   std::vector<const Cal3_S2Stereo*> st_cal;                                 // calibration object per stereo factor
   std::vector<const Cal3_S2*> sm_cal;                                       // per smart factor: the shared K of a pose-type factor, null for a camera-type one
@@ -404,6 +416,16 @@ void addStereo(Extract& x, const StereoFactor& p, const std::vector<Key>& keys) 
   x.st_cal.push_back(p.calibration().get());
   if (p.body_P_sensor()) { x.st_sen.push_back((int32_t)(x.sensor.size() / 12)); packPose(*p.body_P_sensor(), Extract::grow(x.sensor, 12)); x.sensor_shared.push_back(0); }
   else x.st_sen.push_back(-1);
+}
+// BearingRangeFactor / RangeFactor / BearingFactor <Pose3, Point3> (gtsam/sam): one row of the sam table; bearing: the measured Unit3 or
+// null, range: the measured range or null.  No calibration, no sensor.
+void addSam(Extract& x, int32_t kind, Key pose, Key point, const Unit3* bearing, const double* range, const SharedNoiseModel& nm, const std::vector<Key>& keys) {
+  x.fac_map.emplace_back(GTG_FAC_SAM, (int64_t)x.sam_pose.size());
+  x.sam_kind.push_back(kind); x.sam_pose.push_back(idOf(keys, pose)); x.sam_pt.push_back(idOf(keys, point));
+  double* z = Extract::grow(x.sam_z, 4);
+  if (bearing) { const Vector3 u = bearing->unitVector(); z[0] = u(0); z[1] = u(1); z[2] = u(2); }
+  if (range) z[3] = *range;
+  Extract::run(x.sam_nz, nm); x.sam_dim.push_back(kind == GTG_SAM_BEARING_RANGE ? 3 : kind == GTG_SAM_RANGE ? 1 : 2);
 }
 // the rows every smart factor has, whatever its camera type: parameters, noise model, keys and measurements
 template <class FACTOR>
@@ -459,6 +481,9 @@ void addFactor(Extract& x, const NonlinearFactor* f, const std::vector<Key>& key
   else if (auto p = dynamic_cast<const ProjFactor*>(f)) addProjection(x, *p, keys);
   else if (auto pd = dynamic_cast<const ProjFactorDS2*>(f)) addProjection(x, *pd, keys);
   else if (auto st = dynamic_cast<const StereoFactor*>(f)) addStereo(x, *st, keys);
+  else if (auto br = dynamic_cast<const SamBearingRangeFactor*>(f)) { const Unit3 u = br->measured().bearing(); const double r = br->measured().range(); addSam(x, GTG_SAM_BEARING_RANGE, br->keys()[0], br->keys()[1], &u, &r, br->noiseModel(), keys); }
+  else if (auto rf = dynamic_cast<const SamRangeFactor*>(f)) { const double r = rf->measured(); addSam(x, GTG_SAM_RANGE, rf->keys()[0], rf->keys()[1], nullptr, &r, rf->noiseModel(), keys); }
+  else if (auto bf = dynamic_cast<const SamBearingFactor*>(f)) addSam(x, GTG_SAM_BEARING, bf->keys()[0], bf->keys()[1], &bf->measured(), nullptr, bf->noiseModel(), keys);
   else if (auto sf = dynamic_cast<const SmartFactor*>(f)) addSmart(x, *sf, keys);
   else if (auto sp = dynamic_cast<const SmartPoseFactor*>(f)) addSmartPose(x, *sp, keys);
   else if (auto bb = dynamic_cast<const BetweenFactor<Pose3>*>(f)) addBetween(x, *bb, keys);
@@ -469,7 +494,7 @@ void addFactor(Extract& x, const NonlinearFactor* f, const std::vector<Key>& key
   else if (auto p3 = dynamic_cast<const PriorFactor<Point3>*>(f)) addPrior(x, *p3, keys);
   else throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: factor type outside the GPU hot path "   // (anything else is a hard error)
                                    "(supported: GeneralSFMFactor<SfmCamera,Point3>, GenericProjectionFactor<Pose3,Point3,Cal3_S2|Cal3DS2>, "
-                                   "GenericStereoFactor<Pose3,Point3>, SmartProjectionFactor<SfmCamera>, SmartProjectionPoseFactor<Cal3_S2>, BetweenFactor<Pose3|Pose2>, PriorFactor<Pose3|Pose2|SfmCamera|Point3>)");
+                                   "GenericStereoFactor<Pose3,Point3>, BearingRangeFactor|RangeFactor|BearingFactor<Pose3,Point3>, SmartProjectionFactor<SfmCamera>, SmartProjectionPoseFactor<Cal3_S2>, BetweenFactor<Pose3|Pose2>, PriorFactor<Pose3|Pose2|SfmCamera|Point3>)");
 }
 // The factors [b, e) of `graph` into x, each pointer also copied into `graphCopy`; the chunk stops at its first offending factor and keeps what that threw.
 void extractChunk(Extract& x, const NonlinearFactorGraph& graph, NonlinearFactorGraph& graphCopy, const std::vector<Key>& keys, size_t b, size_t e) {
@@ -498,13 +523,13 @@ template <class T> struct Raw {
   T* data() const { return p.get(); } size_t size() const { return n; }
 };
 typedef Raw<int32_t> RawI; typedef Raw<double> RawD;
-struct Place { int64_t o_sfm, o_pj, o_st, o_bt, o_pr, o_sm; std::vector<std::pair<int64_t, int32_t>> sfm_rows; };   // per chunk: offsets of its tables, (count, noise row) of its GeneralSFM runs
+struct Place { int64_t o_sfm, o_pj, o_st, o_sam, o_bt, o_pr, o_sm; std::vector<std::pair<int64_t, int32_t>> sfm_rows; };   // per chunk: offsets of its tables, (count, noise row) of its GeneralSFM runs
 struct HostProblem {
   NoiseTable nt;
   RawI sfm_cam, sfm_pt, sfm_nz;
   RawD sfm_z;
-  std::vector<int32_t> pj_pose, pj_pt, pj_nz, pj_cal, pj_sen, st_pose, st_pt, st_nz, st_cal, st_sen, bt_1, bt_2, bt_nz, pr_var, pr_nz, sm_cam, sm_nz, sm_cal, sm_sen;
-  std::vector<double> pj_z, st_z, calib, sensor, bt_z, pr_data, sm_z, sm_prm;
+  std::vector<int32_t> pj_pose, pj_pt, pj_nz, pj_cal, pj_sen, st_pose, st_pt, st_nz, st_cal, st_sen, sam_kind, sam_pose, sam_pt, sam_nz, bt_1, bt_2, bt_nz, pr_var, pr_nz, sm_cam, sm_nz, sm_cal, sm_sen;
+  std::vector<double> pj_z, st_z, sam_z, calib, sensor, bt_z, pr_data, sm_z, sm_prm;
   std::vector<int64_t> pr_off, sm_ptr{0};    // (smart factors: one track each)
   bool any_smart_pose = false;               // a SmartProjectionPoseFactor: the smart_calib / smart_sensor tables go to the library
   std::map<std::array<double, 12>, int32_t> shared_sensor;   // the body_P_sensor of smart factors -> row of the sensor table
@@ -544,6 +569,8 @@ struct HostProblem {
     pb.n_stereo = (int64_t)st_pose.size(); pb.stereo_pose = st_pose.data(); pb.stereo_point = st_pt.data(); pb.stereo_z = st_z.data();
     pb.stereo_noise = st_nz.data(); pb.stereo_calib = st_cal.data(); pb.stereo_sensor = st_sen.data();
     pb.calib_baseline = pb.n_stereo ? calib_base.data() : nullptr;
+    pb.n_sam = (int64_t)sam_pose.size(); pb.sam_kind = sam_kind.data(); pb.sam_pose = sam_pose.data(); pb.sam_point = sam_pt.data();
+    pb.sam_z = sam_z.data(); pb.sam_noise = sam_nz.data();
     pb.n_between = (int64_t)bt_1.size(); pb.between_v1 = bt_1.data(); pb.between_v2 = bt_2.data(); pb.between_z = bt_z.data(); pb.between_noise = bt_nz.data();
     pb.n_smart = (int64_t)sm_nz.size(); pb.smart_ptr = sm_ptr.data(); pb.smart_cam = sm_cam.data(); pb.smart_z = sm_z.data();
     pb.smart_noise = sm_nz.data(); pb.smart_params = sm_prm.data();
@@ -656,7 +683,7 @@ HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap
       sen_row[r] = (int32_t)(hp.sensor.size() / 12);
       hp.sensor.insert(hp.sensor.end(), sp, sp + 12);
     }
-    place[pi].o_sfm = o_sfm_next; place[pi].o_pj = (int64_t)hp.pj_pose.size(); place[pi].o_st = (int64_t)hp.st_pose.size(); place[pi].o_bt = (int64_t)hp.bt_1.size();
+    place[pi].o_sfm = o_sfm_next; place[pi].o_pj = (int64_t)hp.pj_pose.size(); place[pi].o_st = (int64_t)hp.st_pose.size(); place[pi].o_sam = (int64_t)hp.sam_pose.size(); place[pi].o_bt = (int64_t)hp.bt_1.size();
     place[pi].o_pr = (int64_t)hp.pr_var.size(); place[pi].o_sm = (int64_t)hp.sm_nz.size();
     o_sfm_next += (int64_t)x.sfm_cam.size();
     for (const auto& r : x.sfm_nz) place[pi].sfm_rows.emplace_back(r.first, hp.nt.add(r.second, 2));
@@ -668,6 +695,8 @@ HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap
     rows3(hp.st_nz, x.st_nz);
     for (int32_t sidx : x.st_sen) hp.st_sen.push_back(sidx < 0 ? -1 : sen_row[(size_t)sidx]);
     for (const Cal3_S2Stereo* K : x.st_cal) hp.st_cal.push_back(hp.stereoCalibRow(K));
+    cat(hp.sam_kind, x.sam_kind); cat(hp.sam_pose, x.sam_pose); cat(hp.sam_pt, x.sam_pt); cat(hp.sam_z, x.sam_z);
+    rows(hp.sam_nz, x.sam_nz, &x.sam_dim);
     cat(hp.bt_1, x.bt_1); cat(hp.bt_2, x.bt_2); cat(hp.bt_z, x.bt_z);
     rows(hp.bt_nz, x.bt_nz, &x.bt_dim);
     cat(hp.pr_var, x.pr_var); cat(hp.pr_data, x.pr_data);
@@ -692,7 +721,7 @@ HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap
     }
     auto* fm_out = fac_map->data() + cut(nfac, part.size(), pi);     // (the chunk's factors: the range extractFactors gave it)
     for (const auto& fm : x.fac_map)
-      *fm_out++ = {fm.first, fm.second + (fm.first == GTG_FAC_GENERAL_SFM ? pl.o_sfm : fm.first == GTG_FAC_PROJECTION ? pl.o_pj : fm.first == GTG_FAC_STEREO ? pl.o_st :
+      *fm_out++ = {fm.first, fm.second + (fm.first == GTG_FAC_GENERAL_SFM ? pl.o_sfm : fm.first == GTG_FAC_PROJECTION ? pl.o_pj : fm.first == GTG_FAC_STEREO ? pl.o_st : fm.first == GTG_FAC_SAM ? pl.o_sam :
                                            fm.first == GTG_FAC_BETWEEN_POSE3 ? pl.o_bt : fm.first == GTG_FAC_PRIOR ? pl.o_pr : fm.first == -2 ? pl.o_sm : 0)};
   });
   return hp;
@@ -748,6 +777,7 @@ void GpuLevenbergMarquardtOptimizer::init(const NonlinearFactorGraph& graph, con
   const HostProblem hp = mergeTables(part, graph.size(), &m.fac_map);
   lap("factors: merge, noise / calibration tables");
   const gtg_problem pb = hp.view(m.var_type);
+  m.sam_kind = hp.sam_kind;
   if (shards.n_shards < 1 || shards.shard < 0 || shards.shard >= shards.n_shards) throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: bad ShardSpec");
   if (shards.n_shards > 1 && !shards.allreduce) throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: n_shards > 1 needs an all-reduce callback");
   for (auto& t : packers) t.join();

@@ -123,7 +123,7 @@ def _check(rc, what):
 class DeviceGraph:
     """One factor graph resident on one MI355X (one handle of the C ABI)."""
 
-    JAC_ROW = {0: 26, 1: 20, 2: 78, 3: 90, 4: 30}
+    JAC_ROW = {0: 26, 1: 20, 2: 78, 3: 90, 4: 30, 5: 30}
 
     def __init__(self, problem: Problem, device: int = 0, shard: int = 0, n_shards: int = 1,
                  reduced_ordering=None, allreduce=None):
@@ -190,7 +190,7 @@ class DeviceGraph:
         return out
 
     def jacobians(self, ftype):
-        n = {0: self.problem.n_sfm, 1: self.problem.n_proj, 2: self.problem.n_between, 3: self.problem.n_prior, 4: self.problem.n_stereo}[ftype]
+        n = {0: self.problem.n_sfm, 1: self.problem.n_proj, 2: self.problem.n_between, 3: self.problem.n_prior, 4: self.problem.n_stereo, 5: self.problem.n_sam}[ftype]
         out = np.empty((n, self.JAC_ROW[ftype]), np.float64)
         _check(self.lib.gtg_get_jacobians(self.h, ftype, out.ctypes.data, out.size), "gtg_get_jacobians")
         return out

@@ -14,7 +14,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 VAR_POSE3, VAR_SFM_CAMERA, VAR_POINT3, VAR_POSE2 = 0, 1, 2, 3
-FAC_GENERAL_SFM, FAC_PROJECTION, FAC_BETWEEN_POSE3, FAC_PRIOR, FAC_STEREO = 0, 1, 2, 3, 4
+FAC_GENERAL_SFM, FAC_PROJECTION, FAC_BETWEEN_POSE3, FAC_PRIOR, FAC_STEREO, FAC_SAM = 0, 1, 2, 3, 4, 5
+SAM_BEARING_RANGE, SAM_RANGE, SAM_BEARING = 0, 1, 2
 NOISE_UNIT, NOISE_ISOTROPIC, NOISE_DIAGONAL, NOISE_GAUSSIAN = 0, 1, 2, 3
 ROBUST_NONE, ROBUST_FAIR, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY, ROBUST_WELSCH, ROBUST_GEMANMCCLURE, ROBUST_DCS, ROBUST_L2WITHDEADZONE = range(9)
 
@@ -43,6 +44,7 @@ class gtg_problem(C.Structure):
         ("n_stereo", C.c_int64), ("stereo_pose", _i32p), ("stereo_point", _i32p), ("stereo_z", _f64p), ("stereo_noise", _i32p),
         ("stereo_calib", _i32p), ("stereo_sensor", _i32p), ("calib_baseline", _f64p),
         ("smart_calib", _i32p), ("smart_sensor", _i32p),
+        ("n_sam", C.c_int64), ("sam_kind", _i32p), ("sam_pose", _i32p), ("sam_point", _i32p), ("sam_z", _f64p), ("sam_noise", _i32p),
     ]
 
 
@@ -90,6 +92,13 @@ class Problem:
     stereo_calib: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     stereo_sensor: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     calib_baseline: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float64))   # [n_calib] or empty (no stereo factors)
+    # BearingRangeFactor / RangeFactor / BearingFactor <Pose3, Point3> (gtsam/sam): sam_kind SAM_*, sam_z 4 per factor = the measured
+    # Unit3's three doubles, then the range (the entries a kind does not use are 0)
+    sam_kind: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    sam_pose: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    sam_point: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    sam_z: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float64))
+    sam_noise: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     sensor: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float64))
     between_v1: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     between_v2: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
@@ -114,7 +123,9 @@ class Problem:
                          ("prior_data", np.float64), ("prior_noise", np.int32),
                          ("stereo_pose", np.int32), ("stereo_point", np.int32), ("stereo_z", np.float64),
                          ("stereo_noise", np.int32), ("stereo_calib", np.int32), ("stereo_sensor", np.int32),
-                         ("calib_baseline", np.float64), ("smart_calib", np.int32), ("smart_sensor", np.int32)):
+                         ("calib_baseline", np.float64), ("smart_calib", np.int32), ("smart_sensor", np.int32),
+                         ("sam_kind", np.int32), ("sam_pose", np.int32), ("sam_point", np.int32), ("sam_z", np.float64),
+                         ("sam_noise", np.int32)):
             setattr(self, name, _a(getattr(self, name), dt))
 
     # ---- sizes -------------------------------------------------------------------------------
@@ -126,6 +137,8 @@ class Problem:
     def n_proj(self): return int(self.proj_pose.size)
     @property
     def n_stereo(self): return int(self.stereo_pose.size)
+    @property
+    def n_sam(self): return int(self.sam_pose.size)
     @property
     def n_between(self): return int(self.between_v1.size)
     @property
@@ -243,6 +256,14 @@ class Problem:
         p.stereo_calib = ptr(self.stereo_calib, C.c_int32)
         p.stereo_sensor = ptr(self.stereo_sensor, C.c_int32)
         p.calib_baseline = ptr(self.calib_baseline, C.c_double)
+        p.n_sam = self.n_sam
+        if self.sam_z.size != 4 * self.n_sam or any(a.size != self.n_sam for a in (self.sam_kind, self.sam_point, self.sam_noise)):
+            raise ValueError("inconsistent bearing / range factor tables (sam_z holds 4 doubles per factor)")
+        p.sam_kind = ptr(self.sam_kind, C.c_int32)
+        p.sam_pose = ptr(self.sam_pose, C.c_int32)
+        p.sam_point = ptr(self.sam_point, C.c_int32)
+        p.sam_z = ptr(self.sam_z, C.c_double)
+        p.sam_noise = ptr(self.sam_noise, C.c_int32)
         p._keep = keep
         return p
 
@@ -271,6 +292,23 @@ class Problem:
             pad = lambda a: np.concatenate([a, np.full(n - a.size, -1, np.int32)])
             self.smart_calib = np.append(pad(self.smart_calib), np.int32(calib))
             self.smart_sensor = np.append(pad(self.smart_sensor), np.int32(sensor))
+
+    # ---- bearing / range factors ---------------------------------------------------------------
+    def add_sam(self, kind: int, pose: int, point: int, noise_idx: int, bearing=None, range_=None):
+        """One BearingRangeFactor (SAM_BEARING_RANGE: bearing and range_), RangeFactor (SAM_RANGE: range_) or BearingFactor
+        (SAM_BEARING: bearing) <Pose3, Point3>.  bearing: the measured Unit3's three doubles (a unit vector, stored as given)."""
+        if kind not in (SAM_BEARING_RANGE, SAM_RANGE, SAM_BEARING):
+            raise ValueError("unknown sam kind")
+        if (bearing is None) != (kind == SAM_RANGE) or (range_ is None) != (kind == SAM_BEARING):
+            raise ValueError("a bearing-range factor takes a bearing and a range, a range factor a range, a bearing factor a bearing")
+        z = np.zeros(4)
+        if bearing is not None:
+            z[:3] = _a(bearing, np.float64)
+        if range_ is not None:
+            z[3] = float(range_)
+        self.sam_kind = np.append(self.sam_kind, np.int32(kind)); self.sam_pose = np.append(self.sam_pose, np.int32(pose))
+        self.sam_point = np.append(self.sam_point, np.int32(point)); self.sam_noise = np.append(self.sam_noise, np.int32(noise_idx))
+        self.sam_z = np.concatenate([self.sam_z, z])
 
     # ---- priors ------------------------------------------------------------------------------
     def add_prior(self, var: int, value, noise_idx: int):

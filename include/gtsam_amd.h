@@ -46,12 +46,21 @@ enum { GTG_FAC_GENERAL_SFM = 0,   /* GeneralSFMFactor<PinholeCamera<Cal3Bundler>
        GTG_FAC_BETWEEN_POSE3 = 2, /* BetweenFactor<Pose3>, or BetweenFactor<Pose2> when its  slam/BetweenFactor.h:111-124
                                      two variables are POSE2 (same table, see between_z)                                  */
        GTG_FAC_PRIOR = 3,         /* PriorFactor<T>                                        nonlinear/PriorFactor.h:98-102 */
-       GTG_FAC_STEREO = 4 };      /* GenericStereoFactor<Pose3,Point3>                     slam/StereoFactor.h:126-154:
+       GTG_FAC_STEREO = 4,       /* GenericStereoFactor<Pose3,Point3>                     slam/StereoFactor.h:126-154:
                                      residual h(x) - z with THREE rows (uL, uR, v), h = StereoCamera::project2
                                      (geometry/StereoCamera.cpp:37-79) with a Cal3_S2Stereo (fx, fy, u0, v0 and a baseline; the skew is
                                      stored and not used, as there); body_P_sensor: H1 = H1 * H0 of pose.compose(sensor, H0) (:129-135);
                                      q.z <= 0 (StereoCheiralityException, throwCheirality_ = false): both Jacobians zero, residual
                                      Vector3::Constant(2 fx) (:144-153).  Its landmark is eliminated like a projection factor's. */
+       GTG_FAC_SAM = 5 };         /* BearingRangeFactor / RangeFactor / BearingFactor <Pose3,Point3>   sam/BearingRangeFactor.h,
+                                     sam/RangeFactor.h, sam/BearingFactor.h (ExpressionFactorN, nonlinear/ExpressionFactor.h:104-153):
+                                     h = Pose3::bearing / Pose3::range of the landmark (geometry/Pose3.cpp:399-439), b = Local(h, z)
+                                     (BearingRange.h:138-144, Unit3::localCoordinates geometry/Unit3.cpp:285-303, in the basis of the
+                                     PREDICTED direction), Jacobians those of h alone, the whole system whitened (:147-150).  Rows:
+                                     bearing-range 3 (bearing 0-1, range 2), range 1, bearing 2.  Its landmark is eliminated like a
+                                     projection factor's. */
+/* sam_kind */
+enum { GTG_SAM_BEARING_RANGE = 0, GTG_SAM_RANGE = 1, GTG_SAM_BEARING = 2 };
 
 /* Noise models (linear/NoiseModel.cpp).  whiten(v) is
  *   UNIT v ; ISOTROPIC v*invsigma (:641-663) ; DIAGONAL v.*invsigmas (:311-325) ; GAUSSIAN R*v (:163-181)
@@ -168,6 +177,19 @@ typedef struct gtg_problem {
    * (Appended after the stereo tables: a caller built against the older struct must be recompiled.) */
   const int32_t* smart_calib;     /* [n_smart] index into the calib table, or -1 for a camera-type smart factor; NULL: all -1 */
   const int32_t* smart_sensor;    /* [n_smart] index into the sensor table or -1 (no body_P_sensor); NULL: none */
+
+  /* GTG_FAC_SAM: BearingRangeFactor<Pose3, Point3>, RangeFactor<Pose3, Point3> and BearingFactor<Pose3, Point3> (gtsam/sam), the
+   * landmark factors of a lidar, sonar, radar or UWB front end.  They use no calib or sensor entry: n_calib may be 0.  NULL / 0: no
+   * such factors.  Refused by gtg_upload_problem: keys that are not (POSE3, POINT3); a noise dimension that does not match the kind
+   * (3, 1, 2); an unknown kind; pose-type smart factors in the same graph (three-row records).
+   * (Appended after the pose-type smart tables: a caller built against the older struct must be recompiled.) */
+  int64_t n_sam;
+  const int32_t* sam_kind;        /* [n_sam] GTG_SAM_* */
+  const int32_t* sam_pose;        /* [n_sam] variable id of the POSE3 */
+  const int32_t* sam_point;       /* [n_sam] variable id of the POINT3 */
+  const double* sam_z;            /* [n_sam*4] the measured Unit3's three stored doubles (a unit vector, as the reference holds it),
+                                     then the measured range; the entries a kind does not use are 0 */
+  const int32_t* sam_noise;       /* [n_sam] index into the noise table (dim 3, 1 or 2 by kind) */
 } gtg_problem;
 
 /* ---- lifetime -------------------------------------------------------------------------------- */
@@ -183,7 +205,7 @@ const char* gtg_version(void);
 /* One-time symbolic analysis + upload.  Replaces what the reference redoes on EVERY lambda try:
  * VariableIndex (inference/VariableIndex-inl.h:27-49), EliminationTree
  * (EliminationTree-inst.h:77-155), JunctionTree (JunctionTree-inst.h:63-151), Scatter
- * (linear/Scatter.cpp:39-73).  Landmarks (POINT3 touched only by projection / stereo factors / priors) are
+ * (linear/Scatter.cpp:39-73).  Landmarks (POINT3 touched only by projection / stereo / bearing-range factors / priors) are
  * eliminated first -- the Schur ordering of timing/timeSFMBAL.h:74-83 -- the remaining variables
  * form the reduced system.  shard/n_shards: this handle owns landmark-factors with
  * (landmark rank) % n_shards == shard and other factors with (factor index) % n_shards == shard
@@ -260,7 +282,9 @@ int gtg_get_hessian_diagonal(gtg_handle h, double* d, int64_t n);     /* Gaussia
 /* whitened Jacobian blocks + rhs of factor type `factor_type` after gtg_linearize():
  * row-major per factor: SFM [A1 2x9 | A2 2x3 | b 2], PROJECTION [2x6 | 2x3 | 2],
  * (the caller's own factors: never the measurements of smart factors), BETWEEN [6x6 | 6x6 | 6], PRIOR [d x d | d] padded to d=9 (81+9), STEREO [A1 3x6 | A2 3x3 | b 3] (30 doubles, the caller's stereo
- * factors in the caller's order; PROJECTION keeps returning the 20-double records of the monocular factors alone).
+ * factors in the caller's order; PROJECTION keeps returning the 20-double records of the monocular factors alone), SAM the same
+ * 30-double record (the caller's bearing / range factors in the caller's order: bearing rows 0-1 and range row 2 of a bearing-range
+ * factor, a range-only factor in row 0, a bearing-only factor in rows 0-1; the rows a kind does not use are exactly 0).
  * n = doubles available in out. */
 int gtg_get_jacobians(gtg_handle h, int factor_type, double* out, int64_t n);
 int64_t gtg_reduced_dim(gtg_handle h);
