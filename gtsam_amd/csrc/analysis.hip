@@ -950,7 +950,7 @@ void analyze(gtg_context& c) {
   // written; stored records: + the Jacobian records written and read once by the assembly.  GeneralSFM factors of a fused graph
   // (fused.h) have no stored records: SURVEY.md section 8(d)'s fused figure -- indices, measurement and noise row read, the
   // off-diagonal block W = Jc^T Jp written (216 B; here in its lambda-dependent form E, by the first point elimination).
-  c.lin_bytes = (double)n_sfm * (2 * 4 + 16 + 4 + (c.fused_sfm ? 216.0 : 2.0 * kSfmRec * 8)) + (double)n_proj * (c.f.rows3 ? 2 * 4 + 24 + 12 + 2.0 * kStereoRec * 8 : 2 * 4 + 16 + 12 + 2.0 * kProjRec * 8) +
+  c.lin_bytes = (double)n_sfm * (2 * 4 + 16 + 4 + (c.fused_sfm ? 216.0 : 2.0 * kSfmRec * 8)) + (double)n_proj * (2 * 4 + 8 * proj_rows(c.f.form) + 12 + 2.0 * proj_rec(c.f.form) * 8) +
                 (double)n_btw * (2 * 4 + 96 + 4 + 2.0 * kBetweenRec * 8) + (double)c.val_size * 8 +
                 (double)c.n_red_vars * 90 * 8 + (double)c.n_lm * 12 * 8 + (double)c.n_hoff * 36 * 8;
 }

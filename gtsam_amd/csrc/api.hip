@@ -552,7 +552,7 @@ int gtg_get_jacobians(gtg_handle c, int type, double* out, int64_t n) {
     check_hip(hipStreamSynchronize(c->stream), "sync");
     src = recomputed.p;
   }
-  if (type == GTG_FAC_PROJECTION && c->f.rows3 && cnt) {
+  if (type == GTG_FAC_PROJECTION && proj_rows(c->f.form) == 3 && cnt) {
     // beside stereo factors the monocular records are stored with three rows, the third zero: give back the two-row records
     // [A1 2x6 | A2 2x3 | b 2] they hold
     std::vector<double> wide((size_t)c->f.n_mono * kStereoRec);

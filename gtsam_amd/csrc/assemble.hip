@@ -30,7 +30,7 @@ struct JTabs {
 
 // (A, rows, row stride, b) of one contribution to a reduced variable.  PR: rows of a projection record -- 2, or 3 in a graph with
 // stereo factors, where every observation of the projection range has the record [A1 PR x 6 | A2 PR x 3 | b PR] (factors.h kStereoRec)
-static_assert(kProjRec == 10 * 2 && kStereoRec == 10 * 3, "a projection record is addressed by its row count");
+static_assert(proj_rec(ProjForm::Rows2) == kProjRec && proj_rec(ProjForm::Rows3) == kStereoRec, "a projection record is addressed by its row count");
 template <int PR>
 __device__ __forceinline__ void contribution(const JTabs& t, int kind, int idx, int d, const double*& A,
                                              int& rows, const double*& b) {
@@ -735,6 +735,7 @@ void launch_obs_wpos(gtg_context& c, int64_t n_inc) {
 
 void launch_assemble(gtg_context& c) {
   JTabs t = jtabs(c);
+  const bool three = proj_rows(c.f.form) == 3;
   if (c.n_red_vars && c.fused_sfm) {
     // several workgroups per camera where there are few cameras (a 16-camera graph has thousands of observations per camera)
     const int splits = c.n_red_vars >= 512 ? 1 : std::min(16, (1024 + c.n_red_vars - 1) / c.n_red_vars);
@@ -747,20 +748,14 @@ void launch_assemble(gtg_context& c) {
     if (c.f.n_proj + c.f.n_between + c.f.n_prior > 0)     // the other factor types' contributions on top
       hipLaunchKernelGGL(k_red_diag<2>, dim3(c.n_red_vars), dim3(64 * kRedWaves), 0, c.stream, c.n_red_vars, c.red_inc_ptr.p,
                          c.red_inc_kind.p, c.red_inc_idx.p, c.red_dim.p, c.red_off.p, t, c.Hd.p, c.gred0.p, c.hdiag_red.p, 1);
-  } else if (c.n_red_vars && c.f.rows3)     // (a graph with stereo factors is never fused: upload.hip)
-    hipLaunchKernelGGL(k_red_diag<3>, dim3(c.n_red_vars), dim3(64 * kRedWaves), 0, c.stream, c.n_red_vars, c.red_inc_ptr.p,
-                       c.red_inc_kind.p, c.red_inc_idx.p, c.red_dim.p, c.red_off.p, t, c.Hd.p, c.gred0.p, c.hdiag_red.p, 0);
-  else if (c.n_red_vars)
-    hipLaunchKernelGGL(k_red_diag<2>, dim3(c.n_red_vars), dim3(64 * kRedWaves), 0, c.stream, c.n_red_vars, c.red_inc_ptr.p,
+  } else if (c.n_red_vars)     // (a three-row graph is never fused: upload.hip)
+    hipLaunchKernelGGL(three ? k_red_diag<3> : k_red_diag<2>, dim3(c.n_red_vars), dim3(64 * kRedWaves), 0, c.stream, c.n_red_vars, c.red_inc_ptr.p,
                        c.red_inc_kind.p, c.red_inc_idx.p, c.red_dim.p, c.red_off.p, t, c.Hd.p, c.gred0.p, c.hdiag_red.p, 0);
   if (c.n_lm && c.fused_sfm)
     hipLaunchKernelGGL(k_lm_fused, dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_obs_ptr.p, c.lm_obs.p,
                        c.lm_pri_ptr.p, c.lm_pri.p, t, sfm_tabs(c), c.V.p, c.gp.p);
-  else if (c.n_lm && c.f.rows3)
-    hipLaunchKernelGGL(k_lm_diag<3>, dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_obs_ptr.p, c.lm_obs.p,
-                       c.lm_pri_ptr.p, c.lm_pri.p, t, c.V.p, c.gp.p);
   else if (c.n_lm)
-    hipLaunchKernelGGL(k_lm_diag<2>, dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_obs_ptr.p, c.lm_obs.p,
+    hipLaunchKernelGGL(three ? k_lm_diag<3> : k_lm_diag<2>, dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_obs_ptr.p, c.lm_obs.p,
                        c.lm_pri_ptr.p, c.lm_pri.p, t, c.V.p, c.gp.p);
   if (c.n_hoff)
     hipLaunchKernelGGL(k_hoff, dim3((unsigned)c.n_hoff), dim3(64), 0, c.stream, c.n_hoff, c.hoff_ptr.p, c.hoff_fac.p,
@@ -855,11 +850,8 @@ void launch_point_eliminate(gtg_context& c, double lambda, int diag, double dmin
   else if (c.f.n_sfm)
     hipLaunchKernelGGL((k_obs_E<kSfmRec, 9, 2, false>), dim3(grid1(c.f.n_sfm / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_sfm, c.f.sfm_J.p, st,
                        c.obs_lm.p, c.Linv.p, c.ylm.p, c.E.p, c.wobs.p, c.obs_wpos.p);
-  if (c.f.n_proj && c.f.rows3)
-    hipLaunchKernelGGL((k_obs_E<kStereoRec, 6, 3, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
-                       c.f.proj_J.p, st, c.obs_lm.p + c.f.n_sfm, c.Linv.p, c.ylm.p, c.E.p + (int64_t)kEStride * c.f.n_sfm, c.wobs.p, c.obs_wpos.p + c.f.n_sfm);
-  else if (c.f.n_proj)
-    hipLaunchKernelGGL((k_obs_E<kProjRec, 6, 2, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
+  if (c.f.n_proj)
+    hipLaunchKernelGGL((proj_rows(c.f.form) == 3 ? k_obs_E<kStereoRec, 6, 3, false> : k_obs_E<kProjRec, 6, 2, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
                        c.f.proj_J.p, st, c.obs_lm.p + c.f.n_sfm, c.Linv.p, c.ylm.p, c.E.p + (int64_t)kEStride * c.f.n_sfm, c.wobs.p, c.obs_wpos.p + c.f.n_sfm);
   check_hip(hipGetLastError(), "point_eliminate");
 }
@@ -895,11 +887,8 @@ void launch_back_substitute(gtg_context& c) {
   else if (c.f.n_sfm && c.n_lm)
     hipLaunchKernelGGL((k_obs_v<kSfmRec, 9, 2, false>), dim3(grid1(c.f.n_sfm / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_sfm, c.f.sfm_J.p, st,
                        c.obs_red.p, c.red_off.p, c.xred.p, c.vobs.p);
-  if (c.f.n_proj && c.n_lm && c.f.rows3)
-    hipLaunchKernelGGL((k_obs_v<kStereoRec, 6, 3, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
-                       c.f.proj_J.p, st, c.obs_red.p + c.f.n_sfm, c.red_off.p, c.xred.p, c.vobs.p + 3 * c.f.n_sfm);
-  else if (c.f.n_proj && c.n_lm)
-    hipLaunchKernelGGL((k_obs_v<kProjRec, 6, 2, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
+  if (c.f.n_proj && c.n_lm)
+    hipLaunchKernelGGL((proj_rows(c.f.form) == 3 ? k_obs_v<kStereoRec, 6, 3, false> : k_obs_v<kProjRec, 6, 2, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
                        c.f.proj_J.p, st, c.obs_red.p + c.f.n_sfm, c.red_off.p, c.xred.p, c.vobs.p + 3 * c.f.n_sfm);
   if (c.n_lm)
     hipLaunchKernelGGL(k_backsub_lm, dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_owned.p,

@@ -136,6 +136,20 @@ struct DfPlan {
   double flops_executed = 0.0;                  // flops minus the contraction MFMAs skipped on structurally empty 16 x 16 sub-tiles (upload_df_plan)
 };
 
+// The form of the projection range: what its records look like and which kernels linearise and evaluate it.  Decided once per
+// upload (upload.hip::upload_projection) from facts of the WHOLE graph -- a shard may own none of the factors that define the form.
+// These four are the only states: pose-type smart factors beside stereo or bearing / range factors are refused by SmartView
+// (upload.hip), and bearing / range factors alone already make a three-row graph.
+enum class ProjForm {
+  Rows2,        // GenericProjectionFactors only: records [A1 2x6 | A2 2x3 | b 2], two measurement entries
+  Rows2Smart,   // ... and the measurements of pose-type smart factors behind them (gtg_context::smart_pose, which this state is derived from)
+  Rows3,        // the graph has a GenericStereoFactor: three-row records and three measurement entries for every observation of the range
+  Rows3Sam,     // the graph has bearing / range factors (with or without stereo factors): the same records, the sam factors in [n_cam, n_proj)
+};
+constexpr int proj_rows(ProjForm f) { return f == ProjForm::Rows3 || f == ProjForm::Rows3Sam ? 3 : 2; }
+constexpr int proj_rec(ProjForm f) { return 10 * proj_rows(f); }   // doubles per record [A1 R x 6 | A2 R x 3 | b R]: kProjRec / kStereoRec (factors.h)
+constexpr bool has_sam(ProjForm f) { return f == ProjForm::Rows3Sam; }
+
 struct FactorTables {
   // SFM
   int64_t n_sfm = 0;
@@ -146,18 +160,17 @@ struct FactorTables {
   int64_t n_proj = 0;
   DevBuf<int32_t> proj_pose, proj_point, proj_noise, proj_calib, proj_sensor;
   DevBuf<double> proj_z, proj_J, calib, sensor;
-  // GenericStereoFactor<Pose3, Point3>: the stereo factors are the observations [n_mono, n_cam) of the projection range.  A graph
-  // with at least one (rows3, decided on the WHOLE graph, not on a shard's rows) keeps three-row records (kStereoRec) and three
-  // measurement entries for every observation of the range, the monocular ones with a zero third row.
+  ProjForm form = ProjForm::Rows2;
+  // GenericStereoFactor<Pose3, Point3>: the stereo factors are the observations [n_mono, n_cam) of the projection range.  A three-row
+  // graph keeps three-row records (kStereoRec) and three measurement entries for every observation of the range, the monocular ones
+  // with a zero third row.
   int64_t n_mono = 0;
-  bool rows3 = false;              // three-row records: the WHOLE graph has a stereo or a sam factor
   DevBuf<double> calib_baseline;   // [n_calib] Cal3_S2Stereo::baseline
   // BearingRangeFactor / RangeFactor / BearingFactor <Pose3, Point3> (gtsam/sam): the observations [n_cam, n_proj) of the projection
   // range, behind the stereo factors [n_mono, n_cam).  They read no calib or sensor entry (proj_calib / proj_sensor hold -1 for them) and
   // keep their measurements in an array of their own: sam_z[4 (i - n_cam)] = the measured Unit3, then the range; sam_kind GTG_SAM_*.
   // Without sam factors n_cam == n_proj and both buffers are empty.
   int64_t n_cam = 0;
-  bool sam = false;                // the WHOLE graph has sam factors (a shard may own none of them)
   DevBuf<int32_t> sam_kind;
   DevBuf<double> sam_z;
   // between
@@ -228,7 +241,7 @@ struct gtg_context {
   gt::DevBuf<double> smart_cache_pose;      // 12 per measurement: the camera poses of the cached triangulation
   gt::DevBuf<double> smart_cache_point;     // 3 per factor
   // SmartProjectionPoseFactor<Cal3_S2> (gtg_problem.smart_calib >= 0): the measurements are PROJECTION observations smart_obs0 .. of
-  // the proj tables instead (keys POSE3, one shared Cal3_S2, optional body_P_sensor); a graph has smart factors of one kind only
+  // the proj tables instead (keys POSE3, one shared Cal3_S2, optional body_P_sensor); a graph has smart factors of one kind only.  f.form is ProjForm::Rows2Smart exactly when this is set
   bool smart_pose = false;
   gt::DevBuf<int32_t> obs_smart, lm_smart;  // per observation of the range the smart measurements live in (GeneralSFM, or projection when smart_pose) / per landmark: its smart factor or -1
   gt::DevBuf<int32_t> var_type;

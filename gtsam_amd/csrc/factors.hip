@@ -74,42 +74,19 @@ __global__ __launch_bounds__(kBlock) void k_lin_sfm(int64_t n, const int32_t* __
   }
 }
 
+// The projection range of a two-row graph (ProjForm::Rows2 / Rows2Smart, context.h).  SMART: the range holds the measurements of
+// pose-type smart factors (SmartProjectionPoseFactor<Cal3_S2>, smart_of[i] >= 0): one whose track is not VALID at the linearisation
+// point contributes nothing -- its record is zeroed (k_lin_smart_pose_at_infinity then writes the records of the tracks that became
+// points at infinity).  <false> receives the two smart pointers and does not read them.
+// How the variants of a range's kernels may share code (checked on the gfx950 instruction streams of every instantiation): an
+// `if constexpr` around an otherwise unchanged body with an unchanged argument list keeps the instruction stream -- k_lin_proj<false>,
+// k_lin_proj<true>, k_lin_rows3<true> and k_error_rows3<true> are the kernels that were once written out one by one (k_lin_proj,
+// k_lin_proj_smart, k_lin_obs3, k_error_obs3), mnemonic for mnemonic with the same registers and scratch, and the <false> forms of the
+// three-row kernels have the f64 sequence, instruction and register counts of the former k_lin_stereo / k_error_stereo.  A shared
+// force-inlined body or a helper for the per-observation gather does NOT: it changed the f64 instructions of the two-row kernels and
+// of k_error<2|6>, and with them the rounding of the records (the step of projection_small was no longer bit-equal to its recording).
+template <bool SMART>
 __global__ __launch_bounds__(kBlock) void k_lin_proj(int64_t n, const int32_t* __restrict__ pose,
-    const int32_t* __restrict__ pt, const double* __restrict__ z, const int32_t* __restrict__ nz,
-    const int32_t* __restrict__ calib_idx, const int32_t* __restrict__ sensor_idx,
-    const double* __restrict__ calib, const double* __restrict__ sensor,
-    const double* __restrict__ values, const int64_t* __restrict__ val_off, NoiseTab nt,
-    double* __restrict__ J) {
-  typedef RecIO<kProjRec> IO;
-  __shared__ double img[kBlock / 64][IO::LDS_DOUBLES];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  double* my = img[wave];
-  const int64_t nchunks = (n + 63) / 64, stride = (int64_t)gridDim.x * (kBlock / 64);
-  for (int64_t ch = blockIdx.x * (int64_t)(kBlock / 64) + wave; ch < nchunks; ch += stride) {
-    const int64_t i = ch * 64 + lane;
-    if (i < n) {
-      double T[12], p[3], zz[2], K[kCalibStride], S[12];
-      const double* tp = values + val_off[pose[i]];
-      const double* pp = values + val_off[pt[i]];
-      for (int k = 0; k < 12; k++) T[k] = tp[k];
-      for (int k = 0; k < 3; k++) p[k] = pp[k];
-      for (int k = 0; k < kCalibStride; k++) K[k] = calib[kCalibStride * calib_idx[i] + k];
-      const int si = sensor_idx[i];
-      if (si >= 0) for (int k = 0; k < 12; k++) S[k] = sensor[12 * si + k];
-      zz[0] = z[2 * i]; zz[1] = z[2 * i + 1];
-      proj_linearize(T, K, si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]), my + lane * IO::PITCH);   // in place in the LDS image (see k_lin_sfm)
-    }
-    const int64_t left = n - ch * 64;
-    IO::store(my, J + (int64_t)kProjRec * ch * 64, left < 64 ? (int)left : 64, lane);
-  }
-}
-
-// The same kernel for a projection range that holds the measurements of pose-type smart factors (SmartProjectionPoseFactor<Cal3_S2>,
-// smart_of[i] >= 0): one whose track is not VALID at the linearisation point contributes nothing -- its record is zeroed
-// (k_lin_smart_pose_at_infinity then writes the records of the tracks that became points at infinity).  A kernel of its own, so that
-// k_lin_proj above stays the code every other graph ran before, instruction for instruction (one force-inlined body behind both kernels
-// had the same register counts and another rounding of the records: the step of projection_small was no longer bit-equal to its recording).
-__global__ __launch_bounds__(kBlock) void k_lin_proj_smart(int64_t n, const int32_t* __restrict__ pose,
     const int32_t* __restrict__ pt, const double* __restrict__ z, const int32_t* __restrict__ nz,
     const int32_t* __restrict__ calib_idx, const int32_t* __restrict__ sensor_idx,
     const double* __restrict__ calib, const double* __restrict__ sensor,
@@ -133,53 +110,23 @@ __global__ __launch_bounds__(kBlock) void k_lin_proj_smart(int64_t n, const int3
       if (si >= 0) for (int k = 0; k < 12; k++) S[k] = sensor[12 * si + k];
       zz[0] = z[2 * i]; zz[1] = z[2 * i + 1];
       proj_linearize(T, K, si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]), my + lane * IO::PITCH);   // in place in the LDS image (see k_lin_sfm)
-      if (smart_of[i] >= 0 && smart_status[smart_of[i]] != kTriValid)
-        for (int k = 0; k < kProjRec; k++) my[lane * IO::PITCH + k] = 0.0;
+      if constexpr (SMART) {
+        if (smart_of[i] >= 0 && smart_status[smart_of[i]] != kTriValid)
+          for (int k = 0; k < kProjRec; k++) my[lane * IO::PITCH + k] = 0.0;
+      }
     }
     const int64_t left = n - ch * 64;
     IO::store(my, J + (int64_t)kProjRec * ch * 64, left < 64 ? (int)left : 64, lane);
   }
 }
 
-// The projection range of a graph WITH stereo factors: observations [0, n_mono) are monocular, [n_mono, n) GenericStereoFactors; every
-// record has three rows (kStereoRec, the monocular ones a zero third row) and every measurement three entries.  Records in place in the
-// LDS image as above.
-__global__ __launch_bounds__(kBlock) void k_lin_stereo(int64_t n, int64_t n_mono, const int32_t* __restrict__ pose,
-    const int32_t* __restrict__ pt, const double* __restrict__ z, const int32_t* __restrict__ nz,
-    const int32_t* __restrict__ calib_idx, const int32_t* __restrict__ sensor_idx,
-    const double* __restrict__ calib, const double* __restrict__ baseline, const double* __restrict__ sensor,
-    const double* __restrict__ values, const int64_t* __restrict__ val_off, NoiseTab nt,
-    double* __restrict__ J) {
-  typedef RecIO<kStereoRec> IO;
-  __shared__ double img[kBlock / 64][IO::LDS_DOUBLES];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  double* my = img[wave];
-  const int64_t nchunks = (n + 63) / 64, stride = (int64_t)gridDim.x * (kBlock / 64);
-  for (int64_t ch = blockIdx.x * (int64_t)(kBlock / 64) + wave; ch < nchunks; ch += stride) {
-    const int64_t i = ch * 64 + lane;
-    if (i < n) {
-      double T[12], p[3], zz[3], K[kCalibStride], S[12];
-      const double* tp = values + val_off[pose[i]];
-      const double* pp = values + val_off[pt[i]];
-      for (int k = 0; k < 12; k++) T[k] = tp[k];
-      for (int k = 0; k < 3; k++) p[k] = pp[k];
-      const int ci = calib_idx[i];
-      for (int k = 0; k < kCalibStride; k++) K[k] = calib[kCalibStride * ci + k];
-      const int si = sensor_idx[i];
-      if (si >= 0) for (int k = 0; k < 12; k++) S[k] = sensor[12 * si + k];
-      for (int k = 0; k < 3; k++) zz[k] = z[3 * i + k];
-      if (i < n_mono) proj_linearize_rows3(T, K, si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]), my + lane * IO::PITCH);
-      else stereo_linearize(T, K, baseline[ci], si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]), my + lane * IO::PITCH);
-    }
-    const int64_t left = n - ch * 64;
-    IO::store(my, J + (int64_t)kStereoRec * ch * 64, left < 64 ? (int)left : 64, lane);
-  }
-}
-
-// The projection range of a graph WITH bearing / range factors (gtsam/sam): k_lin_stereo with a third sub-range.  Observations
-// [0, n_mono) are monocular, [n_mono, n_cam) GenericStereoFactors, [n_cam, n) sam factors of sam_kind[i - n_cam] with the measurement
-// sam_z[4 (i - n_cam)]; they read no calib or sensor entry.  The same three-row records, LDS image and store.
-__global__ __launch_bounds__(kBlock) void k_lin_obs3(int64_t n, int64_t n_mono, int64_t n_cam, const int32_t* __restrict__ pose,
+// The projection range of a three-row graph (ProjForm::Rows3 / Rows3Sam): observations [0, n_mono) are monocular, [n_mono, n_cam)
+// GenericStereoFactors and, SAM (a graph WITH bearing / range factors, gtsam/sam), [n_cam, n) sam factors of sam_kind[i - n_cam] with the
+// measurement sam_z[4 (i - n_cam)]; they read no calib or sensor entry.  Every record has three rows (kStereoRec, the monocular ones a
+// zero third row) and every camera measurement three entries.  Records in place in the LDS image as above.  <false> has n_cam == n and
+// does not read sam_kind / sam_z.
+template <bool SAM>
+__global__ __launch_bounds__(kBlock) void k_lin_rows3(int64_t n, int64_t n_mono, int64_t n_cam, const int32_t* __restrict__ pose,
     const int32_t* __restrict__ pt, const double* __restrict__ z, const int32_t* __restrict__ nz,
     const int32_t* __restrict__ calib_idx, const int32_t* __restrict__ sensor_idx,
     const double* __restrict__ calib, const double* __restrict__ baseline, const double* __restrict__ sensor,
@@ -199,7 +146,9 @@ __global__ __launch_bounds__(kBlock) void k_lin_obs3(int64_t n, int64_t n_mono, 
       const double* pp = values + val_off[pt[i]];
       for (int k = 0; k < 12; k++) T[k] = tp[k];
       for (int k = 0; k < 3; k++) p[k] = pp[k];
-      if (i >= n_cam) {
+      bool is_sam = false;
+      if constexpr (SAM) is_sam = i >= n_cam;
+      if (is_sam) {
         const int64_t s = i - n_cam;
         double zz[4];
         for (int k = 0; k < 4; k++) zz[k] = sam_z[4 * s + k];
@@ -263,9 +212,10 @@ struct ErrArgs {
   const int32_t *smart_of, *smart_status;   // smart factors: the factor of an observation of their range (or -1) and its triangulation status
 };
 
-// Block b handles a fixed slice, so the summation order is fixed.  TYPES: bit 0 -- the GeneralSFM factors, bit 1 -- the other three
-// types, bit 2 (with bit 1) -- the projection range holds the measurements of pose-type smart factors, a.smart_of is its map.  (One kernel for all four types -- rounds 1-4 -- needed 256 registers + scratch for the union of their evaluators: one
+// Block b handles a fixed slice, so the summation order is fixed.  TYPES: kErrSfm -- the GeneralSFM factors, kErrRest -- the other
+// three types, kErrSmartProj (with kErrRest) -- the projection range holds the measurements of pose-type smart factors, a.smart_of is its map.  (One kernel for all four types -- rounds 1-4 -- needed 256 registers + scratch for the union of their evaluators: one
 // wavefront per SIMD, 32 us for the 0.68 M factors of the L1723 shape, a gather-and-evaluate kernel that lives on occupancy.)
+constexpr int kErrSfm = 1, kErrRest = 2, kErrSmartProj = 4;
 template <int TYPES>
 __global__ __launch_bounds__(kBlock) void k_error(ErrArgs a, const double* __restrict__ values, NoiseTab nt,
                                                   double* __restrict__ partials) {
@@ -324,35 +274,10 @@ __global__ __launch_bounds__(kBlock) void k_error(ErrArgs a, const double* __res
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
-// The projection range of a graph with stereo factors (k_lin_stereo): k_error<2> is then launched without that range.  Fixed slices
-// per block as above.
-__global__ __launch_bounds__(kBlock) void k_error_stereo(int64_t n, int64_t n_mono, const int32_t* __restrict__ pose,
-    const int32_t* __restrict__ pt, const double* __restrict__ z, const int32_t* __restrict__ nz,
-    const int32_t* __restrict__ calib_idx, const int32_t* __restrict__ sensor_idx,
-    const double* __restrict__ calib, const double* __restrict__ baseline, const double* __restrict__ sensor,
-    const double* __restrict__ values, const int64_t* __restrict__ val_off, NoiseTab nt, double* __restrict__ partials) {
-  double acc = 0.0;
-  const int64_t tid = blockIdx.x * (int64_t)kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t i = tid; i < n; i += stride) {
-    double T[12], p[3], zz[3], K[kCalibStride], S[12];
-    const double* tp = values + val_off[pose[i]];
-    const double* pp = values + val_off[pt[i]];
-    for (int k = 0; k < 12; k++) T[k] = tp[k];
-    for (int k = 0; k < 3; k++) p[k] = pp[k];
-    const int ci = calib_idx[i];
-    for (int k = 0; k < kCalibStride; k++) K[k] = calib[kCalibStride * ci + k];
-    const int si = sensor_idx[i];
-    if (si >= 0) for (int k = 0; k < 12; k++) S[k] = sensor[12 * si + k];
-    for (int k = 0; k < 3; k++) zz[k] = z[3 * i + k];
-    if (i < n_mono) acc += proj_error(T, K, si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]));
-    else acc += stereo_error(T, K, baseline[ci], si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]));
-  }
-  const double s = block_sum(acc);
-  if (threadIdx.x == 0) partials[blockIdx.x] = s;
-}
-
-// k_error_stereo for the range of k_lin_obs3 (a graph with bearing / range factors)
-__global__ __launch_bounds__(kBlock) void k_error_obs3(int64_t n, int64_t n_mono, int64_t n_cam, const int32_t* __restrict__ pose,
+// The projection range of a three-row graph (the range of k_lin_rows3<SAM>): k_error<kErrRest> is then launched without that range.
+// Fixed slices per block as above.
+template <bool SAM>
+__global__ __launch_bounds__(kBlock) void k_error_rows3(int64_t n, int64_t n_mono, int64_t n_cam, const int32_t* __restrict__ pose,
     const int32_t* __restrict__ pt, const double* __restrict__ z, const int32_t* __restrict__ nz,
     const int32_t* __restrict__ calib_idx, const int32_t* __restrict__ sensor_idx,
     const double* __restrict__ calib, const double* __restrict__ baseline, const double* __restrict__ sensor,
@@ -366,7 +291,9 @@ __global__ __launch_bounds__(kBlock) void k_error_obs3(int64_t n, int64_t n_mono
     const double* pp = values + val_off[pt[i]];
     for (int k = 0; k < 12; k++) T[k] = tp[k];
     for (int k = 0; k < 3; k++) p[k] = pp[k];
-    if (i >= n_cam) {
+    bool is_sam = false;
+    if constexpr (SAM) is_sam = i >= n_cam;
+    if (is_sam) {
       const int64_t s = i - n_cam;
       double zz[4];
       for (int k = 0; k < 4; k++) zz[k] = sam_z[4 * s + k];
@@ -641,7 +568,7 @@ __global__ __launch_bounds__(kBlock) void k_error_smart_at_infinity(int64_t n_me
 }
 
 // The same two kernels for pose-type smart factors (SmartProjectionPoseFactor<Cal3_S2>): their measurements are projection
-// observations (k_lin_proj_smart has zeroed the records of the failed tracks).  The record is built in place in LDS, one slot per
+// observations (k_lin_proj<true> has zeroed the records of the failed tracks).  The record is built in place in LDS, one slot per
 // lane (pitch 21 doubles: odd, so the lanes' slots start in different banks), not in a local array (see k_lin_sfm).
 struct SmartProjTabs {
   const int32_t *pose, *pt, *nz, *calib_idx, *sensor_idx; const double *z, *calib, *sensor; const int64_t* val_off;
@@ -721,25 +648,28 @@ void launch_linearize(gtg_context& c) {
     hipLaunchKernelGGL(k_lin_smart_at_infinity, dim3(grid_for(f.n_sfm - c.smart_obs0)), dim3(kBlock), 0, c.stream, f.n_sfm - c.smart_obs0, c.smart_obs0,
                        f.sfm_cam.p, f.sfm_point.p, f.sfm_z.p, f.sfm_noise.p, c.values.p, c.val_off.p, nt, f.sfm_J.p, c.obs_smart.p,
                        c.smart_lin_status.p, c.scalars.p);
-  if (f.n_proj && f.sam)
-    hipLaunchKernelGGL(k_lin_obs3, dim3(grid_for(f.n_proj)), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.n_cam, f.proj_pose.p,
-                       f.proj_point.p, f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_baseline.p,
-                       f.sensor.p, f.sam_kind.p, f.sam_z.p, c.values.p, c.val_off.p, nt, f.proj_J.p);
-  else if (f.n_proj && f.rows3)
-    hipLaunchKernelGGL(k_lin_stereo, dim3(grid_for(f.n_proj)), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.proj_pose.p,
-                       f.proj_point.p, f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_baseline.p,
-                       f.sensor.p, c.values.p, c.val_off.p, nt, f.proj_J.p);
-  else if (f.n_proj && c.smart_pose) {   // (the smart measurements of this shard may be none: the smart form all the same)
-    hipLaunchKernelGGL(k_lin_proj_smart, dim3(grid_for(f.n_proj)), dim3(kBlock), 0, c.stream, f.n_proj, f.proj_pose.p,
+  // the projection range: one kernel per row count, its instantiation by the form of the range (context.h)
+  const auto two_row = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid_for(f.n_proj)), dim3(kBlock), 0, c.stream, f.n_proj, f.proj_pose.p,
                        f.proj_point.p, f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p,
                        f.sensor.p, c.values.p, c.val_off.p, nt, f.proj_J.p, c.obs_smart.p, c.smart_lin_status.p);
-    if (f.n_proj > c.smart_obs0)
-      hipLaunchKernelGGL(k_lin_smart_pose_at_infinity, dim3(grid_for(f.n_proj - c.smart_obs0)), dim3(kBlock), 0, c.stream, f.n_proj - c.smart_obs0,
-                         c.smart_obs0, smart_proj_tabs(c, c.smart_lin_status.p), c.values.p, nt, f.proj_J.p, c.scalars.p);
-  } else if (f.n_proj)
-    hipLaunchKernelGGL(k_lin_proj, dim3(grid_for(f.n_proj)), dim3(kBlock), 0, c.stream, f.n_proj, f.proj_pose.p,
-                       f.proj_point.p, f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p,
-                       f.sensor.p, c.values.p, c.val_off.p, nt, f.proj_J.p);
+  };
+  const auto three_row = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid_for(f.n_proj)), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.n_cam, f.proj_pose.p,
+                       f.proj_point.p, f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_baseline.p,
+                       f.sensor.p, f.sam_kind.p, f.sam_z.p, c.values.p, c.val_off.p, nt, f.proj_J.p);
+  };
+  if (f.n_proj) switch (f.form) {
+    case ProjForm::Rows2: two_row(k_lin_proj<false>); break;
+    case ProjForm::Rows2Smart:   // (the smart measurements of this shard may be none: the smart form all the same)
+      two_row(k_lin_proj<true>);
+      if (f.n_proj > c.smart_obs0)
+        hipLaunchKernelGGL(k_lin_smart_pose_at_infinity, dim3(grid_for(f.n_proj - c.smart_obs0)), dim3(kBlock), 0, c.stream, f.n_proj - c.smart_obs0,
+                           c.smart_obs0, smart_proj_tabs(c, c.smart_lin_status.p), c.values.p, nt, f.proj_J.p, c.scalars.p);
+      break;
+    case ProjForm::Rows3: three_row(k_lin_rows3<false>); break;
+    case ProjForm::Rows3Sam: three_row(k_lin_rows3<true>); break;
+  }
   if (f.n_between)
     hipLaunchKernelGGL(k_lin_between, dim3(grid_for(f.n_between)), dim3(kBlock), 0, c.stream, f.n_between,
                        f.between_v1.p, f.between_v2.p, f.between_z.p, f.between_noise.p, c.var_type.p, c.values.p,
@@ -779,8 +709,8 @@ void launch_sfm_records(gtg_context& c, double* dst) {
 
 void launch_error(gtg_context& c, const double* values, int slot, const double* gate) {
   auto& f = c.f;
-  // (a three-row graph: its projection range goes to k_error_stereo -- k_error_obs3 with sam factors --, the third group of block partials)
-  ErrArgs a{f.n_sfm, f.rows3 ? 0 : f.n_proj, f.n_between, f.n_prior,
+  const bool three = proj_rows(f.form) == 3;   // (its projection range goes to k_error_rows3, the third group of block partials)
+  ErrArgs a{f.n_sfm, three ? 0 : f.n_proj, f.n_between, f.n_prior,
             f.sfm_cam.p, f.sfm_point.p, f.sfm_noise.p, f.sfm_z.p,
             f.proj_pose.p, f.proj_point.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.proj_z.p, f.calib.p, f.sensor.p,
             f.between_v1.p, f.between_v2.p, f.between_noise.p, f.between_z.p,
@@ -790,18 +720,16 @@ void launch_error(gtg_context& c, const double* values, int slot, const double* 
   if (c.smart_pose) a_sfm.smart_of = nullptr;
   // the GeneralSFM factors and the other types in a kernel each, their block partials one behind the other
   const int64_t nrest = std::max(a.n_proj, std::max(f.n_between, f.n_prior));
-  const int gmax = f.rows3 ? kMaxBlocks / 4 : kMaxBlocks / 2;
+  const int gmax = three ? kMaxBlocks / 4 : kMaxBlocks / 2;
   const int g1 = f.n_sfm ? std::min(grid_for(f.n_sfm), gmax) : 0, g2 = (nrest || !g1) ? std::min(grid_for(nrest), gmax) : 0;
-  const int g3 = f.rows3 && f.n_proj ? std::min(grid_for(f.n_proj), gmax) : 0;
-  if (g1) hipLaunchKernelGGL(k_error<1>, dim3(g1), dim3(kBlock), 0, c.stream, a_sfm, values, noise_tab(c), c.partials.p);
-  if (g2 && c.smart_pose) hipLaunchKernelGGL(k_error<6>, dim3(g2), dim3(kBlock), 0, c.stream, a, values, noise_tab(c), c.partials.p + g1);
-  else if (g2) hipLaunchKernelGGL(k_error<2>, dim3(g2), dim3(kBlock), 0, c.stream, a, values, noise_tab(c), c.partials.p + g1);
-  if (g3 && f.sam) hipLaunchKernelGGL(k_error_obs3, dim3(g3), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.n_cam, f.proj_pose.p, f.proj_point.p,
-                                      f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_baseline.p, f.sensor.p,
-                                      f.sam_kind.p, f.sam_z.p, values, c.val_off.p, noise_tab(c), c.partials.p + g1 + g2);
-  else if (g3) hipLaunchKernelGGL(k_error_stereo, dim3(g3), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.proj_pose.p, f.proj_point.p, f.proj_z.p,
-                             f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_baseline.p, f.sensor.p, values, c.val_off.p,
-                             noise_tab(c), c.partials.p + g1 + g2);
+  const int g3 = three && f.n_proj ? std::min(grid_for(f.n_proj), gmax) : 0;
+  const auto k_rest = f.form == ProjForm::Rows2Smart ? k_error<kErrRest | kErrSmartProj> : k_error<kErrRest>;
+  const auto k_three = has_sam(f.form) ? k_error_rows3<true> : k_error_rows3<false>;
+  if (g1) hipLaunchKernelGGL(k_error<kErrSfm>, dim3(g1), dim3(kBlock), 0, c.stream, a_sfm, values, noise_tab(c), c.partials.p);
+  if (g2) hipLaunchKernelGGL(k_rest, dim3(g2), dim3(kBlock), 0, c.stream, a, values, noise_tab(c), c.partials.p + g1);
+  if (g3) hipLaunchKernelGGL(k_three, dim3(g3), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.n_cam, f.proj_pose.p, f.proj_point.p,
+                             f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_baseline.p, f.sensor.p,
+                             f.sam_kind.p, f.sam_z.p, values, c.val_off.p, noise_tab(c), c.partials.p + g1 + g2);
   hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(kBlock), 0, c.stream, c.partials.p, g1 + g2 + g3, 1, c.scalars.p, slot);
   if (c.n_smart && c.smart_pose)
     hipLaunchKernelGGL(k_error_smart_pose_at_infinity, dim3(1), dim3(kBlock), 0, c.stream, f.n_proj - c.smart_obs0, c.smart_obs0,
@@ -820,10 +748,9 @@ void launch_linear_error(gtg_context& c) {
                f.sfm_J.p, f.proj_J.p, f.between_J.p, f.prior_J.p, c.var_type.p, c.dim_off.p};
   const int64_t nmax = std::max(std::max(f.n_sfm, f.n_proj), std::max(f.n_between, f.n_prior));
   const int g = grid_for(nmax);
-  static_assert(kProjRec == 10 * 2 && kStereoRec == 10 * 3, "k_linear_error addresses a projection record by its row count");
-  if (f.rows3) hipLaunchKernelGGL((k_linear_error<false, 3>), dim3(g), dim3(kBlock), 0, c.stream, a, sfm_tabs(c), c.delta.p, c.partials.p);   // (stereo: never fused, upload.hip)
-  else if (c.fused_sfm) hipLaunchKernelGGL((k_linear_error<true, 2>), dim3(g), dim3(kBlock), 0, c.stream, a, sfm_tabs(c), c.delta.p, c.partials.p);
-  else hipLaunchKernelGGL((k_linear_error<false, 2>), dim3(g), dim3(kBlock), 0, c.stream, a, sfm_tabs(c), c.delta.p, c.partials.p);
+  static_assert(proj_rec(ProjForm::Rows2) == kProjRec && proj_rec(ProjForm::Rows3) == kStereoRec, "k_linear_error addresses a projection record by its row count");
+  const auto kernel = proj_rows(f.form) == 3 ? k_linear_error<false, 3> : c.fused_sfm ? k_linear_error<true, 2> : k_linear_error<false, 2>;   // (three-row: never fused, upload.hip)
+  hipLaunchKernelGGL(kernel, dim3(g), dim3(kBlock), 0, c.stream, a, sfm_tabs(c), c.delta.p, c.partials.p);
   hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(kBlock), 0, c.stream, c.partials.p, g, 2, c.scalars.p, (int)SC_LIN0);
   check_hip(hipGetLastError(), "linear_error");
 }
@@ -842,12 +769,14 @@ void launch_retract(gtg_context& c) {
 // ---- gtg_prewarm: this unit's kernels (kernels.h)
 namespace {
 void prewarm_factors(int) {
-  gt::prewarm_kernels({(const void*)gt::k_lin_sfm, (const void*)gt::k_lin_proj, (const void*)gt::k_lin_between, (const void*)gt::k_lin_prior,
-                       (const void*)gt::k_error<1>, (const void*)gt::k_error<2>, (const void*)gt::k_final_sum, (const void*)gt::k_linear_error<true, 2>,
-                       (const void*)gt::k_linear_error<false, 2>, (const void*)gt::k_linear_error<false, 3>, (const void*)gt::k_lin_stereo, (const void*)gt::k_error_stereo, (const void*)gt::k_lin_obs3, (const void*)gt::k_error_obs3, (const void*)gt::k_retract, (const void*)gt::k_sumsq, (const void*)gt::k_smart_triangulate<false>,
-                       (const void*)gt::k_lin_smart_at_infinity, (const void*)gt::k_error_smart_at_infinity, (const void*)gt::k_sfm_value_offsets,
-                       (const void*)gt::k_smart_triangulate<true>, (const void*)gt::k_lin_proj_smart, (const void*)gt::k_error<6>,
-                       (const void*)gt::k_lin_smart_pose_at_infinity, (const void*)gt::k_error_smart_pose_at_infinity});
+  using namespace gt;
+  prewarm_kernels({(const void*)k_lin_sfm, (const void*)k_lin_proj<false>, (const void*)k_lin_proj<true>, (const void*)k_lin_rows3<false>, (const void*)k_lin_rows3<true>,
+                   (const void*)k_lin_between, (const void*)k_lin_prior, (const void*)k_error<kErrSfm>, (const void*)k_error<kErrRest>,
+                   (const void*)k_error<kErrRest | kErrSmartProj>, (const void*)k_error_rows3<false>, (const void*)k_error_rows3<true>, (const void*)k_final_sum,
+                   (const void*)k_linear_error<true, 2>, (const void*)k_linear_error<false, 2>, (const void*)k_linear_error<false, 3>, (const void*)k_retract,
+                   (const void*)k_sumsq, (const void*)k_smart_triangulate<false>, (const void*)k_smart_triangulate<true>, (const void*)k_lin_smart_at_infinity,
+                   (const void*)k_error_smart_at_infinity, (const void*)k_sfm_value_offsets, (const void*)k_lin_smart_pose_at_infinity,
+                   (const void*)k_error_smart_pose_at_infinity});
 }
 gt::PrewarmUnit prewarm_factors_registered(prewarm_factors);
 }  // namespace

@@ -316,7 +316,8 @@ void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, cons
   auto& f = c.f;
   std::vector<int32_t> pose, pt, nz, cal, sen; std::vector<double> z;
   const int64_t n_stereo = p.n_stereo > 0 ? p.n_stereo : 0, n_sam = p.n_sam > 0 ? p.n_sam : 0;
-  f.rows3 = n_stereo > 0 || n_sam > 0;   // a three-row graph keeps three measurement entries per camera observation (context.h)
+  f.form = n_sam > 0 ? ProjForm::Rows3Sam : n_stereo > 0 ? ProjForm::Rows3 : c.smart_pose ? ProjForm::Rows2Smart : ProjForm::Rows2;   // from the WHOLE graph (context.h; SmartView has refused smart_pose beside the other two)
+  static_assert(proj_rec(ProjForm::Rows2) == kProjRec && proj_rec(ProjForm::Rows3) == kStereoRec, "context.h states the record lengths of factors.h");
   for (int64_t i = 0; i < p.n_proj; i++) {
     check_var(p, p.proj_pose[i]); check_var(p, p.proj_point[i]); check_noise(p, p.proj_noise[i], 2, "GenericProjectionFactor");
     if (p.proj_calib[i] < 0 || p.proj_calib[i] >= p.n_calib) throw std::invalid_argument("bad calibration index");
@@ -326,7 +327,7 @@ void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, cons
     pose.push_back(p.proj_pose[i]); pt.push_back(p.proj_point[i]); nz.push_back(p.proj_noise[i]);
     cal.push_back(p.proj_calib[i]); sen.push_back(si);
     z.push_back(p.proj_z[2 * i]); z.push_back(p.proj_z[2 * i + 1]);
-    if (f.rows3) z.push_back(0.0);
+    if (proj_rows(f.form) == 3) z.push_back(0.0);   // a three-row graph keeps three measurement entries per camera observation
   }
   f.n_mono = (int64_t)pose.size();
   if (c.smart_pose) upload_smart_tracks(c, p.n_proj, p.proj_point, of_obs, own);   // (their measurements are part of the range above)
@@ -369,7 +370,6 @@ void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, cons
     for (int k = 0; k < 4; k++) sam_z.push_back(p.sam_z[4 * i + k]);
   }
   f.n_proj = (int64_t)pose.size();
-  f.sam = n_sam > 0;
   if (n_sam) { up(f.sam_kind, sam_kind, c.stream); up(f.sam_z, sam_z, c.stream); } else { f.sam_kind.free(); f.sam_z.free(); }
   up(f.proj_pose, pose, c.stream); up(f.proj_point, pt, c.stream); up(f.proj_noise, nz, c.stream); up(f.proj_calib, cal, c.stream);
   up(f.proj_sensor, sen, c.stream); up(f.proj_z, z, c.stream);
@@ -384,7 +384,7 @@ void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, cons
     std::vector<double> bl(p.calib_baseline, p.calib_baseline + p.n_calib);
     up(f.calib_baseline, bl, c.stream);
   } else f.calib_baseline.free();
-  f.proj_J.alloc(std::max<size_t>((size_t)(f.rows3 ? kStereoRec : kProjRec) * f.n_proj, 1));
+  f.proj_J.alloc(std::max<size_t>((size_t)proj_rec(f.form) * f.n_proj, 1));
   hi.proj_pose = pose; hi.proj_point = pt;
 }
 

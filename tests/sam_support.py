@@ -6,26 +6,6 @@ from tests import stereo_support as S
 from tests.stereo_support import fixture, problem_of, rel  # noqa: F401
 
 
-def stereo_mixed_step(lib):
-    """Everything one linearisation and three lambda tries of stereo_mixed (a three-row graph WITHOUT sam factors) compute, for the
-    bit comparison with the recording made with the parent commit's library (tests/golden/stereo_mixed_step_parent.npz)."""
-    g = S.fixture("stereo_mixed")
-    dev = lib.DeviceGraph(S.problem_of(g))
-    dev.set_values(g["values0"])
-    got = {"error": np.float64(dev.error())}
-    dev.linearize()
-    for ft in (1, 2, 3, 4):
-        got[f"jac{ft}"] = dev.jacobians(ft)
-    got["hessian_diagonal"], got["gradient"] = dev.hessian_diagonal(), dev.gradient()
-    for i, (lam, dd) in enumerate(((1e-3, False), (1e-4, True))):
-        rc, out = dev.try_lambda(lam, dd)
-        got[f"rc{i}"], got[f"out{i}"], got[f"delta{i}"], got[f"trial{i}"] = np.int64(rc), out, dev.delta(), dev.trial_values()
-    rc, out, its = dev.try_lambda_pcg(1e-3, False, max_iterations=300, min_iterations=1, epsilon_rel=1e-10, epsilon_abs=1e-14)
-    got["rc_pcg"], got["out_pcg"], got["delta_pcg"], got["its_pcg"] = np.int64(rc), out, dev.delta(), np.int64(its)
-    dev.close()
-    return got
-
-
 TEXT_FIELDS = S.TEXT_FIELDS[:S.TEXT_FIELDS.index("between_v1")] + ("sam_kind", "sam_pose", "sam_point", "sam_z", "sam_noise") + \
     S.TEXT_FIELDS[S.TEXT_FIELDS.index("between_v1"):]
 

@@ -1,6 +1,6 @@
 """Designs and references for the scalars of one Levenberg-Marquardt step and for the retraction (tests only, numpy on the host).
 
-error(), the error of the trial point, the two linear costs, |delta| and the trial values come from k_error<1|2|6>, k_error_stereo,
+error(), the error of the trial point, the two linear costs, |delta| and the trial values come from k_error<1|2|6>, k_error_rows3,
 k_linear_error, k_sumsq, k_final_sum and k_retract (csrc/factors.hip).  Three families of graphs are built here:
 
 EXACT designs (exact_design, EXACT): every factor's error is a dyadic rational by construction -- identity rotations, focal length
@@ -57,7 +57,7 @@ def grid_for(n):
 
 
 def error_grids(n_sfm=0, n_proj=0, n_stereo=0, n_between=0, n_prior=0):
-    """(g1, g2, g3) of launch_error: k_error<1>, k_error<2>, k_error_stereo; their partials lie at 0, g1 and g1 + g2."""
+    """(g1, g2, g3) of launch_error: k_error<1>, k_error<2>, k_error_rows3; their partials lie at 0, g1 and g1 + g2."""
     stereo = n_stereo > 0
     total_proj = n_proj + n_stereo                       # the device's projection range: monocular first, then stereo
     nrest = max(0 if stereo else n_proj, n_between, n_prior)

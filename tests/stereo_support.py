@@ -66,26 +66,6 @@ def rel(a, b):
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
-def projection_small_step(lib):
-    """Everything one linearisation and three lambda tries of projection_small (a graph WITHOUT stereo factors) compute, for the
-    bit comparison with the recording made with the parent commit's library (tests/golden/projection_small_step_parent.npz)."""
-    from tests import problems as PB
-    p, v0 = PB.SYNTH["projection_small"]()
-    dev = lib.DeviceGraph(p)
-    dev.set_values(v0)
-    got = {"error": np.float64(dev.error())}
-    dev.linearize()
-    got["jac1"], got["jac3"] = dev.jacobians(1), dev.jacobians(3)
-    got["hessian_diagonal"], got["gradient"] = dev.hessian_diagonal(), dev.gradient()
-    for i, (lam, dd) in enumerate(((1e-3, False), (1e-4, True))):
-        rc, out = dev.try_lambda(lam, dd)
-        got[f"rc{i}"], got[f"out{i}"], got[f"delta{i}"], got[f"trial{i}"] = np.int64(rc), out, dev.delta(), dev.trial_values()
-    rc, out, its = dev.try_lambda_pcg(1e-3, False, max_iterations=300, min_iterations=1, epsilon_rel=1e-10, epsilon_abs=1e-14)
-    got["rc_pcg"], got["out_pcg"], got["delta_pcg"], got["its_pcg"] = np.int64(rc), out, dev.delta(), np.int64(its)
-    dev.close()
-    return got
-
-
 TEXT_FIELDS = ("var_type", "noise_kind", "noise_dim", "noise_off", "noise_data", "noise_robust", "noise_robust_param",
                "proj_pose", "proj_point", "proj_z", "proj_noise", "proj_calib", "proj_sensor", "calib", "calib_distortion", "sensor",
                "stereo_pose", "stereo_point", "stereo_z", "stereo_noise", "stereo_calib", "stereo_sensor", "calib_baseline",

@@ -16,6 +16,7 @@ from gtsam_amd.params import LevenbergMarquardtParams as LMP
 from gtsam_amd.problem import NOISE_ISOTROPIC
 from tests import sam_support as SS
 from tests.sam_support import rel
+from tests.step_recording import record_step
 from tests.test_gpu_stereo import check_solves, check_trajectory, run_two_shards
 
 pytestmark = pytest.mark.gpu
@@ -342,7 +343,21 @@ def test_three_row_step_without_sam_factors_equals_the_parent_commits(gpu):
     (tests/golden/stereo_mixed_step_parent.npz).  The two-row path has the same test in tests/test_gpu_stereo.py
     (projection_small_step_parent.npz), which stays as it is."""
     rec = dict(np.load(os.path.join(ROOT, "tests", "golden", "stereo_mixed_step_parent.npz")))
-    got = SS.stereo_mixed_step(gpu)
+    g = SS.fixture("stereo_mixed")
+    got = record_step(gpu, SS.problem_of(g), g["values0"], jac_types=(1, 2, 3, 4))
+    assert set(got) == set(rec)
+    for k in got:
+        assert np.array_equal(np.asarray(got[k]), rec[k]), k
+
+
+def test_three_row_step_with_sam_factors_equals_the_parent_commits(gpu, mixed):
+    """sam3d_mixed (40 monocular + 90 stereo + 301 bearing / range observations: both sub-range boundaries and the end inside a
+    64-factor chunk, two workgroups, robust rows) through k_lin_rows3<true> / k_error_rows3<true>: bit-equal to a recording made on the
+    MI355X with the library of the commit before the two kernels became instantiations (tests/golden/sam3d_mixed_step_parent.npz;
+    recorded twice in two processes, every key agreed)."""
+    p, v0, _ = mixed
+    rec = dict(np.load(os.path.join(ROOT, "tests", "golden", "sam3d_mixed_step_parent.npz")))
+    got = record_step(gpu, p, v0, jac_types=(1, 2, 3, 4, 5))
     assert set(got) == set(rec)
     for k in got:
         assert np.array_equal(np.asarray(got[k]), rec[k]), k

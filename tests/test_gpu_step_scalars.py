@@ -1,5 +1,5 @@
 """The scalars Levenberg-Marquardt accepts or rejects a step on, and the trial values, at the boundaries of their kernels:
-k_error<1|2>, k_error_stereo, k_linear_error, k_sumsq, k_final_sum and k_retract (csrc/factors.hip) on the designs of
+k_error<1|2>, k_error_rows3, k_linear_error, k_sumsq, k_final_sum and k_retract (csrc/factors.hip) on the designs of
 tests/step_designs.py, every one of which tests/test_step_designs_reference.py proves fit for its purpose on the host.
 
 EXACT designs (per-factor errors are dyadic rationals: every partial sum is exact in double, in any order):

@@ -15,7 +15,9 @@ import pytest
 
 from gtsam_amd.params import LevenbergMarquardtParams as LMP
 from gtsam_amd.problem import NOISE_ISOTROPIC
+from tests import problems as PB
 from tests import stereo_support as S
+from tests.step_recording import record_step
 from tests.stereo_support import rel
 
 pytestmark = pytest.mark.gpu
@@ -367,7 +369,7 @@ def test_no_stereo_step_equals_the_parent_commits(gpu):
     """projection_small (n_stereo = 0) takes the kernels it took before: its records, sums and two damped steps are bit-equal to a
     recording made on the MI355X with the library of the parent commit (tests/golden/projection_small_step_parent.npz)."""
     rec = dict(np.load(os.path.join(ROOT, "tests", "golden", "projection_small_step_parent.npz")))
-    got = S.projection_small_step(gpu)
+    got = record_step(gpu, *PB.SYNTH["projection_small"](), jac_types=(1, 3))
     assert set(got) == set(rec)
     for k in got:
         assert np.array_equal(np.asarray(got[k]), rec[k]), k

@@ -193,7 +193,7 @@ def test_designs_cover_the_grid_boundaries():
     mono_graphs = [c for c in counts.values() if not c.get("n_stereo")]
     for rng in ("n_sfm", "n_proj", "n_between", "n_prior"):
         assert set(SD._caps(SD.CAP_ERROR)) <= {c.get(rng, 0) for c in mono_graphs}, rng
-    # ... k_error_stereo (the whole projection range of a stereo graph) ...
+    # ... k_error_rows3 (the whole projection range of a three-row graph) ...
     stereo_total = {c.get("n_proj", 0) + c["n_stereo"] for c in counts.values() if c.get("n_stereo")}
     assert set(SD._caps(SD.CAP_ERROR_STEREO)) <= stereo_total
     # ... and the cap of k_linear_error in EVERY one of its loops, with the linear part of the test on: the fused GeneralSFM loop (no
