@@ -821,7 +821,7 @@ void analyze(gtg_context& c) {
         const int dev = c.device;
         dfh = std::thread([&] { try { StageClock k; check_hip(hipSetDevice(dev), "hipSetDevice"); build_chol_plan(c.plan, nt, dense ? nullptr : &B2, s, &pair_part, &part_parent);
                                       sp_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - k.t).count(); } catch (...) { dferr = std::current_exception(); } });
-        try { StageClock k; if (c.use_df) build_df_plan_host(c.df, nt, dense ? nullptr : &T1, &tile_part, &part_parent); k.lap("  (dataflow task lists, this thread)"); }
+        try { StageClock k; if (c.use_df) plan_dataflow(c.df, nt, dense ? nullptr : &T1, &tile_part, &part_parent); k.lap("  (dataflow task lists, this thread)"); }
         catch (...) { if (dfh.joinable()) dfh.join(); throw; }
         if (dfh.joinable()) dfh.join();
         if (dferr) std::rethrow_exception(dferr);

@@ -778,7 +778,7 @@ int gtg_dense_cholesky_host(gtg_handle c, double* A, int32_t n, double* rhs) {
   DevBuf<double> S, Dinv, x, fail;
   DfPlan df;
   const bool use_df = dataflow_schedule_selected();
-  if (use_df) build_df_plan(df, nt, nullptr, c->stream, plan.h_slot, plan.n_stored);   // (before S: the plan may want scratch slots behind the tiles)
+  if (use_df) { plan_dataflow(df, nt, nullptr); upload_df_plan(df, c->stream, plan.h_slot, plan.n_stored); }   // (before S: the plan may want scratch slots behind the tiles)
   S.alloc((size_t)(plan.n_stored + df.n_scratch) * kTileDoubles); Dinv.alloc((size_t)nt * kTile * kTile); x.alloc(2 * (size_t)NP); fail.alloc(2);
   check_hip(hipMemset(Dinv.p, 0, sizeof(double) * Dinv.n), "memset");
   if (!c->chol_epoch_dev.p) { c->chol_epoch_dev.alloc(1); check_hip(hipMemset(c->chol_epoch_dev.p, 0, sizeof(long long)), "memset"); }

@@ -47,9 +47,7 @@ constexpr int PX = SB + 2;        // LDS pitch (doubles) of a 128 x 32 block of 
 // A dependency wait gives up after kWaitTicks of the 100 MHz constant clock (20 ms: four factorisations of the headline problem; the
 // try is then repeated with the other schedule, api.hip) -- the bound used to be 4 M polls, more than a second per stuck wait.
 constexpr long long kWaitTicks = 2000000;
-constexpr long long kPieceBase = 4096;   // part_flag = kPieceBase epoch + finished pieces of the tile's contraction (< kPieceBase pieces per tile)
-constexpr int kChainWords = 4;     // words per diagonal tile in the chain kernel's table: slot of (J, J), slot of (J, J-1) or -1, the 64-bit sub-tile mask of (J, J-1)
-constexpr int kStepWords = 6;      // words of a contraction step in the device klist: slots of (I, k), (J, k), their two 64-bit sub-tile masks
+// (kPieceBase, kStepWords, kChainWords: tile_plan.h -- the planner that writes the tables shares them)
 constexpr int kImgDoubles = 2 * 64 * 8;   // one MFMA operand image of a 32x32 block (chol_device.h opnd_off): 8 KB
 constexpr size_t kSmemBulk = std::max<size_t>(4 * (size_t)CH, sizeof(double) * (T * PX + 4 * kImgDoubles));
 constexpr size_t kSmemPotrf = sizeof(double) * kPotrfSmemDoubles;
@@ -756,360 +754,54 @@ __global__ __launch_bounds__(256) void k_df_resolve(int64_t n_tasks, int nt, con
 
 #ifndef GT_KERNEL_EMU   // (host code from here on)
 
-// ---- host: task lists --------------------------------------------------------------------------------------------
-// tile_struct: (nt x nt) row-major bytes, lower triangle: tile (I, J) holds something before the factorisation
-// (nullptr = dense).  Symbolic elimination at tile granularity adds the fill; the rhs row (tile row nt) is dense.
-// Two halves: build_df_plan_host is pure host code (no runtime call: analysis.hip runs it on its own thread beside build_chol_plan),
-// upload_df_plan resolves the tiles to slots -- which come from the stream schedule's plan -- and makes the device copies.
-void build_df_plan(DfPlan& df, int nt, const std::vector<uint8_t>* tile_struct, hipStream_t stream,
-                   const std::vector<int32_t>& slot, int64_t n_slots,
-                   const std::vector<int32_t>* tile_part, const std::vector<int32_t>* part_parent) {
-  build_df_plan_host(df, nt, tile_struct, tile_part, part_parent);
-  upload_df_plan(df, stream, slot, n_slots);
-}
-
-void build_df_plan_host(DfPlan& df, int nt, const std::vector<uint8_t>* tile_struct,
-                        const std::vector<int32_t>* tile_part, const std::vector<int32_t>* part_parent) {
-  const bool sect_on = std::getenv("GTG_DF_PLAN_TIMING") != nullptr;
-  auto sect_t = std::chrono::high_resolution_clock::now();
-  auto sect = [&](const char* what) { if (!sect_on) return; const auto n = std::chrono::high_resolution_clock::now(); std::fprintf(stderr, "[df plan] %-28s %7.3f ms\n", what, std::chrono::duration<double, std::milli>(n - sect_t).count()); sect_t = n; };
-  std::vector<uint8_t> B((size_t)nt * nt, 0);
-  for (int i = 0; i < nt; i++)
-    for (int j = 0; j <= i; j++) B[(size_t)i * nt + j] = tile_struct ? (*tile_struct)[(size_t)i * nt + j] : 1;
-  for (int i = 0; i < nt; i++) B[(size_t)i * nt + i] = 1;
-  for (int k = 0; k < nt; k++) {
-    std::vector<int> r;
-    for (int i = k + 1; i < nt; i++) if (B[(size_t)i * nt + k]) r.push_back(i);
-    for (size_t a = 0; a < r.size(); a++)
-      for (size_t b = 0; b <= a; b++) B[(size_t)r[a] * nt + r[b]] = 1;
-  }
-  std::vector<std::vector<int32_t>> rowcols(nt);
-  const int bw = (nt + 63) / 64;
-  std::vector<uint64_t> rowbits((size_t)nt * bw, 0);     // the same rows as bit sets: a tile's contraction list is the AND of two of them
-  for (int i = 0; i < nt; i++)
-    for (int k = 0; k < i; k++) if (B[(size_t)i * nt + k]) { rowcols[i].push_back(k); rowbits[(size_t)i * bw + (k >> 6)] |= 1ull << (k & 63); }
-
-  sect("symbolic fill + row lists");
-  // ---- elimination-tree parallelism: several diagonal chains --------------------------------------------------------
-  // With a nested-dissection ordering (analysis.hip) the block columns fall into PARTS: leaves that do not touch each other and the
-  // separators above them (part_parent; children are numbered before their parent, a part is a contiguous range of tiles).  The
-  // reference eliminates independent subtrees of its junction tree concurrently (inference/ClusterTree-inst.h:218-317,
-  // base/treeTraversal/parallelTraversalTasks.h:35-156); here every leaf gets its own chain of diagonal tiles:
-  //   * the block columns are taken in an order `seq` that interleaves the parts that are ready (all children done) column by
-  //     column, pos[c] = place of column c in it.  Ticket order, contraction lists and the placement of early pieces below are all
-  //     stated in terms of pos (without parts pos[c] = c and everything is what it was);
-  //   * the chain kernel runs 2 workgroups per SLOT (<= 4 slots on the 8 reserved CUs); a leaf takes the next slot round robin,
-  //     a separator the slot of its first child; a slot's tiles are taken in pos order, alternating between its two workgroups.
-  // Deadlock freedom is unchanged: a task only waits for tasks with smaller tickets and for diagonal tiles whose own inputs have
-  // smaller tickets; a chain workgroup walks its tiles in pos order, so the tile it waits for is always the one whose inputs come first.
-  const bool tree = tile_part && part_parent && part_parent->size() > 1 && (int)tile_part->size() == nt;
-  const int nparts = tree ? (int)part_parent->size() : 1;
-  std::vector<int32_t> part_of(nt, 0), seq, pos(nt, 0);
-  if (tree) for (int c = 0; c < nt; c++) part_of[c] = (*tile_part)[c];
-  {
-    std::vector<std::vector<int32_t>> cols(nparts);
-    for (int c = 0; c < nt; c++) cols[part_of[c]].push_back(c);
-    std::vector<int> pending(nparts, 0), next(nparts, 0);
-    if (tree) for (int x = 0; x < nparts; x++) if ((*part_parent)[x] >= 0) pending[(*part_parent)[x]]++;
-    std::vector<int> active;
-    for (int x = 0; x < nparts; x++) if (pending[x] == 0) active.push_back(x);
-    while (!active.empty()) {
-      std::vector<int> still;
-      for (int x : active) {
-        if (next[x] < (int)cols[x].size()) seq.push_back(cols[x][next[x]++]);
-        if (next[x] < (int)cols[x].size()) { still.push_back(x); continue; }
-        const int par = tree ? (*part_parent)[x] : -1;
-        if (par >= 0 && --pending[par] == 0) still.push_back(par);
-      }
-      active.swap(still);
-    }
-    if ((int)seq.size() != nt) throw std::runtime_error("dataflow plan: the parts do not cover the block columns");
-    for (int q = 0; q < nt; q++) pos[seq[q]] = q;
-    // slots and chain lists
-    std::vector<int> slot(nparts, 0);
-    int nslots = 1;
-    if (tree) {
-      // (round 4: 8 slots = 16 reserved CUs by default -- with the accumulator lanes of the separators' diagonal tiles in place the leaf
-      // chains are the critical path of a pose graph, and they run side by side; up to 16 slots = 32 reserved CUs on request)
-      // (16 slots = 32 reserved CUs since round 6: one slot per leaf of a 4-level dissection with room to spare; measured against 8 / 12
-      // slots, profiles/r06j_slots_sweep.txt: sphere2500 0.913 / 0.892 / 0.892 ms, w20000 2.71 / 2.78 / 2.58 ms -- the pose graphs' bulk
-      // work is a few GFLOP, the CUs cost nothing; what bounds them is the serial top of the tree, profiles/r06k_trace_sphere2500.json)
-      constexpr int max_slots = 16;
-      std::vector<int> first_child(nparts, -1);
-      for (int x = nparts - 1; x >= 0; x--) if ((*part_parent)[x] >= 0) first_child[(*part_parent)[x]] = x;
-      int leaves = 0;
-      for (int x = 0; x < nparts; x++) if (first_child[x] < 0) slot[x] = leaves++ % max_slots;
-      for (int x = 0; x < nparts; x++) if (first_child[x] >= 0) slot[x] = slot[first_child[x]];   // (children precede their parent)
-      nslots = std::min(leaves, max_slots);
-    }
-    std::vector<std::vector<int32_t>> per_slot(nslots);
-    for (int q = 0; q < nt; q++) per_slot[slot[part_of[seq[q]]]].push_back(seq[q]);      // pos order
-    df.h_chain_off.assign(1, 0); df.h_chain_tiles.clear();
-    const int per = nt > 1 ? 2 : 1;
-    int longest = 0;
-    for (int sl = 0; sl < nslots; sl++) {
-      longest = std::max(longest, (int)per_slot[sl].size());
-      for (int w = 0; w < per; w++) {
-        for (size_t i = w; i < per_slot[sl].size(); i += per) df.h_chain_tiles.push_back(per_slot[sl][i]);
-        df.h_chain_off.push_back((int32_t)df.h_chain_tiles.size());
-      }
-    }
-    df.n_chain = (int)df.h_chain_off.size() - 1;
-    df.h_seq = seq;
-    df.critical_tiles = longest;
-  }
-  auto by_pos = [&](std::vector<int32_t>& v) { if (tree) std::sort(v.begin(), v.end(), [&](int32_t a, int32_t b) { return pos[a] < pos[b]; }); };
-
-  df.h_tasks.clear(); df.h_klist.clear();
-  const double t3 = (double)T * T * T;
-  double flops = 0.0; int64_t stored = 0;
-  // A tile's contraction is serial on one CU (14 us per step, up to ~30 steps) and the workgroups in flight cover only ~9 block
-  // columns: a long contraction taken when its column comes up would not be done when the column's diagonal tile is factored.
-  // So a long list is cut into PIECES of at most kPiece steps; piece r accumulates in place (tile -= its steps, flag
-  // part_flag = kPieceBase epoch + r + 1) and is queued EARLIER than the tile's own column: right behind the block column of its
-  // youngest operand, where everything it reads is final and it runs without waiting.  Only the last piece (the youngest
-  // kFinal steps + the substitution) sits in the tile's column and streams behind the columns before it.
-  // (kPiece, kFinal) swept on the L1723 shape in round 4 (Cholesky ms): (6,3) 5.17, (4,4) 5.09, (6,4) 5.10, (4,5) 5.11, (3,4) 5.14,
-  // (4,3) 5.15, (4,6) 5.16, (8,3) 5.32, (2,4) 5.32, (6,2) 5.48, (10,3) 5.51.
-  constexpr int kPiece = 4, kFinal = 4;
-  // The DIAGONAL tile's last piece is shorter: PD(J) is on the serial chain -- the chain workgroup of tile J cannot start before it -- and a
-  // last piece of 4 steps is 72 us of contraction (18 us per step) that only starts when a workgroup takes its ticket.  Round 5 trace
-  // (profiles/r05f_late_pd.txt): on 13 of 120 block columns of the L1723 shape the ticket was taken 53 - 74 us before the tile was needed
-  // instead of the usual 77 - 120, PD(J) came 7 - 20 us late, and those 13 periods (57 us instead of 41) were 0.27 ms of the 5.05.
-  // The same holds for the tiles right below it: (J + 1, J) feeds the next diagonal tile through the chain kernel, (J + 2, J) is the youngest
-  // operand of PD(J + 2) AND of the critical tile (J + 2, J + 1) -- when its last piece was taken 40 - 60 us before its column's diagonal
-  // tile was out (normally: 100), it was final 25 us late and both were late with it -- and (J + 3, J) is the youngest operand of that one.
-  // Swept on the L1723 shape (profiles/r05_plan_cut_sweep.txt; Cholesky ms): last piece of the diagonal tile 1 / 2 / 3 / 4 steps 5.17 / 5.04 / 5.03 /
-  // 5.09; short pieces + pulled for 0 / 2 / 3 rows below it 5.07 / 5.03 / 5.00.
-#ifndef GT_DF_FINAL_DIAG
-#define GT_DF_FINAL_DIAG 2
-#endif
-#ifndef GT_DF_NEAR_ROWS
-#define GT_DF_NEAR_ROWS 3
-#endif
-  constexpr int kFinalDiag = GT_DF_FINAL_DIAG, kNearRows = GT_DF_NEAR_ROWS;
-  struct Rec { int32_t I, J, koff, kcnt, r, R; };
-  std::vector<std::vector<Rec>> finals(nt), early(nt);      // by place in `seq`
-  std::vector<int> diag_last_g(nt + 1, -1);                  // group of the last early piece of PD(J) (-1: none)
-  std::vector<int> cut;
-  { size_t tiles = 0; for (int i = 0; i < nt; i++) tiles += rowcols[i].size();       // (room up front: a tile has a last piece and ~ a piece per 4 steps)
-    for (int g = 0; g < nt; g++) { finals[g].reserve(rowcols[g].size() + nt / 2 + 4); early[g].reserve(2 * (tiles / nt + 1) + 16); }
-    df.h_klist.reserve(16 * tiles); }
-  auto emit = [&](int I, int J, std::vector<int32_t>& ks) {
-    by_pos(ks);                                        // the steps in the order in which their operands come into being
-    const int n = (int)ks.size(), G = pos[J];
-    const bool near = I - J <= kNearRows;              // the diagonal tile and the kNearRows tiles below it: on or next to the serial chain
-    int m = std::max(0, n - (near ? kFinalDiag : kFinal));   // older steps, in early pieces of at most kPiece; the last piece: the youngest
-    while (m > 0 && pos[ks[m - 1]] > G - 3) m--;     // (an early piece sits two groups before its tile's column at the latest)
-    const int f = n - m;
-    // the early steps cut into pieces of kPiece from the old end; a DIAGONAL tile's last early piece is short as well (kFinalDiag steps):
-    // the last piece cannot start before it is done, and 4 steps are 73 us (round 5 trace: PD(J) late whenever that piece had 4)
-    cut.clear();             // piece r = steps [cut[r], cut[r + 1])
-    {
-      const int tail = (near && m > kFinalDiag) ? kFinalDiag : 0;
-      for (int b = 0; b < m - tail; b += kPiece) cut.push_back(b);
-      if (tail) cut.push_back(m - tail);
-      cut.push_back(m);
-    }
-    const int R = (int)cut.size();     // early pieces + the last one
-    if (R >= (int)kPieceBase) throw std::runtime_error("dataflow plan: a contraction list needs more pieces than the part flags can count");
-    const int32_t off = (int32_t)df.h_klist.size();
-    df.h_klist.insert(df.h_klist.end(), ks.begin(), ks.end());
-    int gprev = 0;
-    for (int r = 0; r + 1 < R; r++) {
-      const int b = cut[r], e = cut[r + 1];
-      const int last_k = ks[e - 1];
-      const int g = std::max(pos[last_k] + 1, gprev);   // as early as its operands exist (<= G - 2)
-      early[g].push_back(Rec{I, J, off + b, e - b, r, R}); gprev = g;
-      if (I == J) diag_last_g[J] = g;
-    }
-    finals[G].push_back(Rec{I, J, off + m, f, R - 1, R});
-  };
-  sect("parts, chains");
-  std::vector<int32_t> ks;
-  std::vector<int32_t> has_sub(nt, 0);
-  for (int J = 0; J < nt; J++) {
-    // the contribution of block column J-1 to the diagonal tile is applied by k_df_chain itself (streamed): not in PD's list
-    ks = rowcols[J];
-    if (!ks.empty() && ks.back() == J - 1) { ks.pop_back(); has_sub[J] = 1; }
-    // (also streaming column J-2's contribution in the chain workgroup was measured in round 4: PD(J) is never late then -- the p90 of
-    // the chain period falls from 59 to 54 us -- but the extra 16 us of slices push the MEDIAN period from 40.0 to 41.6 us: 5.25 ->
-    // 5.49 ms on L1723.  Removed.)
-    emit(J, J, ks);
-    flops += t3 / 3.0 + (double)rowcols[J].size() * t3; stored++;
-    for (int I = J + 1; I < nt; I++) {
-      if (!B[(size_t)I * nt + J]) continue;
-      ks.clear();
-      for (int w = 0; w < bw; w++) {
-        uint64_t both = rowbits[(size_t)I * bw + w] & rowbits[(size_t)J * bw + w];
-        while (both) { ks.push_back(64 * w + __builtin_ctzll(both)); both &= both - 1; }
-      }
-      emit(I, J, ks);
-      flops += t3 + (double)ks.size() * 2.0 * t3; stored++;
-    }
-    ks = rowcols[J];
-    emit(nt, J, ks);   // rhs row: y_J (flops not counted, as in the right-looking plan)
-  }
-  // (Round 6, measured and removed -- profiles/r06i_level_sweep.txt, tools/df_plan_load.py: early pieces are queued As Soon As Possible, and
-  // on a banded system they arrive in bursts: the work of a ticket-order iteration swings between 0.4 and 1.9 times what 246 workgroups get
-  // done in a chain period, 39 of 122 iterations of the L1723 shape are over.  A forward sweep that moved the pieces with the latest
-  // deadlines out of overfull iterations (same pieces, same order inside a tile: bit-identical) levelled that profile completely -- and the
-  // factorisation went from 5.00 to 5.97 ms (capacity = 100 % of a period's work; 9.2 ms at 90 %, no change at 120 - 150 %).  The aggregate
-  // is not what binds: a tile's pieces are a serial chain of ~70 us links, and every deferral shortens the time that chain has.)
-  // ticket order: the own tasks of the column in place q (diagonal accumulation, the tile below it, ...), then the early pieces whose
-  // youngest operand is in place q - 2: the latency-critical tasks of a column are taken a whole group of background work ahead of the
-  // pieces that merely have to be done some columns later (with the early pieces of group q - 1 in front of them, the diagonal
-  // accumulation was taken 30 us before it was needed and the chain waited 20 us for it every few columns)
-  sect("contraction lists, pieces");
-  { size_t recs = 0; for (int g = 0; g < nt; g++) recs += finals[g].size() + early[g].size(); df.h_tasks.reserve(6 * recs); }
-  auto put1 = [&](const Rec& t) { const int32_t f[6] = {t.I, t.J, t.koff, t.kcnt, t.r, t.R}; df.h_tasks.insert(df.h_tasks.end(), f, f + 6); };
-  auto put = [&](const std::vector<Rec>& v) { for (const Rec& t : v) put1(t); };
-  // One chain: the two tasks of a column that the serial chain waits for -- PD(J) and the tile right below the diagonal tile -- are
-  // queued one group EARLIER than the rest of their column, in front of the previous group's burst of early pieces (and behind their
-  // own early pieces of that burst, so that a task still only waits for smaller tickets).  A burst is several hundred pieces of
-  // ~100 us: behind it PD(J) was taken 12 - 30 us too late on every sixth column of the L1723 shape and the chain period stretched
-  // from 40 to 60 - 76 us (round 4 trace: 19 of 121 periods, 0.4 ms of 5.2).  Taken early the two tasks just hold two of the 248
-  // workgroups a period longer.
-  // (pulled with the diagonal tile: the kNearRows tiles below it; measured on L1723 in round 4, with last pieces of 4 steps everywhere: 0 rows
-  // below 5.17 ms, 1 row 5.17, 3 rows 5.19; no pulling at all 5.30)
-  const int pull_rows = tree ? -1 : kNearRows;
-  const bool pull = pull_rows >= 0;
-  auto critical = [&](const Rec& t, int c) { return t.J == c && t.I >= c && t.I <= c + pull_rows && t.I < nt; };
-  // PD(c) itself goes one group further ahead (round 5): its last piece -- two contraction steps, 36 us, the second one streaming behind the
-  // substitution of tile (c, c - 2) -- was still taken only 20 - 25 us before the chain needed it on some columns of the L1723 shape
-  // (230 tickets behind the tile (c, c - 1) of the group before: profiles/r05i trace).  Allowed when all its early pieces sit in groups
-  // <= q - 1 (they are queued in front of it then: a task still only waits for smaller tickets; its operand tiles (c, c - 3), (c, c - 2)
-  // belong to columns <= q, whose own tasks are queued by then).
-  std::vector<char> pulled(nt + 1, 0), pd_out(nt + 2, 0);
-  auto is_pd = [&](const Rec& t, int c) { return t.I == c && t.J == c; };
-  for (int q = 0; q < nt; q++) {
-    for (const Rec& t : finals[q]) { if (pulled[q] && critical(t, q)) continue; put1(t); }
-    if (q >= 1) {
-      const int c = q + 1, c2 = q + 2;            // the columns whose critical tasks are pulled in front of early[q - 1]
-      if (pull && c < nt) {
-        const bool pd2 = c2 < nt && diag_last_g[c2] <= q - 1;
-        for (const Rec& t : early[q - 1]) if (critical(t, c) || (pd2 && is_pd(t, c2))) put1(t);
-        for (const Rec& t : finals[c]) if (critical(t, c) && !(is_pd(t, c) && pd_out[c])) put1(t);
-        pulled[c] = 1;
-        if (pd2) { for (const Rec& t : finals[c2]) if (is_pd(t, c2)) put1(t); pd_out[c2] = 1; }
-        for (const Rec& t : early[q - 1]) if (!(critical(t, c) || (pd2 && is_pd(t, c2)))) put1(t);
-      } else put(early[q - 1]);
-    }
-  }
-  put(early[nt - 1]);
-  df.nt = nt; df.n_tasks = (int64_t)df.h_tasks.size() / 6;
-  df.flops = flops; df.dense_fraction = (double)stored / ((double)nt * (nt + 1) / 2.0);
-  if (df.h_klist.empty()) df.h_klist.push_back(0);
-  df.h_has_sub = has_sub;
-  sect("ticket order");
-}
-
+// ---- host: the plan's device copies ---------------------------------------------------------------------------------
+// The task lists come from tile_plan.cpp::plan_dataflow (pure host code: analysis.hip runs it beside build_chol_plan); here they are
+// resolved to slots -- which come from the stream schedule's plan -- and uploaded.  The tables are resolved on the host
+// (df_resolve_host) or, with d_slot = the device copy of `slot`, by k_df_resolve.
 void upload_df_plan(DfPlan& df, hipStream_t stream, const std::vector<int32_t>& slot, int64_t n_slots, const std::vector<uint64_t>* sub16, const int32_t* d_slot) {
   const int nt = df.nt;
-  const std::vector<int32_t>& has_sub = df.h_has_sub;
-  // Device form: tiles AND their flag words are addressed by SLOT (context.h::SMat; the slots come from the stream schedule's plan,
-  // whose stored set -- fill at the granularity of column pairs -- contains this one).  A task carries the slots of its tile and of
-  // its diagonal tile, a contraction step the slots of its two operand tiles; h_tasks / h_klist keep the tile coordinates (debug
-  // getters, tests/test_chol_plan.py).
-  auto slot_of = [&](int I, int J) {
-    const int32_t q = slot[(size_t)I * nt + J];
-    if (q < 0) throw std::runtime_error("dataflow plan: a tile of the task list has no slot in the stored-tile list");
-    return q;
-  };
-  {
-    // accumulator lanes of the tiles with very long contraction lists (run_task): G - 1 scratch slots each, behind the stored tiles
-    constexpr int lane_min = 8;   // early pieces from which a tile gets lanes
-    constexpr int lane_max = 8;
-    std::map<int32_t, std::pair<int32_t, int32_t>> lanes;   // slot of the tile -> (G, first scratch slot)
-    df.n_scratch = 0;
-    for (int64_t t = 0; t < df.n_tasks; t++) {
-      const int32_t* d = df.h_tasks.data() + 6 * t;
-      const int E = d[5] - 1;
-      if (d[4] != d[5] - 1 || E < lane_min || lane_max < 2) continue;       // (looked at once per tile: at its final piece)
-      const int G = std::min(lane_max, E / 4);
-      if (G < 2) continue;
-      lanes[slot_of(d[0], d[1])] = {G, (int32_t)(n_slots + df.n_scratch)};
-      df.n_scratch += G - 1;
-    }
-    // sub-tile masks of a contraction step's operand tiles (analysis.hip: strip-level symbolic factorisation; none = every sub-tile): the
-    // right-hand-side row has one row of sub-tiles
-    auto mask_of = [&](int I, int k) -> uint64_t { return I >= nt ? 0xFFull : sub16 ? (*sub16)[(size_t)I * nt + k] : ~0ull; };
-    double skipped = 0.0;
-    if (d_slot && df.n_tasks >= 1024 && !getenv("GTG_HOST_SYMBOLIC")) {
-      // On the DEVICE (k_df_resolve, one lane per task; d_slot = the device copy of `slot`): the host lists go up as they are (6 words per
-      // task, one per step) instead of the resolved tables (12 and 6 words), and the 64 x 64 bit products of the skipped-MFMA count run
-      // there as well (2.4 ms of host loop on the L1723 shape).  GTG_HOST_SYMBOLIC=1 keeps the loop below: same tables, same count
-      // (tests/test_gpu_device_analysis.py); so do the dry-run runtime of the CPU tests and small plans.
-      std::vector<int32_t> lane_tab(2 * (size_t)n_slots);
-      for (int64_t q = 0; q < n_slots; q++) { lane_tab[2 * q] = 1; lane_tab[2 * q + 1] = -1; }
-      for (const auto& kv : lanes) { lane_tab[2 * (size_t)kv.first] = kv.second.first; lane_tab[2 * (size_t)kv.first + 1] = kv.second.second; }
-      auto al = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
-      const size_t b_t6 = al(4 * df.h_tasks.size()), b_kl = al(4 * df.h_klist.size()), b_lane = al(4 * lane_tab.size()), b_sub = sub16 ? al(8 * sub16->size()) : 0;
-      DevBuf<unsigned char> ws; ws.alloc(b_t6 + b_kl + b_lane + b_sub + 256);
-      int32_t* d_t6 = reinterpret_cast<int32_t*>(ws.p); int32_t* d_kl = reinterpret_cast<int32_t*>(ws.p + b_t6);
-      int32_t* d_lane = reinterpret_cast<int32_t*>(ws.p + b_t6 + b_kl);
-      unsigned long long* d_sub = sub16 ? reinterpret_cast<unsigned long long*>(ws.p + b_t6 + b_kl + b_lane) : nullptr;
-      unsigned long long* d_acc = reinterpret_cast<unsigned long long*>(ws.p + b_t6 + b_kl + b_lane + b_sub);
-      check_hip(hipMemcpyAsync(d_t6, df.h_tasks.data(), 4 * df.h_tasks.size(), hipMemcpyHostToDevice, stream), "H2D");
-      check_hip(hipMemcpyAsync(d_kl, df.h_klist.data(), 4 * df.h_klist.size(), hipMemcpyHostToDevice, stream), "H2D");
-      check_hip(hipMemcpyAsync(d_lane, lane_tab.data(), 4 * lane_tab.size(), hipMemcpyHostToDevice, stream), "H2D");
-      if (sub16) check_hip(hipMemcpyAsync(d_sub, sub16->data(), 8 * sub16->size(), hipMemcpyHostToDevice, stream), "H2D");
-      check_hip(hipMemsetAsync(d_acc, 0, 16, stream), "memset");
-      df.tasks.alloc(12 * (size_t)df.n_tasks); df.klist.alloc(kStepWords * df.h_klist.size());
-      hipLaunchKernelGGL(k_df_resolve, dim3((unsigned)((df.n_tasks + 255) / 256)), dim3(256), 0, stream, df.n_tasks, nt, d_t6, d_kl, d_slot, d_sub, d_lane,
-                         df.tasks.p, df.klist.p, d_acc);
-      check_hip(hipGetLastError(), "df plan resolve");
-      unsigned long long acc[2] = {0, 0};
-      check_hip(hipMemcpyAsync(acc, d_acc, 16, hipMemcpyDeviceToHost, stream), "D2H");
-      check_hip(hipStreamSynchronize(stream), "df plan resolve");
-      if (acc[1]) throw std::runtime_error("dataflow plan: a tile of the task list has no slot in the stored-tile list");
-      skipped = (double)acc[0] * 0.5 * 2048.0;
-    } else {
-    std::vector<int32_t> dt; dt.reserve((size_t)df.n_tasks * 12);
-    std::vector<int32_t> dk(kStepWords * df.h_klist.size(), 0);
-    std::vector<uint8_t> seen(df.h_klist.size(), 0);
-    for (int64_t t = 0; t < df.n_tasks; t++) {
-      const int32_t* d = df.h_tasks.data() + 6 * t;
-      const int I = d[0], J = d[1];
-      for (int x = 0; x < 6; x++) dt.push_back(d[x]);
-      dt.push_back(slot_of(I, J)); dt.push_back(slot_of(J, J));
-      { const auto it = lanes.find(slot_of(I, J)); dt.push_back(it == lanes.end() ? 1 : it->second.first); dt.push_back(it == lanes.end() ? -1 : it->second.second); }
-      { const uint64_t m = I == J ? ~0ull : mask_of(I, J); dt.push_back((int32_t)(uint32_t)m); dt.push_back((int32_t)(uint32_t)(m >> 32)); }   // sub-tile mask of the tile itself (substitute)
-      for (int32_t e = d[2]; e < d[2] + d[3]; e++) {   // (the pieces of a tile share one list: every entry is visited once)
-        const int k = df.h_klist[e];
-        int32_t* w = dk.data() + kStepWords * (size_t)e;
-        const uint64_t ma = mask_of(I, k), mb = mask_of(J, k);
-        w[0] = slot_of(I, k); w[1] = slot_of(J, k);
-        w[2] = (int32_t)(uint32_t)ma; w[3] = (int32_t)(uint32_t)(ma >> 32); w[4] = (int32_t)(uint32_t)mb; w[5] = (int32_t)(uint32_t)(mb >> 32);
-        if (!seen[e]) {   // MFMAs the step leaves out: per 16-column strip (row tiles with a live A sub-tile) x (column tiles with a live B sub-tile), 4 each
-          int live = 0;
-          for (int sp = 0; sp < 8; sp++) live += 4 * __builtin_popcountll(ma & (0x0101010101010101ull << sp)) * __builtin_popcountll(mb & (0x0101010101010101ull << sp));
-          const int rows = I >= nt ? 1 : 8;   // (the flop count has always taken the right-hand-side row as a full tile row; its 7 idle row tiles are not counted as skipped work here)
-          skipped += (I == J ? 0.5 : 1.0) * (double)(4 * 8 * rows * 8 - live) * 2048.0 * (I >= nt ? 0.0 : 1.0);
-        }
-        seen[e] = 1;
-      }
-    }
-    df.tasks.upload(dt.data(), dt.size(), stream);
-    df.klist.upload(dk.data(), dk.size(), stream);
-    }
-    df.flops_executed = df.flops - skipped;
-    std::vector<int32_t> cs(kChainWords * (size_t)nt, -1);
-    for (int J = 0; J < nt; J++) {
-      cs[kChainWords * J] = slot_of(J, J);
-      if (has_sub[J] & 1) {
-        cs[kChainWords * J + 1] = slot_of(J, J - 1);
-        const uint64_t m = mask_of(J, J - 1);
-        cs[kChainWords * J + 2] = (int32_t)(uint32_t)m; cs[kChainWords * J + 3] = (int32_t)(uint32_t)(m >> 32);
-      }
-    }
-    df.has_sub.upload(cs.data(), cs.size(), stream);   // (per diagonal tile: kChainWords)
-    check_hip(hipStreamSynchronize(stream), "df plan upload");
+  const std::vector<int32_t> lane_tab = df_lane_table(df, slot, n_slots);
+  double skipped = 0.0;
+  if (d_slot && df.n_tasks >= 1024 && !getenv("GTG_HOST_SYMBOLIC")) {
+    // On the DEVICE (k_df_resolve, one lane per task): the host lists go up as they are (6 words per task, one per step) instead of the
+    // resolved tables (12 and 6 words), and the 64 x 64 bit products of the skipped-MFMA count run there as well (2.4 ms of host loop on
+    // the L1723 shape).  GTG_HOST_SYMBOLIC=1 keeps the host loop: same tables, same count (tests/test_gpu_device_analysis.py); so do the
+    // dry-run runtime of the CPU tests and small plans.
+    auto al = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    const size_t b_t6 = al(4 * df.h_tasks.size()), b_kl = al(4 * df.h_klist.size()), b_lane = al(4 * lane_tab.size()), b_sub = sub16 ? al(8 * sub16->size()) : 0;
+    DevBuf<unsigned char> ws; ws.alloc(b_t6 + b_kl + b_lane + b_sub + 256);
+    int32_t* d_t6 = reinterpret_cast<int32_t*>(ws.p); int32_t* d_kl = reinterpret_cast<int32_t*>(ws.p + b_t6);
+    int32_t* d_lane = reinterpret_cast<int32_t*>(ws.p + b_t6 + b_kl);
+    unsigned long long* d_sub = sub16 ? reinterpret_cast<unsigned long long*>(ws.p + b_t6 + b_kl + b_lane) : nullptr;
+    unsigned long long* d_acc = reinterpret_cast<unsigned long long*>(ws.p + b_t6 + b_kl + b_lane + b_sub);
+    check_hip(hipMemcpyAsync(d_t6, df.h_tasks.data(), 4 * df.h_tasks.size(), hipMemcpyHostToDevice, stream), "H2D");
+    check_hip(hipMemcpyAsync(d_kl, df.h_klist.data(), 4 * df.h_klist.size(), hipMemcpyHostToDevice, stream), "H2D");
+    check_hip(hipMemcpyAsync(d_lane, lane_tab.data(), 4 * lane_tab.size(), hipMemcpyHostToDevice, stream), "H2D");
+    if (sub16) check_hip(hipMemcpyAsync(d_sub, sub16->data(), 8 * sub16->size(), hipMemcpyHostToDevice, stream), "H2D");
+    check_hip(hipMemsetAsync(d_acc, 0, 16, stream), "memset");
+    df.tasks.alloc(kTaskWords * (size_t)df.n_tasks); df.klist.alloc(kStepWords * df.h_klist.size());
+    hipLaunchKernelGGL(k_df_resolve, dim3((unsigned)((df.n_tasks + 255) / 256)), dim3(256), 0, stream, df.n_tasks, nt, d_t6, d_kl, d_slot, d_sub, d_lane,
+                       df.tasks.p, df.klist.p, d_acc);
+    check_hip(hipGetLastError(), "df plan resolve");
+    unsigned long long acc[2] = {0, 0};
+    check_hip(hipMemcpyAsync(acc, d_acc, 16, hipMemcpyDeviceToHost, stream), "D2H");
+    check_hip(hipStreamSynchronize(stream), "df plan resolve");
+    if (acc[1]) throw std::runtime_error("dataflow plan: a tile of the task list has no slot in the stored-tile list");
+    skipped = (double)acc[0] * 0.5 * 2048.0;
+  } else {
+    const DfTables t = df_resolve_host(df, slot, sub16, lane_tab);
+    df.tasks.upload(t.tasks.data(), t.tasks.size(), stream);
+    df.klist.upload(t.steps.data(), t.steps.size(), stream);
+    skipped = t.skipped;
   }
+  df.flops_executed = df.flops - skipped;
+  const std::vector<int32_t> cs = df_chain_words(df, slot, sub16);
+  df.has_sub.upload(cs.data(), cs.size(), stream);   // (per diagonal tile: kChainWords)
+  check_hip(hipStreamSynchronize(stream), "df plan upload");
   df.chain_off.upload(df.h_chain_off.data(), df.h_chain_off.size(), stream);
   df.chain_tiles.upload(df.h_chain_tiles.data(), df.h_chain_tiles.size(), stream);
-  df.shadow = (n_slots + df.n_scratch + 511) / 512 * 512;   // flag words by slot, the scratch slots of the accumulator lanes included (the name is from rounds 3 - 5, when every flag had a shadow word this far behind it)
-  df.tile_flag.alloc((size_t)df.shadow); df.part_flag.alloc((size_t)df.shadow); df.pd_flag.alloc((size_t)df.shadow); df.ctrl.alloc(32);
+  df.n_flag_words = (n_slots + df.n_scratch + 511) / 512 * 512;   // flag words by slot, the scratch slots of the accumulator lanes included
+  df.tile_flag.alloc((size_t)df.n_flag_words); df.part_flag.alloc((size_t)df.n_flag_words); df.pd_flag.alloc((size_t)df.n_flag_words); df.ctrl.alloc(32);
   if (getenv("GTG_DF_TRACE")) { df.trace.alloc(8 * (size_t)df.n_tasks + 66 * (size_t)nt); check_hip(hipMemsetAsync(df.trace.p, 0, sizeof(long long) * df.trace.n, stream), "memset"); }
   check_hip(hipMemsetAsync(df.tile_flag.p, 0, sizeof(long long) * df.tile_flag.n, stream), "memset");
   check_hip(hipMemsetAsync(df.pd_flag.p, 0, sizeof(long long) * df.pd_flag.n, stream), "memset");

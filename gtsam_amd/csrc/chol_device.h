@@ -3,7 +3,8 @@
 // panel (chain wavefront + followers) and the diagonal-tile body built from it.
 #pragma once
 // (GT_KERNEL_EMU: tools/kernel_emu compiles this header for the host -- one thread per work-item -- and supplies the device vocabulary,
-// the constants of context.h it needs and the three macros below itself)
+// and the macros below itself)
+#include "tile_plan.h"   // kTile, kTileDoubles: host-only, includable in the emulation as well
 #ifndef GT_KERNEL_EMU
 #include "kernels.h"
 #define GT_PIN(x) asm volatile("" : "+v"(x))                           // keeps a value in its register at this point of the schedule

@@ -172,8 +172,7 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 // XCD-aware tile order: workgroup b runs on XCD b % 8 (MI355X_MICROARCH.md).  The host emits the (I,J) tile list
 // of an update in 8x4-tile supertile order; each XCD takes one contiguous eighth of that list, so the 32
 // workgroups resident on one XCD share a few row/column panels in that XCD's 4 MiB L2 instead of streaming
-// 2 x 256 KB per tile from HBM.
-constexpr int STI = 8, STJ = 4;
+// 2 x 256 KB per tile from HBM.  (STI x STJ: tile_plan.h, where the lists are sorted)
 
 // Wave geometry: a wavefront can keep only ONE v_mfma_f64_16x16x4_f64 in flight (measured issue interval per wave
 // 138 cycles, tools/mfma_f64_peak.hip: 36 TFLOP/s at 1 wave/SIMD, 47 at 2, 70 at 4), so the matrix pipe needs
@@ -277,158 +276,24 @@ static inline int syrk_grid(int64_t npairs) { return (int)(((npairs + 7) / 8) * 
 constexpr int64_t kLatencyTiles = 320;   // launches up to this many tiles use the quadrant (latency) variant of k_syrk
 
 // ---- host: tile schedule ------------------------------------------------------------------------------------
-// Symbolic factorisation at the granularity of 256-wide column pairs (the unit the trailing update contracts
-// over), then the per-pair tile lists.  This is the reduced system's elimination structure: what the reference
-// rebuilds as EliminationTree + JunctionTree on every lambda try (inference/EliminationTree-inst.h:77-155,
-// JunctionTree-inst.h:63-151), computed once here.
+// The lists come from the planner (tile_plan.cpp::plan_chol, plan_stream_pairs); here they go to the device.
 void build_chol_plan(CholPlan& plan, int nt, const std::vector<uint8_t>* pair_struct, hipStream_t stream,
                      const std::vector<int32_t>* pair_part, const std::vector<int32_t>* part_parent) {
-  const int np = (nt + 1) / 2;
-  const bool tree = pair_part && !pair_part->empty();
-  plan.pair_part.clear(); plan.part_parent.clear();
-  if (tree) { plan.pair_part = *pair_part; plan.part_parent = *part_parent; }
-  plan.anc_off.assign(np, 0); plan.anc_cnt.assign(np, 0);
-  std::vector<uint8_t> B((size_t)np * np, 0);
-  for (int q = 0; q < np; q++)
-    for (int p = 0; p <= q; p++) B[(size_t)q * np + p] = pair_struct ? (*pair_struct)[(size_t)q * np + p] : 1;
-  for (int p = 0; p < np; p++) B[(size_t)p * np + p] = 1;
-  for (int p = 0; p < np; p++) {   // symbolic elimination: the rows of column p become a clique
-    std::vector<int> r;
-    for (int q = p + 1; q < np; q++) if (B[(size_t)q * np + p]) r.push_back(q);
-    for (size_t a = 0; a < r.size(); a++)
-      for (size_t b = 0; b <= a; b++) B[(size_t)r[a] * np + r[b]] = 1;
-  }
-  auto tiles_of = [&](int q, std::vector<int32_t>& out) { out.push_back(2 * q); if (2 * q + 1 < nt) out.push_back(2 * q + 1); };
-  std::vector<int32_t> rows, pairs, bcols, stored_list;
-  plan.nt = nt;
-  plan.trsm_off.assign(nt, 0); plan.trsm_cnt.assign(nt, 0);
-  plan.s1_off.assign(np, 0); plan.s1_cnt.assign(np, 0); plan.nar_off.assign(np, 0); plan.nar_cnt.assign(np, 0);
-  plan.rest_off.assign(np, 0); plan.rest_cnt.assign(np, 0);
-  plan.bwd_off.assign(nt, 0); plan.bwd_cnt.assign(nt, 0);
-  const double t3 = (double)T * T * T;
-  double flops = 0.0; int64_t stored = 0;
-  // (the SYRK pair lists of the stream schedule -- a sorted list of (I, J) per column pair, 0.4 M entries on the L1723 shape -- are built
-  // by ensure_stream_lists when that schedule, the fall-back and A/B of the dataflow pass, is first used: 0.5 of this function's 0.7 ms)
-  plan.h_fill = B; plan.stream_lists = false;
-  for (int p = 0; p < np; p++) {
-    const int k = 2 * p; const bool two = k + 1 < nt;
-    std::vector<int32_t> R;
-    for (int q = p + 1; q < np; q++) if (B[(size_t)q * np + p]) tiles_of(q, R);
-    stored += (two ? 3 : 1) + (int64_t)R.size() * (two ? 2 : 1);
-    for (int cc = k; cc <= (two ? k + 1 : k); cc++) {
-      for (int rr = cc; rr <= (two ? k + 1 : k); rr++) { stored_list.push_back(rr); stored_list.push_back(cc); }
-      for (int32_t I : R) { stored_list.push_back(I); stored_list.push_back(cc); }
-      stored_list.push_back(nt); stored_list.push_back(cc);
-    }
-    // column k: rows below = [k+1] + R + [rhs]
-    plan.trsm_off[k] = (int64_t)rows.size();
-    if (two) rows.push_back(k + 1);
-    rows.insert(rows.end(), R.begin(), R.end()); rows.push_back(nt);
-    plan.trsm_cnt[k] = (int64_t)rows.size() - plan.trsm_off[k];
-    flops += t3 / 3.0 + (double)(plan.trsm_cnt[k] - 1) * t3;
-    if (two) {
-      flops += (double)((int64_t)R.size() + 1) * 2.0 * t3;     // (the thin update's pairs: (k + 1, k + 1), (I, k + 1) for I in R; the rhs row's excluded)
-      plan.trsm_off[k + 1] = (int64_t)rows.size();
-      rows.insert(rows.end(), R.begin(), R.end()); rows.push_back(nt);
-      plan.trsm_cnt[k + 1] = (int64_t)rows.size() - plan.trsm_off[k + 1];
-      flops += t3 / 3.0 + (double)(plan.trsm_cnt[k + 1] - 1) * t3;
-    }
-    const double kk = two ? 2.0 : 1.0;
-    flops += (double)((int64_t)R.size() * ((int64_t)R.size() + 1) / 2) * 2.0 * t3 * kk;   // rhs row excluded
-  }
-  for (int kt = 0; kt < nt; kt++) {   // backward solve: non-zero column tiles of row tile kt
-    plan.bwd_off[kt] = (int64_t)bcols.size();
-    const int q = kt / 2;
-    for (int p = 0; p < q; p++) if (B[(size_t)q * np + p]) tiles_of(p, bcols);
-    if (kt & 1) bcols.push_back(kt - 1);
-    plan.bwd_cnt[kt] = (int64_t)bcols.size() - plan.bwd_off[kt];
-  }
-  {   // the same tiles by column, rows descending: what the one-launch backward sweep walks
-    std::vector<std::vector<int32_t>> by_col(nt);
-    for (int kt = nt - 1; kt >= 0; kt--)
-      for (int64_t e = plan.bwd_off[kt]; e < plan.bwd_off[kt] + plan.bwd_cnt[kt]; e++) by_col[bcols[e]].push_back(kt);
-    std::vector<int32_t> off(nt + 1, 0), list;
-    for (int jt = 0; jt < nt; jt++) { list.insert(list.end(), by_col[jt].begin(), by_col[jt].end()); off[jt + 1] = (int32_t)list.size(); }
-    if (list.empty()) list.push_back(0);
-    plan.bwd_col_off.upload(off.data(), off.size(), stream);
-    plan.bwd_col_rows.upload(list.data(), list.size(), stream);
-  }
-  plan.critical_pairs = np;
-  if (tree) {   // longest leaf-to-root path in pairs
-    const int nparts = (int)plan.part_parent.size();
-    std::vector<int> len(nparts, 0), path(nparts, 0);
-    for (int p = 0; p < np; p++) len[plan.pair_part[p]]++;
-    int best = 0;
-    for (int x = nparts - 1; x >= 0; x--) {   // parents have larger indices: walk down from the root
-      const int par = plan.part_parent[x];
-      path[x] = len[x] + (par >= 0 ? path[par] : 0);
-      best = std::max(best, path[x]);
-    }
-    plan.critical_pairs = best;
-  }
-  plan.flops = flops;
-  plan.dense_fraction = (double)stored / ((double)nt * (nt + 1) / 2.0);
-  if (rows.empty()) rows.push_back(0);
-  if (bcols.empty()) bcols.push_back(0);
-  plan.rows.upload(rows.data(), rows.size(), stream);
+  const CholTables t = plan_chol(plan, nt, pair_struct, pair_part, part_parent);
+  plan.bwd_col_off.upload(t.bwd_col_off.data(), t.bwd_col_off.size(), stream);
+  plan.bwd_col_rows.upload(t.bwd_col_rows.data(), t.bwd_col_rows.size(), stream);
+  plan.rows.upload(t.rows.data(), t.rows.size(), stream);
   plan.pairs.free();
-  plan.bcols.upload(bcols.data(), bcols.size(), stream);
-  plan.n_stored = (int64_t)stored_list.size() / 2;
-  plan.stored.upload(stored_list.data(), stored_list.size(), stream);
-  // tile -> slot (chol_device.h::SMat): the stored tiles in list order
-  plan.h_slot.assign((size_t)(nt + 1) * nt, -1);
-  for (int64_t q = 0; q < plan.n_stored; q++) {
-    int32_t& sl = plan.h_slot[(size_t)stored_list[2 * q] * nt + stored_list[2 * q + 1]];
-    if (sl >= 0) throw std::runtime_error("cholesky plan: a tile is listed twice");
-    sl = (int32_t)q;
-  }
+  plan.bcols.upload(t.bcols.data(), t.bcols.size(), stream);
+  plan.stored.upload(t.stored.data(), t.stored.size(), stream);
   plan.slot.upload(plan.h_slot.data(), plan.h_slot.size(), stream);
   check_hip(hipStreamSynchronize(stream), "plan upload");
 }
 
-// The stream schedule's SYRK pair lists (see build_chol_plan), from the fill structure the plan keeps: per column pair p the thin update
-// of its second column (s1), the look-ahead part of the trailing update (targets in pair p + 1: nar), the rest, and -- with parts -- the
-// targets in ancestor parts (anc); every list in supertile order.
+// The stream schedule's SYRK pair lists, built on its first use (the fall-back and A/B of the dataflow pass)
 void ensure_stream_lists(CholPlan& plan, hipStream_t stream) {
   if (plan.stream_lists) return;
-  const int nt = plan.nt, np = (nt + 1) / 2;
-  const bool tree = !plan.pair_part.empty();
-  const std::vector<uint8_t>& B = plan.h_fill;
-  std::vector<int32_t> pairs;
-  auto tiles_of = [&](int q, std::vector<int32_t>& out) { out.push_back(2 * q); if (2 * q + 1 < nt) out.push_back(2 * q + 1); };
-  auto emit_pairs = [&](std::vector<std::pair<int32_t, int32_t>>& v, int64_t& off, int64_t& cnt) {
-    // supertile order: (J / STJ, I / STI, J % STJ, I % STI)
-    std::sort(v.begin(), v.end(), [](const std::pair<int32_t, int32_t>& a, const std::pair<int32_t, int32_t>& b) {
-      const int64_t ka = (((int64_t)(a.second / STJ) * 65536 + a.first / STI) * STJ + a.second % STJ) * STI + a.first % STI;
-      const int64_t kb = (((int64_t)(b.second / STJ) * 65536 + b.first / STI) * STJ + b.second % STJ) * STI + b.first % STI;
-      return ka < kb; });
-    off = (int64_t)pairs.size() / 2; cnt = (int64_t)v.size();
-    for (auto& ij : v) { pairs.push_back(ij.first); pairs.push_back(ij.second); }
-  };
-  for (int p = 0; p < np; p++) {
-    const int k = 2 * p; const bool two = k + 1 < nt;
-    std::vector<int32_t> R;
-    for (int q = p + 1; q < np; q++) if (B[(size_t)q * np + p]) tiles_of(q, R);
-    if (two) {
-      std::vector<std::pair<int32_t, int32_t>> s1;
-      s1.emplace_back(k + 1, k + 1);
-      for (int32_t I : R) s1.emplace_back(I, k + 1);
-      s1.emplace_back(nt, k + 1);
-      emit_pairs(s1, plan.s1_off[p], plan.s1_cnt[p]);
-    }
-    std::vector<std::pair<int32_t, int32_t>> nar, rest, anc;
-    for (size_t b = 0; b < R.size(); b++) {
-      const int32_t J = R[b];
-      // with parts: targets in another part can only be in an ancestor (no tiles between independent subtrees)
-      auto& dst = (tree && plan.pair_part[J / 2] != plan.pair_part[p]) ? anc : (J / 2 == p + 1) ? nar : rest;
-      for (size_t a = b; a < R.size(); a++) dst.emplace_back(R[a], J);
-      dst.emplace_back(nt, J);
-    }
-    emit_pairs(nar, plan.nar_off[p], plan.nar_cnt[p]);
-    emit_pairs(rest, plan.rest_off[p], plan.rest_cnt[p]);
-    emit_pairs(anc, plan.anc_off[p], plan.anc_cnt[p]);
-  }
-  if (pairs.empty()) { pairs.push_back(0); pairs.push_back(0); }
+  const std::vector<int32_t> pairs = plan_stream_pairs(plan);
   plan.pairs.upload(pairs.data(), pairs.size(), stream);
   check_hip(hipStreamSynchronize(stream), "plan upload");
   plan.stream_lists = true;
@@ -499,12 +364,12 @@ void launch_pack_tiles(gtg_context& c, SMat S, const CholPlan& plan, double* buf
 // when it is needed, so it costs one barrier packet (~3 us measured) instead of a fresh signal round trip (~13 us).
 // rest(p) starts after nar(p) so that the two never share CUs (two small MFMA launches side by side double each
 // other's latency).  panel(k) is ONE launch (k_panel128): the diagonal tile and, streamed behind it, the TRSM below.
-void launch_cholesky(gtg_context& c, SMat S, int NP, const CholPlan& plan, double* Xinv, double* fail,
+void launch_cholesky(gtg_context& c, SMat S, int NP, CholPlan& plan, double* Xinv, double* fail,
                      const unsigned char* pivot_kind, double* tile_exp) {
   CholStreams& g_cs = c.cs;
   const int nt = NP / T;
   if (plan.nt != nt) throw std::runtime_error("cholesky plan does not match the matrix");
-  ensure_stream_lists(const_cast<CholPlan&>(plan), c.stream);   // (the pair lists are this schedule's alone: built on its first use)
+  ensure_stream_lists(plan, c.stream);   // (the pair lists are this schedule's alone: built on its first use)
   const size_t smem_potrf = sizeof(double) * kPotrfSmemDoubles;
   const size_t smem_trsm = sizeof(double) * (TR * P);
   const size_t smem_syrk = 4 * (size_t)CHB;

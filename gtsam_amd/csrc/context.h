@@ -20,12 +20,9 @@
 #include <vector>
 
 #include "../../include/gtsam_amd.h"
+#include "tile_plan.h"   // kTile, kSub; CholLists / DfLists: the host halves of the two plans below
 
 namespace gt {
-
-constexpr int kTile = 128;  // dense tile / panel width of the reduced-system Cholesky
-constexpr int kTileDoubles = kTile * kTile;
-constexpr int kSub = 16;    // granularity of the structural masks of a tile (one MFMA tile: 8 x 8 bits per 128 x 128 tile; DfPlan, analysis.hip)
 
 // ---- storage of the reduced system: BY TILES -----------------------------------------------------------------------------
 // Every 128 x 128 tile of the lower triangle that the symbolic factorisation says can become non-zero (fill included), and every
@@ -83,57 +80,29 @@ struct DevBuf {
 // which 128x128 tiles exist after fill-in, at the granularity of 256-wide column pairs.
 constexpr int kEStride = 32;                    // doubles per E slot (one per observation): 9x3 block padded to 256 bytes = two 128-byte lines
 
-struct CholPlan {
-  int nt = 0;                                   // 128-tiles of the square part (the rhs tile is index nt)
+struct CholPlan : CholLists {                    // + the device copies (tile_plan.h: the host half and the planner)
   DevBuf<int32_t> rows, pairs, bcols;           // concatenated lists: TRSM row tiles, SYRK (I,J) pairs, backward column tiles
   DevBuf<int32_t> bwd_col_off, bwd_col_rows;    // the backward tiles by column: offsets (nt + 1), row tiles in descending order
   DevBuf<int32_t> stored;                       // every stored tile (I,J) incl. the rhs row, in SLOT order: tile q of this list lives in slot q of S
-  int64_t n_stored = 0;
-  DevBuf<int32_t> slot;                         // (nt + 1) x nt: tile (I, J) -> its slot in S, -1 = never touched (chol_device.h::SMat)
-  std::vector<int32_t> h_slot;
+  DevBuf<int32_t> slot;                         // (nt + 1) x nt: tile (I, J) -> its slot in S, -1 = never touched (chol_device.h::SMat); h_slot on the device
   DevBuf<int32_t> exch;                         // the stored tiles that can be non-zero BEFORE the factorisation (no fill): what a multi-GPU
-  int64_t n_exch = 0;                           // exchange of the partial reduced systems has to carry (L1723: 19 % fewer than `stored`)
-  std::vector<int64_t> trsm_off, trsm_cnt;      // per column tile
-  std::vector<int64_t> s1_off, s1_cnt, nar_off, nar_cnt, rest_off, rest_cnt;   // per pair: thin update, look-ahead part, rest
-  std::vector<int64_t> bwd_off, bwd_cnt;        // per row tile
-  // nested dissection: part of every 256-column pair (parts numbered in elimination order, children before parents),
-  // parent part (-1: root); updates of a pair whose target columns lie in an ancestor part
-  std::vector<int32_t> pair_part, part_parent;
-  std::vector<int64_t> anc_off, anc_cnt;
-  std::vector<uint8_t> h_fill;                 // the fill structure over column pairs ((np x np) bytes): what ensure_stream_lists builds the SYRK pair lists from
-  bool stream_lists = false;                    // `pairs` and the per-pair offsets are built (on first use of the stream schedule: cholesky.hip::ensure_stream_lists)
-  int critical_pairs = 0;                       // pairs on the longest leaf-to-root path (= all pairs without parts)
-  double flops = 0.0;                           // algorithmic flops of one factorisation over the stored tiles
-  double dense_fraction = 1.0;                  // stored lower tiles / all lower tiles
+                                                // exchange of the partial reduced systems has to carry (L1723: 19 % fewer than `stored`); n_exch of them
 };
 
 
 // Dataflow schedule of the same factorisation (chol_dataflow.hip): one task per stored 128x128 tile, left-looking, executed by
 // persistent workgroups that take tasks in a fixed topological order; dependencies are epoch-stamped flags in HBM.
-struct DfPlan {
-  int nt = 0;
-  int64_t n_tasks = 0;                          // bulk tasks: per block column J the diagonal accumulation PD(J), then the tiles (I, J) below, the rhs tile last
+struct DfPlan : DfLists {                       // + the device copies (tile_plan.h: the host half and the planner)
   DevBuf<int32_t> tasks;                        // 12 per task: I, J, offset / count into klist, piece r of R (the last piece finishes the tile), slots, accumulator lanes
-  int64_t n_scratch = 0;                        // scratch slots behind the stored tiles of S: the accumulator lanes 1.. of the tiles with very long contraction lists
-  DevBuf<long long> part_flag;                  // (nt + 1) x nt: kPieceBase epoch + pieces of the tile's contraction that are in
-  DevBuf<int32_t> has_sub;                      // per diagonal tile J: tile (J, J-1) is stored (its update is streamed by the chain kernel)
-  std::vector<int32_t> h_has_sub;
+  DevBuf<long long> part_flag;                  // n_flag_words, by slot: kPieceBase epoch + pieces of the tile's contraction that are in
+  DevBuf<int32_t> has_sub;                      // per diagonal tile J: kChainWords -- its slot, the slot of tile (J, J-1) where h_has_sub says it is stored (its update is streamed by the chain kernel) and that tile's sub-tile mask
   DevBuf<int32_t> klist;                        // contraction lists: the column tiles k < J with both (I, k) and (J, k) stored; 6 words per step: the two slots, then the
                                                 // 64-bit sub-tile masks of (I, k) and (J, k) (bit 8 r + q: rows 16 r.., columns 16 q.. can be non-zero)
-  DevBuf<long long> tile_flag;                  // (nt + 1) x nt: epoch in which the tile became final
-  DevBuf<long long> pd_flag;                    // nt: epoch in which the diagonal tile received all its updates
-  int64_t shadow = 0;                           // every flag is also stored `shadow` words behind its word (chol_dataflow.hip::st_flag)
+  DevBuf<long long> tile_flag;                  // by slot: epoch in which the tile became final
+  DevBuf<long long> pd_flag;                    // by slot: epoch in which the diagonal tile received all its updates
   DevBuf<int32_t> ctrl;                         // [0] ticket counter of the bulk queue; [8..15] record of the first wait that gave up
   DevBuf<long long> trace;                      // GTG_DF_TRACE=1: 4 stamps per task + 2 per diagonal tile (gtg_debug_df_trace)
-  std::vector<int32_t> h_tasks, h_klist;        // host copies (debug getters, CPU tests)
-  // the diagonal tiles by chain workgroup: workgroup w of k_df_chain factors chain_tiles[chain_off[w] .. chain_off[w + 1]) in that order.
-  // One slot = two workgroups that alternate; several slots when a nested-dissection ordering gave the factorisation independent parts
-  int n_chain = 0;
-  DevBuf<int32_t> chain_off, chain_tiles;
-  std::vector<int32_t> h_chain_off, h_chain_tiles, h_seq;   // h_seq: the order in which the block columns are taken (ticket groups)
-  int critical_tiles = 0;                       // diagonal tiles of the longest slot
-  double flops = 0.0, dense_fraction = 1.0;
-  double flops_executed = 0.0;                  // flops minus the contraction MFMAs skipped on structurally empty 16 x 16 sub-tiles (upload_df_plan)
+  DevBuf<int32_t> chain_off, chain_tiles;       // h_chain_off, h_chain_tiles on the device
 };
 
 // The form of the projection range: what its records look like and which kernels linearise and evaluate it.  Decided once per

@@ -24,15 +24,15 @@ void launch_back_substitute(gtg_context& c);     // delta_lm from xred, ylm, E, 
 void launch_scatter_delta(gtg_context& c);       // delta (variable id order) from xred + delta_lm
 
 // cholesky.hip ------------------------------------------------------------------------------------
-// Host: build the tile schedule.  pair_struct = lower-triangular boolean structure over 256-wide column pairs
-// ((np x np) row-major bytes, np = ceil(nt/2); nullptr = dense); symbolic fill-in is computed here.
+// Host: build the tile schedule (tile_plan.cpp::plan_chol) and upload it.  pair_struct = lower-triangular boolean structure over
+// 256-wide column pairs ((np x np) row-major bytes, np = ceil(nt/2); nullptr = dense); symbolic fill-in is computed there.
 void build_chol_plan(CholPlan& plan, int nt, const std::vector<uint8_t>* pair_struct, hipStream_t s,
                      const std::vector<int32_t>* pair_part = nullptr, const std::vector<int32_t>* part_parent = nullptr);
-void ensure_stream_lists(CholPlan& plan, hipStream_t s);   // the stream schedule's SYRK pair lists, built on its first use
+void ensure_stream_lists(CholPlan& plan, hipStream_t s);   // the stream schedule's SYRK pair lists (plan_stream_pairs), built on its first use
 // In-place tile-sparse blocked Cholesky of the NP x NP lower triangle of S (ld = NP) carrying one extra 128-row
 // tile (the rhs: forward solve for free).  Non-positive pivots set *fail_flag (device double) to nonzero.
 void launch_zero_tiles(gtg_context& c, SMat S, const CholPlan& plan);
-void launch_cholesky(gtg_context& c, SMat S, int NP, const CholPlan& plan, double* Xinv, double* fail_flag,
+void launch_cholesky(gtg_context& c, SMat S, int NP, CholPlan& plan, double* Xinv, double* fail_flag,   // (builds the plan's pair lists on first use)
                      const unsigned char* pivot_kind = nullptr, double* tile_exp = nullptr);
 // x = L^-T y  with L the factor in S, y = row NP of S. Result in x[0..NP).
 void launch_pack_tiles(gtg_context& c, SMat S, const CholPlan& plan, double* buf, bool unpack);
@@ -61,15 +61,12 @@ void exchange_sum(gtg_context& c, double* ptr, int64_t n);   // api.hip: all-red
 void launch_backward_solve(gtg_context& c, SMat S, int NP, const CholPlan& plan, const double* Xinv, double* x, double* fail);
 
 // chol_dataflow.hip -----------------------------------------------------------------------------------
-// The same factorisation as one dataflow pass of two persistent kernels (default schedule).  tile_struct = lower-triangular
-// boolean structure over 128x128 tiles before the factorisation ((nt x nt) row-major bytes; nullptr = dense).
-void build_df_plan(DfPlan& df, int nt, const std::vector<uint8_t>* tile_struct, hipStream_t s,
-                   const std::vector<int32_t>& slot, int64_t n_slots,     // tile -> slot table of the stored tiles (CholPlan::h_slot)
-                   const std::vector<int32_t>* tile_part = nullptr, const std::vector<int32_t>* part_parent = nullptr);
-void build_df_plan_host(DfPlan& df, int nt, const std::vector<uint8_t>* tile_struct,             // the host half (no runtime call)
-                        const std::vector<int32_t>* tile_part = nullptr, const std::vector<int32_t>* part_parent = nullptr);
+// The same factorisation as one dataflow pass of two persistent kernels (default schedule).
+// The task lists are built by tile_plan.cpp::plan_dataflow (host only); upload_df_plan resolves them to the slots of the stored tiles
+// (slot / n_slots: CholPlan::h_slot / n_stored) and makes the device copies (d_slot: the device copy of `slot` -- the tables are
+// resolved by a kernel then)
 void upload_df_plan(DfPlan& df, hipStream_t s, const std::vector<int32_t>& slot, int64_t n_slots, const std::vector<uint64_t>* sub16 = nullptr,
-                    const int32_t* d_slot = nullptr);   // the device half (d_slot: the device copy of `slot` -- the tables are resolved by a kernel then)
+                    const int32_t* d_slot = nullptr);
 void df_prepare_streams_async(int device, int n_chain);   // the masked stream pair of a plan with n_chain chain workgroups, created on a helper thread ahead of the first factorisation
 void df_join_prepared();                                       // (joined by the first factorisation and by gtg_destroy)
 bool dataflow_schedule_selected();   // false: GTG_CHOL=streams (the stream / event schedule of cholesky.hip, the A/B of the dataflow pass)

@@ -1,6 +1,6 @@
 """The symbolic phase of the reduced-system Cholesky, executed on the CPU.
 
-The library's tile schedule (csrc/cholesky.hip::build_chol_plan: symbolic fill at column-pair granularity, TRSM row lists,
+The library's tile schedule (csrc/tile_plan.cpp::plan_chol, uploaded by cholesky.hip::build_chol_plan: symbolic fill at column-pair granularity, TRSM row lists,
 thin / look-ahead / bulk / cross-part update lists, backward-solve lists, elimination-tree parts) is a set of index lists
 that do not depend on the tile size.  Here the real library builds them for real graphs -- in a child process under
 tools/hipstub, host code only -- and a numpy interpreter executes them, step for step what the kernels do, on a random
@@ -149,7 +149,7 @@ def _execute_df(pl, df, t=8, seed=0):
     tasks = np.array(df["tasks"], np.int64).reshape(-1, 6); klist = np.array(df["klist"], np.int64)
     # the order in which the block columns are queued (interleaves the independent parts of a nested-dissection ordering) and the
     # diagonal chains: every diagonal tile in exactly one chain workgroup's list, every list in queueing order -- a chain workgroup
-    # that waits for its next tile then waits for the tile whose inputs are queued first (the no-deadlock argument of build_df_plan)
+    # that waits for its next tile then waits for the tile whose inputs are queued first (the no-deadlock argument of tile_plan.cpp::df_column_sequence)
     seq = np.array(df["seq"], np.int64); coff = np.array(df["chain_off"], np.int64); ctiles = np.array(df["chain_tiles"], np.int64)
     assert sorted(seq.tolist()) == list(range(nt)) and sorted(ctiles.tolist()) == list(range(nt))
     pos = np.empty(nt, np.int64); pos[seq] = np.arange(nt)
@@ -218,7 +218,7 @@ def _simulate_df(pl, df, n_bulk):
     """Deadlock freedom of the dataflow schedule, simulated with BLOCKING workers: n_bulk bulk workgroups take tickets in order and
     then hold their task until everything it reads exists (a piece waits for the piece before it, a contraction for its operand tiles,
     a substitution for the diagonal tile of its column); the chain workgroups walk their tile lists in order and hold a tile until its
-    accumulated updates (PD) and the tile to its left are in.  Nobody ever lets go of a task.  The claim of build_df_plan: this
+    accumulated updates (PD) and the tile to its left are in.  Nobody ever lets go of a task.  The claim of tile_plan.cpp::plan_dataflow: this
     finishes for ANY number of resident bulk workgroups, also one -- a task only waits for smaller tickets and for diagonal tiles
     whose own inputs have smaller tickets, and a chain workgroup waits for its tiles in queueing order."""
     nt = int(df["nt"])

@@ -6,7 +6,7 @@ with its right-hand-side row: the factor and the forward solve against numpy -- 
 pieces, accumulator lanes, slices, panel release) under timings no GPU produces; a dependency that is not really there shows as a hang
 (the run is bounded) or as a wrong number.
 
-The task lists are built here in the layout of chol_dataflow.hip::upload_df_plan, following build_df_plan_host's rules for one chain
+The task lists are built here in the layout of tile_plan.cpp::df_resolve_host (what chol_dataflow.hip::upload_df_plan uploads), following the rules of tile_plan.cpp::plan_dataflow for one chain
 (pieces of a contraction list, early pieces queued behind the block column of their youngest operand, lanes for tiles with many early
 pieces); the library's own plan builder is pinned elsewhere (tests/test_chol_plan.py)."""
 import os
@@ -57,7 +57,7 @@ def plan_dense(nt, k_piece, k_final, lane_min=8, lane_max=8):
             R = (m + k_piece - 1) // k_piece + 1
             off = len(klist)
             # a contraction step: the slots of its operand tiles (I, k), (J, k) and their 64-bit sub-tile masks (dense system: every 16 x 16
-            # sub-tile; the right-hand-side row has one row of them), chol_dataflow.hip::kStepWords
+            # sub-tile; the right-hand-side row has one row of them), tile_plan.h::kStepWords
             klist += [(slot[(I, k)], slot[(J, k)], 0xFF if I == nt else -1, 0 if I == nt else -1, -1, -1) for k in ks]
             gprev = 0
             for r in range(R - 1):

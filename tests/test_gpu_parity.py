@@ -205,7 +205,7 @@ def test_nested_dissection_schedules_are_equivalent(gpu, sched, depth):
     """Elimination-tree parallelism (the reference eliminates independent cliques concurrently, inference/ClusterTree-inst.h:218-317):
     a nested-dissection ordering (parts aligned to 256-column pairs, identity padding between them) gives the tile Cholesky
     independent parts.  dataflow: the parts are several diagonal chains inside the two persistent kernels (the default for
-    sparse pose graphs: 4 levels since round 4, on up to 16 chain slots since round 6; chol_dataflow.hip::build_df_plan); streams: the round-1 tree schedule (chains on their own
+    sparse pose graphs: 4 levels since round 4, on up to 16 chain slots since round 6; tile_plan.cpp::df_chain_lists); streams: the round-1 tree schedule (chains on their own
     streams, cross-part updates on one in-order stream); depth 0: one chain (RCM).  Every variant: the reference's damped solve
     and the reference's full LM trajectory on sphere2500.
 

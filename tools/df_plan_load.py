@@ -7,7 +7,7 @@ order = the final pieces of block column q + the early pieces queued behind colu
 
     python tools/df_plan_load.py [workload]
 
-(Round 6 used it to judge a load-levelling pass over the early pieces -- a GTG_DF_LEVEL switch in build_df_plan_host, since removed: the
+(Round 6 used it to judge a load-levelling pass over the early pieces -- a GTG_DF_LEVEL switch in the dataflow planner (tile_plan.cpp::plan_dataflow today), since removed: the
 levelled plan was slower on the hardware, profiles/r06i_level_sweep.txt.)
 """
 import json

@@ -15,10 +15,8 @@
 #include <cstdio>
 #include <cstdlib>
 
-constexpr int kTile = 128;
-constexpr int kTileDoubles = kTile * kTile;
-constexpr int kSub = 16;
 #include "../../gtsam_amd/csrc/chol_dataflow.hip"
+using gt::kTileDoubles;
 
 template <class T> static T* shared_alloc(size_t n) {
   void* p = mmap(nullptr, sizeof(T) * std::max<size_t>(n, 1), PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
@@ -37,8 +35,8 @@ int main(int argc, char** argv) {
   double* S = shared_alloc<double>((size_t)n_slots * kTileDoubles);
   double* Xinv = shared_alloc<double>((size_t)nt * kTileDoubles);
   int32_t* tasks = shared_alloc<int32_t>((size_t)12 * n_tasks);
-  int32_t* klist = shared_alloc<int32_t>((size_t)6 * n_kp);   // 6 words per contraction step: two slots, two 64-bit sub-tile masks (chol_dataflow.hip::kStepWords)
-  int32_t* chain_slots = shared_alloc<int32_t>((size_t)4 * nt);   // chol_dataflow.hip::kChainWords
+  int32_t* klist = shared_alloc<int32_t>((size_t)6 * n_kp);   // 6 words per contraction step: two slots, two 64-bit sub-tile masks (tile_plan.h::kStepWords)
+  int32_t* chain_slots = shared_alloc<int32_t>((size_t)4 * nt);   // tile_plan.h::kChainWords
   int32_t* chain_off = shared_alloc<int32_t>((size_t)n_chain + 1);
   int32_t* chain_tiles = shared_alloc<int32_t>((size_t)nt);
   long long* tile_flag = shared_alloc<long long>((size_t)n_slots + sh + 8);

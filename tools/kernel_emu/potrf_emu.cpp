@@ -4,8 +4,6 @@
 // repetition against the first bit for bit -- the body's LDS protocol under timings no GPU would produce.
 #include "emu_hip.h"
 
-constexpr int kTile = 128;
-constexpr int kTileDoubles = kTile * kTile;
 #include "../../gtsam_amd/csrc/chol_device.h"
 
 // tile: 128 x 128 row-major (lower part read, factor written back in place); Xinv: 128 x 128 doubles (the four 32 x 32 inverses, the
