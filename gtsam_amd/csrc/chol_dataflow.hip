@@ -14,13 +14,20 @@
 //     32-column panel of chol_device.h.  Dependencies are epoch-stamped flags in HBM (release / acquire at agent
 //     scope): a task only ever waits for tasks that precede it in the ticket order, and tickets are taken in order
 //     by running workgroups, so the earliest unfinished task always runs -- no deadlock whatever the dispatch order.
+//     A bulk workgroup claims its NEXT ticket shortly before it finishes the current task and fetches that task's descriptor,
+//     first step and first flag polls under the rest of the current one (struct Ahead): it holds at most two tickets c < s and
+//     always runs c first.  The argument stands: let s be the smallest unfinished ticket.  Its holder cannot be busy with an
+//     unfinished smaller ticket (there is none), so it is running s; s waits only for smaller tickets, which are all finished, and
+//     for diagonal tiles whose inputs have smaller tickets.  That holds for any number of resident workgroups, one included.  A
+//     final piece claims only when it has seen the last panel of its diagonal tile, so no ticket is held in front of a long wait.
 //   * The serial chain per block column is: diagonal tile (k_df_chain) -> last substitution step of tile (J+1, J) ->
 //     its contribution to the next diagonal tile, applied by k_df_chain itself in 32-column slices as the substitution
 //     publishes them (PD(J+1) leaves that one contraction step out) -> next diagonal tile; everything else runs beside it.
 //
 // All sums run in a fixed order (the k list of a task): results are bit-reproducible and independent of which workgroup
 // ran which task.  A dependency wait that runs into its bound raises fail[1] (reported as an error by the C ABI, never
-// as "not positive definite"), after which every wait falls through and both kernels drain.
+// as "not positive definite"), after which every wait falls through and both kernels drain -- a workgroup that holds a claimed
+// ticket at that moment runs it like any other (its waits fall through as well) and leaves when its claim is past the end.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -206,11 +213,104 @@ constexpr int kBulkThreads = 1024;
 __device__ __forceinline__ int bulk_rt(int wave) { return 2 * (wave >> 2) + (wave & 1); }
 __device__ __forceinline__ int bulk_h(int wave) { return ((wave >> 2) + (wave >> 1)) & 1; }
 
+// which part_flag word a piece waits for before it loads its partial result, and for how many pieces (run_task; the same rule for the task
+// that is fetched ahead)
+struct PartWait { int lane_g, q, acc_slot; long long have; bool wait; };
+__device__ __forceinline__ PartWait first_part_wait(int piece, int pieces, int G, int slotC, int scratch) {
+  const int E = pieces - 1;
+  const bool early = piece < E;
+  PartWait w;
+  w.lane_g = (G > 1 && early) ? piece % G : 0; w.q = (G > 1 && early) ? piece / G : piece;
+  w.acc_slot = w.lane_g == 0 ? slotC : scratch + w.lane_g - 1;
+  w.wait = early ? w.q > 0 : E > 0;
+  w.have = early ? w.q : (E + G - 1) / G;
+  return w;
+}
+
+// ---- the task BEHIND the current one ---------------------------------------------------------------------------------
+// A task boundary used to be a string of dependent memory round trips with all sixteen wavefronts idle: ticket (a device-scope
+// read-modify-write between two barriers), descriptor (its address depends on the ticket), the first step's words (on the descriptor),
+// the first part_flag and tile_flag polls (on both).  Now the workgroup claims its next ticket one set-up length before it finishes the
+// current task and requests those words one after the other UNDER the rest of that task -- each request is issued right behind a point
+// where the wavefront drains its memory counter anyway (a chunk barrier, stores_done(), the epilogue) and used at the next such point, so
+// that no wait of its own lands between the MFMAs or in a substitution step (the vector-memory counter is in order).  The ticket (one lane
+// claims it) and the descriptor (LDS-DMA of wavefront 0) go through LDS; the step's words and the flag polls are fetched by every wavefront
+// for itself, as before, one lane per word (v_readlane hands the words out).  Nothing of the next task is in flight between the task's
+// barrier and its flag store.  `level` says how far the chain got; ahead_complete() does what is missing at the start of the task.
+struct Ahead {
+  int level;          // 0: ticket claimed (in the LDS slot); 1: t; 2: descriptor requested; 3: dw; kw, pv requested; 4: fa, fb requested
+  int t;              // the ticket (>= ntasks: leave after the current task)
+  int dw;             // lane i: word min(i, 11) of the descriptor
+  int kw;             // lane i: word min(i, 5) of the first contraction step
+  long long pv;       // the part_flag word of its first wait, as polled (flags only grow: a value that satisfies the wait stays valid)
+  long long fa, fb;   // the flag words of the first step's operand tiles, as polled
+};
+struct AheadEnv {
+  const int32_t* tasks; int ntasks; const int32_t* klist; const long long* tile_flag; const long long* part_flag; int32_t* ctrl;
+  int* slot;          // LDS word of the ticket that is claimed during the current task
+  int* desc;          // LDS: 64 words for its descriptor (lane i of wavefront 0 brings word min(i, 11))
+};
+__device__ __forceinline__ int ld_word(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }   // (an atomic load stays where it is written)
+// (an increment without a wrap, not atomicAdd: the compiler rewrites an add of a uniform value into "one lane adds the number of active
+// lanes, v_readfirstlane hands the result out" and so waits for the ticket right behind its request -- the round trip this is meant to hide)
+__device__ __forceinline__ int ahead_claim(const AheadEnv& e) { return threadIdx.x == 0 ? (int)atomicInc(reinterpret_cast<unsigned*>(e.ctrl), 0xFFFFFFFFu) : 0; }
+__device__ __forceinline__ void ahead_post(const AheadEnv& e, int tk) { if (threadIdx.x == 0) *(GT_LDS_VOLATILE(int))e.slot = tk; }   // in front of a workgroup barrier
+__device__ __forceinline__ void ahead_ticket(const AheadEnv& e, Ahead& a) { a.t = __builtin_amdgcn_readfirstlane(*(GT_LDS_VOLATILE(int))e.slot); a.level = 1; }   // behind that barrier
+__device__ __forceinline__ void ahead_descriptor(const AheadEnv& e, Ahead& a) {
+  int tid_ = threadIdx.x;
+  GT_PIN(tid_);   // (the lane's word index is made here, not hoisted out of the task loop and kept alive -- or spilled -- across it)
+  const unsigned lane = tid_ & 63;
+  // (every request of the chain is unconditional -- a claim past the end fetches the words of task 0 and ignores them: a value that is
+  // merged with a constant behind a branch is copied, and the copy waits for the load on the spot)
+  const int t = a.t < e.ntasks ? a.t : 0;
+  a.dw = ld_word(e.tasks + kTaskWords * (int64_t)t + (lane < kTaskWords ? lane : kTaskWords - 1));
+  a.level = 2;
+}
+// The same request under a running task: memory -> LDS by LDS-DMA, issued by wavefront 0 alone, read by every wavefront behind the next
+// barrier (ahead_step).  No register holds the words while they are in flight: a register that is live across the MFMAs of the last chunk
+// gets copied by the register allocator, and the copy waits for the load right behind its issue.
+__device__ __forceinline__ void ahead_descriptor_to_lds(const AheadEnv& e, Ahead& a) {
+  int tid_ = threadIdx.x;
+  GT_PIN(tid_);
+  const unsigned lane = tid_ & 63;
+  const int t = a.t < e.ntasks ? a.t : 0;
+  if (__builtin_amdgcn_readfirstlane(tid_ >> 6) == 0)
+    __builtin_amdgcn_global_load_lds((gptr_t)(e.tasks + kTaskWords * (int64_t)t + (lane < kTaskWords ? lane : kTaskWords - 1)), (lptr_t)e.desc, 4, 0, 0);
+  a.level = 2;
+}
+template <bool kFromLds>
+__device__ __forceinline__ void ahead_step(const AheadEnv& e, Ahead& a) {
+  int tid_ = threadIdx.x;
+  GT_PIN(tid_);
+  const unsigned lane = tid_ & 63;
+  if (kFromLds) a.dw = ((GT_LDS_VOLATILE(int))e.desc)[lane < kTaskWords ? lane : kTaskWords - 1];
+  const int t = a.t < e.ntasks ? a.t : 0;
+  const int off = __builtin_amdgcn_readlane(a.dw, 2), kcnt = __builtin_amdgcn_readlane(a.dw, 3);
+  // (a task without a contraction has no step: any six valid words, never looked at)
+  const int32_t* step = kcnt > 0 ? e.klist + kStepWords * (int64_t)off : e.tasks + kTaskWords * (int64_t)t;
+  a.kw = ld_word(step + (lane < kStepWords ? lane : kStepWords - 1));
+  const PartWait w = first_part_wait(__builtin_amdgcn_readlane(a.dw, 4), __builtin_amdgcn_readlane(a.dw, 5), __builtin_amdgcn_readlane(a.dw, 8),
+                                     __builtin_amdgcn_readlane(a.dw, 6), __builtin_amdgcn_readlane(a.dw, 9));
+  a.pv = ld_flag(e.part_flag + (w.wait ? w.acc_slot : 0));   // (read only where the task waits for it)
+  a.level = 3;
+}
+__device__ __forceinline__ void ahead_flags(const AheadEnv& e, Ahead& a) {
+  const bool steps = __builtin_amdgcn_readlane(a.dw, 3) > 0;   // (none: word 0, never looked at)
+  a.fa = ld_flag(e.tile_flag + (steps ? __builtin_amdgcn_readlane(a.kw, 0) : 0)); a.fb = ld_flag(e.tile_flag + (steps ? __builtin_amdgcn_readlane(a.kw, 1) : 0));
+  a.level = 4;
+}
+__device__ __forceinline__ void ahead_complete(const AheadEnv& e, Ahead& a) {
+  if (a.level < 1) ahead_ticket(e, a);
+  if (a.level < 2) ahead_descriptor(e, a);
+  if (a.level < 3) ahead_step<false>(e, a);
+  if (a.level < 4) ahead_flags(e, a);
+}
+
 template <int H>
 __device__ __forceinline__ void substitute(char* smem_raw, v4f64 (&x)[4], double* __restrict__ C, int I, int J,
                                            long long* __restrict__ myflag, const long long* __restrict__ pflag, double* __restrict__ Xinv_all,
                                            double* __restrict__ fail, long long epoch, int32_t* __restrict__ dbg,
-                                           long long* __restrict__ tr, bool row_live) {
+                                           long long* __restrict__ tr, bool row_live, const AheadEnv& env, Ahead& nx) {
   // (row_live: the 16 rows of this wavefront can be non-zero in tile (I, J) -- its sub-tile mask; a row tile without a live sub-tile stays
   // exactly zero through the substitution and its wavefronts leave the MFMAs out: half of the row tiles of a pose graph's tiles)
   // ---- L(I,J) = R L(J,J)^-T: right-looking block substitution over the 32-column blocks q.
@@ -242,6 +342,10 @@ __device__ __forceinline__ void substitute(char* smem_raw, v4f64 (&x)[4], double
       pf = flagbase + q + 1;
     }
     if (tr && tid == 0) tr[4 + q] = wall_clock64();   // panel q seen
+    // Panel 3 seen: nothing this task still waits for lies ahead -- the moment to claim the next ticket, and not before (a final piece can
+    // sit tens of microseconds in front of its panels; a ticket held that long is a task nobody runs)
+    int tk = 0;
+    if (q == 3) tk = ahead_claim(env);
     // (the previous step's images have been consumed: barrier at the end of the loop body)
     {  // images of this step: slots 0 .. 3-q = L(q + s, q - 1) (q > 0), slot 3 = Linv(q,q); wavefront w moves 1 KiB pieces
       // (w & 7) of the slots (w >> 3) and (w >> 3) + 2
@@ -258,6 +362,7 @@ __device__ __forceinline__ void substitute(char* smem_raw, v4f64 (&x)[4], double
     // The image fetch and the acknowledgement of X_{q-1}'s write-through stores are two memory round trips; rounds 3 - 5 took them one after
     // the other (drain, barrier, flag, fetch, barrier), now the fetch is in flight while the stores drain (s_waitcnt vmcnt(0) covers both)
     if (q > 0) stores_done();   // X_{q-1} of this wavefront is in memory
+    if (q == 3) ahead_post(env, tk);   // (the ticket came back with that drain)
     __syncthreads();   // (drains the DMA); -X_{q-1} is complete in the W patches and out of every wavefront
     if (q > 0 && tid == 0) st_flag(myflag, flagbase + q);
     if (q > 0) {
@@ -285,6 +390,8 @@ __device__ __forceinline__ void substitute(char* smem_raw, v4f64 (&x)[4], double
     // the next panel's flag, requested a step's arithmetic ahead of its use: a poll is a memory round trip even when the panel is long out.
     // (In front of this step's write-through stores: the memory counter is in order, a load issued behind them returns with their acknowledgements)
     if (q < 3 && pf < flagbase + q + 2) pf = ld_flag(pflag);
+    // the next task's descriptor rides in the same place of the last step: back with the acknowledgements of X_3's stores
+    if (q == 3) { ahead_ticket(env, nx); ahead_descriptor_to_lds(env, nx); }
 #pragma unroll
     for (int l = 0; l < 2; l++) {
       if (2 * h + l != q) continue;   // (compile-time)
@@ -320,8 +427,11 @@ __device__ __forceinline__ void substitute(char* smem_raw, v4f64 (&x)[4], double
     if (q < 3) __syncthreads();   // this step's images have been consumed by every wavefront: the next step may fetch over them
   }
   stores_done();
-  __syncthreads();
+  __syncthreads();   // the one barrier of the task boundary: every wavefront's stores are in memory, W / img are free for the next task's chunks
   if (tid == 0) st_flag(myflag, flagbase + 4);
+  // (the descriptor is in LDS) the next task's first step and its part_flag poll -- BEHIND the flag: lane 0's wavefront must not find
+  // them in its in-order memory counter when it waits for anything on the way to the flag store
+  ahead_step<true>(env, nx);
 }
 
 
@@ -329,7 +439,9 @@ __device__ __forceinline__ void run_task(char* smem_raw, double* __restrict__ S,
                                          const int32_t* __restrict__ kl, int kcnt, int piece, int pieces, unsigned long long out_mask,
                                          long long* __restrict__ tile_flag, long long* __restrict__ part_flag,
                                          long long* __restrict__ pd_flag, double* __restrict__ Xinv_all,
-                                         double* __restrict__ fail, long long epoch, int32_t* __restrict__ dbg, long long* __restrict__ tr) {
+                                         double* __restrict__ fail, long long epoch, int32_t* __restrict__ dbg, long long* __restrict__ tr,
+                                         const Ahead& got, const AheadEnv& env, Ahead& nx) {
+  // (got: what was fetched of THIS task under its predecessor -- its first step's words, its first flag polls; nx: the task behind it)
   // the thread index is laundered per task: everything derived from it is recomputed here instead of being hoisted out of
   // the persistent task loop and kept alive across it
   int tid_ = threadIdx.x;
@@ -375,8 +487,13 @@ __device__ __forceinline__ void run_task(char* smem_raw, double* __restrict__ S,
   // the lanes up in lane order (a fixed order: bit-reproducible).  G = 1 (every tile of the camera systems) is the in-place chain.
   const int E = pieces - 1;                    // early pieces of the tile
   const bool early = piece < E;
-  const int lane_g = (G > 1 && early) ? piece % G : 0, q = (G > 1 && early) ? piece / G : piece;
-  const int acc_slot = lane_g == 0 ? slotC : scratch + lane_g - 1;
+  const PartWait pw = first_part_wait(piece, pieces, G, slotC, scratch);
+  const int lane_g = pw.lane_g, q = pw.q, acc_slot = pw.acc_slot;
+  // Tasks that wait for nothing once their contraction is staged -- early pieces, PD -- claim the next ticket with the last chunk of the
+  // last step (below); without a contraction, on entry.  A final piece with a substitution claims when it has seen panel 3 (substitute).
+  const bool subst = !early && I != J;
+  int tk = 0;
+  if (!subst && kcnt == 0) tk = ahead_claim(env);
   double* AccRow = S + (int64_t)acc_slot * TT + (16 * rt) * T + 64 * h;
   long long* pflag_mine = part_flag + acc_slot;
   auto load_acc = [&](const double* row, bool add) {     // a partial result written (write-through) by another workgroup: read past the L1 (sc1)
@@ -390,10 +507,12 @@ __device__ __forceinline__ void run_task(char* smem_raw, double* __restrict__ S,
   };
 #pragma unroll
   for (int c = 0; c < 4; c++) x[c] = (v4f64){0.0, 0.0, 0.0, 0.0};
-  if (early ? q > 0 : E > 0) {
-    // lane 0 / this lane: the pieces before this one
-    const long long have = early ? q : (E + G - 1) / G;
-    GT_TIMED(wait_flags(pflag_mine, epoch * kPieceBase + have, pflag_mine, epoch * kPieceBase + have, fail, dbg, 7, I, J, piece));
+  if (pw.wait) {
+    // lane 0 / this lane: the pieces before this one (got.pv: the word as it was polled under the previous task -- if the pieces were in
+    // by then, that round trip is saved)
+    const long long have = pw.have;
+    if (got.pv < epoch * kPieceBase + have) GT_TIMED(wait_flags(pflag_mine, epoch * kPieceBase + have, pflag_mine, epoch * kPieceBase + have, fail, dbg, 7, I, J, piece));
+    else acquired();
     load_acc(AccRow, false);
     if (!early)
       for (int g = 1; g < G; g++) {            // the other lanes, in lane order
@@ -414,9 +533,15 @@ __device__ __forceinline__ void run_task(char* smem_raw, double* __restrict__ S,
     // while its substitution runs: a chunk only waits for the block it reads.  For every step but the most recent ones both
     // tiles are long final and the test is a scalar compare; for the last step (block column J-1, whose tiles become final
     // behind the diagonal tile that is being factored right now) the contraction streams behind the substitution.
-    int ka = kl[0], kb = kl[1];
+    // (the first step's words and the flags of its operand tiles were requested under the previous task: got.kw, got.fa / got.fb)
+    int ka = __builtin_amdgcn_readlane(got.kw, 0), kb = __builtin_amdgcn_readlane(got.kw, 1);
     int cp = 0;
-    GT_TIMED(cp = wait_progress(tile_flag + ka, tile_flag + kb, flagbase, 1, fail, dbg, 1, I, J, ka));   // progress known for the current step
+    {
+      const long long fm = (got.fa < got.fb ? got.fa : got.fb) - flagbase;
+      cp = __builtin_amdgcn_readfirstlane((int)(fm < 0 ? 0 : fm));
+    }
+    if (cp < 1) GT_TIMED(cp = wait_progress(tile_flag + ka, tile_flag + kb, flagbase, 1, fail, dbg, 1, I, J, ka));   // progress known for the current step
+    else acquired();
     const double* Ak = S + (int64_t)ka * TT;
     const double* Bk = S + (int64_t)kb * TT;
     stage(Ak, Bk, 0, 0);
@@ -429,8 +554,8 @@ __device__ __forceinline__ void run_task(char* smem_raw, double* __restrict__ S,
     // holds those four bits for each of the eight strips.  A skipped product is a sum of exact zeros: the factor is unchanged.  (The
     // right-hand-side row, tile row nt, is the extreme case: one live row tile -- fourteen wavefronts multiplied zeros, 6 % of the bulk
     // kernel's resident time, tools/df_wait_analysis.py.)
-    auto live_bits = [&](const int32_t* w) {
-      const unsigned long long ma = (unsigned)w[2] | ((unsigned long long)(unsigned)w[3] << 32), mb = (unsigned)w[4] | ((unsigned long long)(unsigned)w[5] << 32);
+    auto live_bits = [&](int w2, int w3, int w4, int w5) {   // words 2 .. 5 of a step
+      const unsigned long long ma = (unsigned)w2 | ((unsigned long long)(unsigned)w3 << 32), mb = (unsigned)w4 | ((unsigned long long)(unsigned)w5 << 32);
       const unsigned arow = (unsigned)(ma >> (8 * rt)) & 0xFFu;
       unsigned lv = 0;
 #pragma unroll
@@ -441,13 +566,14 @@ __device__ __forceinline__ void run_task(char* smem_raw, double* __restrict__ S,
       }
       return __builtin_amdgcn_readfirstlane(lv);
     };
-    unsigned live = live_bits(kl);
+    unsigned live = live_bits(__builtin_amdgcn_readlane(got.kw, 2), __builtin_amdgcn_readlane(got.kw, 3), __builtin_amdgcn_readlane(got.kw, 4), __builtin_amdgcn_readlane(got.kw, 5));
     const int half = (lk & 1) * 8, hi = lk >> 1, sw = lr;
     for (int ki = 0; ki < kcnt; ki++) {
+      const bool claim_here = !subst && ki + 1 == kcnt;   // the last step of a task that waits for nothing behind it
       // the flags of the next contraction step, fetched a whole step ahead of their use
       const int32_t* kn = kl + kStepWords * (ki + 1 < kcnt ? ki + 1 : ki);
       const int kna = kn[0], knb = kn[1];
-      const unsigned live_next = live_bits(kn);
+      const unsigned live_next = live_bits(kn[2], kn[3], kn[4], kn[5]);
       int np = tile_progress(tile_flag + kna, tile_flag + knb, flagbase);
       const double* An = S + (int64_t)kna * TT;
       const double* Bn = S + (int64_t)knb * TT;
@@ -458,9 +584,13 @@ __device__ __forceinline__ void run_task(char* smem_raw, double* __restrict__ S,
           const int need = ch + 2;   // chunk ch + 1 = the operand tiles' 32-column block ch + 1
           if (cp < need) { cp = tile_progress(tile_flag + ka, tile_flag + kb, flagbase); if (cp < need) GT_TIMED(cp = wait_progress(tile_flag + ka, tile_flag + kb, flagbase, need, fail, dbg, 2, I, J, ka)); }
           stage(Ak, Bk, ch + 1, cur ^ 1);
+          // the last chunk is staged: the next ticket, requested behind it (back when this chunk's barrier drains the DMA)
+          if (ch + 2 == T / KC && claim_here) tk = ahead_claim(env);
         } else if (ki + 1 < kcnt) {
           if (np < 1) GT_TIMED(np = wait_progress(tile_flag + kna, tile_flag + knb, flagbase, 1, fail, dbg, 2, I, J, kna));
           stage(An, Bn, 0, cur ^ 1);
+        } else if (claim_here) {   // the last chunk: the ticket is in LDS, the descriptor is requested under this chunk's MFMAs
+          ahead_ticket(env, nx); ahead_descriptor_to_lds(env, nx);
         }
         const char* Ac = smem_raw + cur * 2 * CH;
         const char* Bc = Ac + CH;
@@ -489,6 +619,7 @@ __device__ __forceinline__ void run_task(char* smem_raw, double* __restrict__ S,
             }
           }
         }
+        if (ch + 2 == T / KC && claim_here) ahead_post(env, tk);   // (lane 0 waits for its ticket where it waits for the DMA anyway)
         __syncthreads();   // drains the DMA of the next chunk (vmcnt) and fences the buffer just read
       }
       ka = kna; kb = knb; Ak = An; Bk = Bn; cp = np; live = live_next;
@@ -497,33 +628,38 @@ __device__ __forceinline__ void run_task(char* smem_raw, double* __restrict__ S,
   if (tr && tid == 0) { tr[1] = wall_clock64(); tr[3] |= waited << 40; }   // (bits 40..: ticks waited; below: where the workgroup runs)
 #undef GT_TIMED
 
-  if (early) {   // an early piece: the partial result goes back into its lane's tile
+  // Hand-over of an early piece / of PD.  ONE barrier per task boundary: every wavefront's stores are in memory (-> the flag), every
+  // wavefront is done with the staging buffers (-> the next task).  The next task's first step and its part_flag poll (the descriptor
+  // came in with the last chunk's barrier) go out BEHIND the flag store.  In front of the result's stores they were measured: they come
+  // back 1.2 us later than the stores' acknowledgements (words no XCD has touched yet, flags that every store drops from the L2), the
+  // in-order counter makes stores_done() wait for them, and every early piece was published that much later -- what the next task's
+  // set-up gained, its dependents lost (profiles/HISTORY.md, section 15).
+  auto hand_over = [&](double* row, long long* flag, long long value) {
 #pragma unroll
     for (int c = 0; c < 4; c++)
 #pragma unroll
-      for (int r = 0; r < 4; r++) st_wt((AccRow + (4 * r) * T + 16 * c) + lane_off, x[c][r]);
+      for (int r = 0; r < 4; r++) st_wt((row + (4 * r) * T + 16 * c) + lane_off, x[c][r]);
     stores_done();
+    if (kcnt == 0) ahead_post(env, tk);   // (claimed on entry)
     __syncthreads();
-    if (tid == 0) st_flag(pflag_mine, epoch * kPieceBase + q + 1);
+    if (tid == 0) st_flag(flag, value);
+    if (kcnt > 0) ahead_step<true>(env, nx);
+  };
+  if (early) {   // an early piece: the partial result goes back into its lane's tile
+    hand_over(AccRow, pflag_mine, epoch * kPieceBase + q + 1);
     return;
   }
   if (I == J) {
     // PD(J): the diagonal tile with its updates in (all but block column J-1's, which k_df_chain applies itself)
-#pragma unroll
-    for (int c = 0; c < 4; c++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) st_wt((Crow + (4 * r) * T + 16 * c) + lane_off, x[c][r]);
-    stores_done();
-    __syncthreads();
-    if (tid == 0) st_flag(pd_flag + J, fin);
+    hand_over(Crow, pd_flag + J, fin);
     return;
   }
 
   // the substitution, specialised for the column half (the wavefront-uniform branch keeps every "is block p mine / still open"
   // test a compile-time constant: with run-time tests the compiler merged the accumulators through scratch at every step)
   const bool row_live = ((out_mask >> (8 * rt)) & 0xFFull) != 0;
-  if (h == 0) substitute<0>(smem_raw, x, C, I, J, tile_flag + slotC, tile_flag + slotD, Xinv_all, fail, epoch, dbg, tr, row_live);
-  else substitute<1>(smem_raw, x, C, I, J, tile_flag + slotC, tile_flag + slotD, Xinv_all, fail, epoch, dbg, tr, row_live);
+  if (h == 0) substitute<0>(smem_raw, x, C, I, J, tile_flag + slotC, tile_flag + slotD, Xinv_all, fail, epoch, dbg, tr, row_live, env, nx);
+  else substitute<1>(smem_raw, x, C, I, J, tile_flag + slotC, tile_flag + slotD, Xinv_all, fail, epoch, dbg, tr, row_live, env, nx);
 }
 
 __device__ __forceinline__ void bulk_loop(char* smem_raw, double* __restrict__ S, const int32_t* __restrict__ tasks,
@@ -533,23 +669,36 @@ __device__ __forceinline__ void bulk_loop(char* smem_raw, double* __restrict__ S
                                           double* __restrict__ Xinv_all, int32_t* __restrict__ ctrl,
                                           double* __restrict__ fail, const long long epoch,
                                           long long* __restrict__ trace) {
-  __shared__ int s_task;
-  for (;;) {
-    if (threadIdx.x == 0) s_task = atomicAdd(ctrl, 1);
-    __syncthreads();
-    const int t = s_task;
-    __syncthreads();
-    if (t >= ntasks) return;
-    const int32_t* d = tasks + 12 * (int64_t)t;   // I, J, offset / count of the step list, piece r of R, slot of (I, J), slot of (J, J), accumulator lanes, first scratch slot, [10, 11]: the tile's own sub-tile mask
-    long long* tr = trace ? trace + 8 * (int64_t)t : nullptr;   // GTG_DF_TRACE: 100 MHz stamps (taken, contraction done, done), place
+  // The ticket of the task behind the current one, claimed by lane 0 during the current task (see Ahead).  Two words, used in turn: the
+  // ticket of task n + 1 is written during task n in front of a barrier and read behind it, at the latest at the start of task n + 1; the
+  // same word is written again during task n + 2, behind the barrier that ends task n + 1.
+  __shared__ int s_ticket[2];
+  __shared__ int s_desc[2][64];   // (and its descriptor, in turn like the tickets)
+  if (ntasks <= 0) return;
+  AheadEnv env{tasks, ntasks, klist, tile_flag, part_flag, ctrl, &s_ticket[0], &s_desc[0][0]};
+  ahead_post(env, ahead_claim(env));   // the first ticket: nothing to hide it under
+  __syncthreads();
+  Ahead nx{};
+  for (int n = 0;; n++) {
+    const long long t_start = trace ? wall_clock64() : 0;   // the predecessor is done: work on this task starts (not the moment of the claim)
+    ahead_complete(env, nx);   // whatever the previous task could not fetch under itself (the first task: everything)
+    const int t = nx.t;
+    if (t >= ntasks) return;   // a claimed index past the end: nothing to run, nothing lost
+    const Ahead got = nx;
+    int d[kTaskWords];   // I, J, offset / count of the step list, piece r of R, slot of (I, J), slot of (J, J), accumulator lanes, first scratch slot, [10, 11]: the tile's own sub-tile mask
+#pragma unroll
+    for (int i = 0; i < kTaskWords; i++) d[i] = __builtin_amdgcn_readlane(got.dw, i);
+    long long* tr = trace ? trace + 8 * (int64_t)t : nullptr;   // GTG_DF_TRACE: 100 MHz stamps (work started, contraction done, done), place
     if (tr && threadIdx.x == 0) {
       unsigned hw, xcc;
       GT_HW_ID(hw);
       GT_XCC_ID(xcc);
-      tr[0] = wall_clock64(); tr[3] = ((long long)(xcc & 0xf) << 32) | hw;
+      tr[0] = t_start; tr[3] = ((long long)(xcc & 0xf) << 32) | hw;
     }
-    run_task(smem_raw, S, d[0], d[1], d[6], d[7], d[8], d[9], klist + kStepWords * (int64_t)d[2], d[3], d[4], d[5], (unsigned)d[10] | ((unsigned long long)(unsigned)d[11] << 32), tile_flag, part_flag, pd_flag, Xinv_all, fail, epoch, ctrl + 8, tr);
-    __syncthreads();   // the substitution buffers / staging buffers are reused by the next task
+    env.slot = &s_ticket[(n + 1) & 1]; env.desc = &s_desc[(n + 1) & 1][0];
+    nx = Ahead{};   // (run_task claims the next ticket and fetches as far as the task lets it; nothing of the old one stays alive)
+    run_task(smem_raw, S, d[0], d[1], d[6], d[7], d[8], d[9], klist + kStepWords * (int64_t)d[2], d[3], d[4], d[5], (unsigned)d[10] | ((unsigned long long)(unsigned)d[11] << 32), tile_flag, part_flag, pd_flag, Xinv_all, fail, epoch, ctrl + 8, tr, got, env, nx);
+    // (run_task ends behind the task's one barrier: stores in memory, flag out, substitution / staging buffers free)
     if (tr && threadIdx.x == 0) tr[2] = wall_clock64();
   }
 }

@@ -167,6 +167,11 @@ inline void emu_global_load_lds(gptr_t g, lptr_t l, int bytes) { std::memcpy(sta
 // the 100 MHz constant clock, slowed down 100 000 times: the kernels' 20 ms wait bounds must not fire at emulation speed
 inline long long wall_clock64() { return (long long)(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count() / 1000000); }
 inline int atomicAdd(int* p, int v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
+inline unsigned atomicInc(unsigned* p, unsigned limit) {   // old >= limit ? 0 : old + 1
+  unsigned old = __atomic_load_n(p, __ATOMIC_SEQ_CST);
+  while (!__atomic_compare_exchange_n(p, &old, old >= limit ? 0u : old + 1u, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {}
+  return old;
+}
 inline int atomicCAS(int* p, int expect, int v) { __atomic_compare_exchange_n(p, &expect, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST); return expect; }
 template <class T, class V> inline T emu_atomic_fetch_max(T* p, V v) {
   T old = __atomic_load_n(p, __ATOMIC_SEQ_CST);
