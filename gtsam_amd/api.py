@@ -146,6 +146,24 @@ class PinholeCameraCal3Bundler:
     def from_packed(p): return PinholeCameraCal3Bundler(Pose3.from_packed(p[:12]), Cal3Bundler(*p[12:17]))
 
 
+class PinholePoseCal3_S2:
+    """PinholePose<Cal3_S2> (geometry/PinholePose.h): a pose and a fixed, shared calibration -- a camera of a rig (pose = body_P_sensor)."""
+
+    def __init__(self, pose: Pose3 | None = None, K: Cal3_S2 | None = None):
+        self._pose = pose or Pose3(); self._K = K or Cal3_S2()
+
+    def pose(self): return self._pose
+    def calibration(self): return self._K
+
+
+class CameraSetPinholePoseCal3_S2(list):
+    """CameraSet<PinholePose<Cal3_S2>> (geometry/CameraSet.h): the cameras of a rig, by camera id."""
+
+    def push_back(self, camera): self.append(camera)
+    def size(self): return len(self)
+    def at(self, i): return self[i]
+
+
 # ---- noise models ------------------------------------------------------------------------------------------------
 def _robust_weight(kind, k, d):
     a = abs(d)
@@ -355,6 +373,41 @@ class SmartProjectionPose3Factor:
     def body_P_sensor(self): return self.sensor or Pose3()
 
 
+class SmartProjectionRigFactorPinholePoseCal3_S2:
+    """SmartProjectionRigFactor<PinholePose<Cal3_S2>> (slam/SmartProjectionRigFactor.h): the keys are BODY poses, every measurement looks
+    through one camera of a fixed rig; add(measured, poseKey, cameraId) per view, the same pose key may occur several times."""
+
+    def __init__(self, sharedNoiseModel, cameraRig: CameraSetPinholePoseCal3_S2, params: SmartProjectionParams | None = None):
+        self.model, self.rig, self.params = sharedNoiseModel, cameraRig, params or SmartProjectionParams()
+        # the reference's constructor (:100-107)
+        if self.params.degeneracyMode != SmartProjectionParams.ZERO_ON_DEGENERACY:
+            raise RuntimeError("SmartProjectionRigFactor: degeneracyMode must be set to ZERO_ON_DEGENERACY")
+        if self.params.linearizationMode != SmartProjectionParams.HESSIAN:
+            raise RuntimeError("SmartProjectionRigFactor: linearizationMode must be set to HESSIAN")
+        self.nonUniqueKeys_, self.keys_, self.cameraIds_, self.zs = [], [], [], []
+
+    def add(self, measured, poseKey, cameraId=None):
+        """add(Point2, key, cameraId = 0), or the vector form add(measurements, keys, cameraIds = []) (:120-164)"""
+        if isinstance(poseKey, (list, tuple, np.ndarray)):
+            keys, ids = list(poseKey), [] if cameraId is None else list(cameraId)
+            if len(keys) != len(measured) or (len(keys) != len(ids) and len(ids) != 0):
+                raise RuntimeError("SmartProjectionRigFactor: trying to add inconsistent inputs")
+            if len(ids) == 0 and len(self.rig) > 1:
+                raise RuntimeError("SmartProjectionRigFactor: camera rig includes multiple camera but add did not input cameraIds")
+            for i, k in enumerate(keys):
+                self.add(measured[i], k, ids[i] if ids else 0)
+            return
+        self.zs.append(np.asarray(measured, np.float64).reshape(2)); self.nonUniqueKeys_.append(poseKey)
+        if poseKey not in self.keys_:
+            self.keys_.append(poseKey)          # the unique keys, in the order of their first appearance
+        self.cameraIds_.append(0 if cameraId is None else int(cameraId))
+
+    def nonUniqueKeys(self): return list(self.nonUniqueKeys_)
+    def keys(self): return list(self.keys_)
+    def cameraIds(self): return list(self.cameraIds_)
+    def cameraRig(self): return self.rig
+
+
 class BetweenFactorPose3:
     def __init__(self, key1, key2, measured: Pose3, model):
         self.keys_, self.z, self.model = (key1, key2), measured, model
@@ -450,6 +503,9 @@ def extract(graph: NonlinearFactorGraph, values: Values):
     sfm, proj, btw, stereo = [], [], [], []
     calibs, sensors = {}, []
     smart_sensors = {}      # pose-type smart factors share their sensor rows (one body_P_sensor for a whole front end)
+    # rig-type smart factors: (rig object, camera id) -> (calib row, row of rig_sensors or -1), shared by every factor of the rig; the
+    # extrinsics stand BEHIND the sensor rows of the other factors (as the C++ shim, which merges its extraction chunks, places them)
+    rig_rows, rig_sensors, rig_factors = {}, [], []
     for f in graph.factors:
         if isinstance(f, GeneralSFMFactorCal3Bundler):
             sfm.append((vid(f.keys_[0]), vid(f.keys_[1]), f.z, nid(f.model, 2)))
@@ -490,6 +546,27 @@ def extract(graph: NonlinearFactorGraph, values: Values):
             p.add_smart([vid(k) for k in f.keys_], np.concatenate(f.zs), nid(f.model, 2), sp.rankTolerance, sp.landmarkDistanceThreshold,
                         sp.dynamicOutlierRejectionThreshold, sp.retriangulationThreshold, sp.degeneracyMode, sp.linearizationMode, sp.enableEPI,
                         calib=calibs[ck][0], sensor=si)
+        elif isinstance(f, SmartProjectionRigFactorPinholePoseCal3_S2):
+            mc, ms = [], []
+            for cid in f.cameraIds_:
+                if not 0 <= cid < len(f.rig):
+                    raise IndexError(f"SmartProjectionRigFactor: camera id {cid} outside the rig")
+                if (id(f.rig), cid) not in rig_rows:
+                    cam = f.rig[cid]
+                    ck = cam.calibration().v.tobytes()
+                    if ck not in calibs:
+                        calibs[ck] = (len(calibs), cam.calibration().v)
+                    si = -1                       # an identity extrinsic is no extrinsic (the composition returns the body pose's own numbers)
+                    if not np.array_equal(cam.pose().packed(), Pose3().packed()):
+                        si = len(rig_sensors); rig_sensors.append(cam.pose().packed())
+                    rig_rows[(id(f.rig), cid)] = (calibs[ck][0], si)
+                c_, s_ = rig_rows[(id(f.rig), cid)]
+                mc.append(c_); ms.append(s_)
+            sp = f.params
+            p.add_smart([vid(k) for k in f.nonUniqueKeys_], np.concatenate(f.zs), nid(f.model, 2), sp.rankTolerance, sp.landmarkDistanceThreshold,
+                        sp.dynamicOutlierRejectionThreshold, sp.retriangulationThreshold, sp.degeneracyMode, sp.linearizationMode, sp.enableEPI,
+                        meas_calib=mc, meas_sensor=ms)
+            rig_factors.append(p.n_smart - 1)
         elif isinstance(f, BetweenFactorPose3):
             btw.append((vid(f.keys_[0]), vid(f.keys_[1]), f.z.packed(), nid(f.model, 6)))
         elif isinstance(f, BetweenFactorPose2):   # same table: the measurement sits in the first 3 of the 12 doubles
@@ -513,6 +590,10 @@ def extract(graph: NonlinearFactorGraph, values: Values):
         p.stereo_pose = np.array([s[0] for s in stereo], np.int32); p.stereo_point = np.array([s[1] for s in stereo], np.int32)
         p.stereo_z = np.concatenate([s[2] for s in stereo]); p.stereo_noise = np.array([s[3] for s in stereo], np.int32)
         p.stereo_calib = np.array([s[4] for s in stereo], np.int32); p.stereo_sensor = np.array([s[5] for s in stereo], np.int32)
+    for i in rig_factors:       # the rig extrinsics' final rows
+        a, b = int(p.smart_ptr[i]), int(p.smart_ptr[i + 1])
+        p.smart_meas_sensor[a:b] = np.where(p.smart_meas_sensor[a:b] >= 0, p.smart_meas_sensor[a:b] + len(sensors), -1)
+    sensors = sensors + rig_sensors
     if proj or stereo or calibs:
         rows = [c[1] for c in sorted(calibs.values(), key=lambda c: c[0])]
         p.calib = np.concatenate([r[:5] for r in rows])

@@ -627,6 +627,7 @@ double gtg_cholesky_flops_block_level(gtg_handle c) {
   return c->chol_flops_block;
 }
 int64_t gtg_structure_hash(gtg_handle c) { return c ? (int64_t)(c->structure_hash & 0x7FFFFFFFFFFFFFFFull) : -1; }
+int gtg_smart_repeated_keys(gtg_handle c) { return c && c->uploaded ? (c->smart_repeats ? 1 : 0) : -1; }
 double gtg_linearize_bytes(gtg_handle c) { return c ? c->lin_bytes : 0.0; }
 
 // debug only (not in the public header): ms per K=256 trailing update over an m x m tile grid, with ablations

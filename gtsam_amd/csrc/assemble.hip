@@ -802,6 +802,23 @@ __global__ __launch_bounds__(kBlock) void k_smart_hdiag(int32_t n_red_vars, cons
   }
   if ((int)threadIdx.x < d) hdiag[red_off[r] + threadIdx.x] -= part[0][threadIdx.x];
 }
+// (1b) A rig-type factor (SmartProjectionRigFactor) may see its landmark several times from one pose; its Hessian factor lives on the
+// unique keys, so the diagonal block of that pose loses |row_i(sum_o E_o)|^2 where (1) took sum_o |row_i(E_o)|^2.  One lane per
+// (pose with such sightings, row): the cross terms of its groups, group after group in table order, on top of what (1) left.  Launched
+// only for a graph with a repeated key (gtg_context::smart_repeats); E: the slots of the projection range.
+__global__ __launch_bounds__(64) void k_smart_hdiag_repeats(SmartRepeats t, const int32_t* __restrict__ red_index, const int64_t* __restrict__ red_off,
+    const int32_t* __restrict__ status, const double* __restrict__ E, double* __restrict__ hdiag) {
+  const int gl = blockIdx.x * 64 + threadIdx.x;
+  const int v = gl / 6, i = gl - 6 * v;
+  if (v >= t.n_vars) return;
+  double acc = 0.0;
+  for (int g = t.grp_ptr[v]; g < t.grp_ptr[v + 1]; g++) {
+    const int st = status[t.track[g]];
+    if (st != 0 && !(st & kTriAtInfinity)) continue;
+    acc += smart_repeat_cross(E, kEStride, t.obs + t.obs_ptr[g], t.obs_ptr[g + 1] - t.obs_ptr[g], i, i);
+  }
+  hdiag[red_off[red_index[t.var[v]]] + i] -= acc;
+}
 // (2) The constant of that Hessian factor is b^T b (CameraSet.h:224), not b^T b - |L^-1 E^T b|^2: linear.error(delta) of the
 // reference lies 0.5 |y_l|^2 per contributing smart landmark above the error of the explicit system at the optimal point update.
 // A JacobianFactorQ / JacobianFactorSVD (JACOBIAN_Q, JACOBIAN_SVD) is Q [F | b] with the projector Q = I - E P E^T instead: its
@@ -830,6 +847,9 @@ void launch_smart_hdiag(gtg_context& c) {
   hipLaunchKernelGGL(k_smart_hdiag, dim3((unsigned)std::max(c.n_red_vars, 1)), dim3(kBlock), 0, c.stream, c.n_red_vars, c.red_inc_ptr.p, c.red_inc_kind.p,
                      c.red_inc_idx.p, c.red_dim.p, c.red_off.p, c.obs_smart.p, c.smart_lin_status.p, c.E.p, c.hdiag_red.p,
                      c.smart_pose ? (int)INC_PROJ : (int)INC_SFM, c.smart_pose ? c.f.n_sfm : (int64_t)0);
+  if (c.smart_repeats && c.n_rep_vars)
+    hipLaunchKernelGGL(k_smart_hdiag_repeats, dim3((unsigned)((6 * c.n_rep_vars + 63) / 64)), dim3(64), 0, c.stream, smart_repeats(c), c.red_index.p,
+                       c.red_off.p, c.smart_lin_status.p, c.E.p + (int64_t)kEStride * c.f.n_sfm, c.hdiag_red.p);
   check_hip(hipGetLastError(), "smart_hdiag");
 }
 void launch_smart_lin1(gtg_context& c) {
@@ -908,7 +928,8 @@ static void prewarm_assemble(int) {
                    (const void*)k_point_factor, (const void*)k_obs_E<kSfmRec, 9, 2, true>, (const void*)k_obs_E<kSfmRec, 9, 2, false>, (const void*)k_obs_E<kProjRec, 6, 2, false>, (const void*)k_obs_E<kStereoRec, 6, 3, false>, (const void*)k_obs_v<kStereoRec, 6, 3, false>,
                    (const void*)k_obs_v<kSfmRec, 9, 2, true>, (const void*)k_obs_v<kSfmRec, 9, 2, false>, (const void*)k_obs_v<kProjRec, 6, 2, false>, (const void*)k_build_diag,
                    (const void*)k_scatter_hoff, (const void*)k_schur_pairs, (const void*)k_schur_pairs_heavy, (const void*)k_pad_diag, (const void*)k_backsub_lm,
-                   (const void*)k_scatter_delta, (const void*)k_obs_wpos, (const void*)k_cam_pack, (const void*)k_smart_hdiag, (const void*)k_smart_lin1});
+                   (const void*)k_scatter_delta, (const void*)k_obs_wpos, (const void*)k_cam_pack, (const void*)k_smart_hdiag, (const void*)k_smart_lin1,
+                   (const void*)k_smart_hdiag_repeats});
 }
 static PrewarmUnit prewarm_assemble_registered(prewarm_assemble);
 

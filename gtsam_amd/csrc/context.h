@@ -212,6 +212,13 @@ struct gtg_context {
   // SmartProjectionPoseFactor<Cal3_S2> (gtg_problem.smart_calib >= 0): the measurements are PROJECTION observations smart_obs0 .. of
   // the proj tables instead (keys POSE3, one shared Cal3_S2, optional body_P_sensor); a graph has smart factors of one kind only.  f.form is ProjForm::Rows2Smart exactly when this is set
   bool smart_pose = false;
+  // SmartProjectionRigFactor (gtg_problem.smart_calib == GTG_SMART_RIG) joins the same range with a calib / sensor entry per measurement
+  // and may name a pose several times in one track.  smart_repeats: some rig-type track of the WHOLE graph does; then rep_* list this
+  // shard's sightings of such (pose, track) groups, CSR by pose variable (rep_var ascending) -> group -> observation of the projection
+  // range (in range order), for the kernels that add the cross terms of a group to the Hessian diagonal and the block-Jacobi blocks
+  bool smart_repeats = false;
+  int32_t n_rep_vars = 0;
+  gt::DevBuf<int32_t> rep_var, rep_grp_ptr, rep_obs_ptr, rep_smart, rep_obs;
   gt::DevBuf<int32_t> obs_smart, lm_smart;  // per observation of the range the smart measurements live in (GeneralSFM, or projection when smart_pose) / per landmark: its smart factor or -1
   gt::DevBuf<int32_t> var_type;
   gt::DevBuf<int64_t> val_off, dim_off;

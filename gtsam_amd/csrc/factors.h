@@ -482,4 +482,23 @@ GT_HD double prior_error(int vtype, const double* x, const double* z, const Nois
   return factor_loss(n, e);
 }
 
+// ---- a pose named several times in one smart track (SmartProjectionRigFactor) ------------------------------------
+// The reference builds that factor's Hessian on the UNIQUE keys (CameraSet::SchurComplementAndRearrangeBlocks,
+// slam/SmartProjectionRigFactor.h:312-322): the sightings o_0 .. o_{n-1} of one track made from one pose are one block row
+// F = [F_0; ..; F_{n-1}], and with E_o = F_o^T E_o' L^-T (the E slots) its diagonal block loses (sum_o E_o)(sum_o E_o)^T, not
+// sum_o E_o E_o^T.  This is entry (i, j) of the difference, sum_{a<b} (row_i(E_a) . row_j(E_b) + row_i(E_b) . row_j(E_a)): every
+// sighting against the running sum of the sightings before it, in list order (no cancellation, one fixed order).
+// E: the slots of the range `obs` indexes, `stride` doubles apart, 3 per row.
+GT_HD double smart_repeat_cross(const double* E, int stride, const int32_t* obs, int n, int i, int j) {
+  double si[3] = {0.0, 0.0, 0.0}, sj[3] = {0.0, 0.0, 0.0}, acc = 0.0;
+  if (i < j) { const int t = i; i = j; j = t; }     // (j, i) is computed as (i, j): the same bits on both sides of the diagonal
+  for (int a = 0; a < n; a++) {
+    const double* e = E + (int64_t)stride * obs[a];
+    const double* ei = e + 3 * i; const double* ej = e + 3 * j;
+    acc += ei[0] * sj[0] + ei[1] * sj[1] + ei[2] * sj[2] + si[0] * ej[0] + si[1] * ej[1] + si[2] * ej[2];
+    for (int k = 0; k < 3; k++) { si[k] += ei[k]; sj[k] += ej[k]; }
+  }
+  return acc;
+}
+
 }  // namespace gt

@@ -57,6 +57,10 @@ bool device_rcm(gtg_context& c, int n, const std::vector<int32_t>& edge_a, const
 void launch_smart_triangulate(gtg_context& c, double* values, const double* gate, bool for_linearize);   // gate: scalars with the linear errors (trial point) or null
 void launch_smart_hdiag(gtg_context& c);
 void launch_smart_lin1(gtg_context& c);
+// the (pose, rig-type track) groups with several sightings (gtg_context::rep_*) as the two kernels that read them take them
+// (k_smart_hdiag_repeats in assemble.hip, k_pcg_setup_repeats in pcg.hip)
+struct SmartRepeats { int32_t n_vars; const int32_t *var, *grp_ptr, *obs_ptr, *track, *obs; };
+inline SmartRepeats smart_repeats(const gtg_context& c) { return {c.n_rep_vars, c.rep_var.p, c.rep_grp_ptr.p, c.rep_obs_ptr.p, c.rep_smart.p, c.rep_obs.p}; }
 void exchange_sum(gtg_context& c, double* ptr, int64_t n);   // api.hip: all-reduce (sum) over the shards on the handle's stream; no-op on one shard
 void launch_backward_solve(gtg_context& c, SMat S, int NP, const CholPlan& plan, const double* Xinv, double* x, double* fail);
 

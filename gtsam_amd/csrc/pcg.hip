@@ -112,6 +112,23 @@ __global__ __launch_bounds__(64 * kSetupWaves) void k_pcg_setup(int32_t n_red_va
   }
 }
 
+// A pose that a rig-type smart factor names several times in one track (SmartProjectionRigFactor, unique keys): the Schur complement's
+// diagonal block of that pose holds (sum_o E_o)(sum_o E_o)^T over the sightings of a group where k_pcg_setup took sum_o E_o E_o^T.  One
+// lane per (pose with such sightings, entry of the 6 x 6 block) subtracts the cross terms E_a E_b^T + E_b E_a^T of its groups, group
+// after group in table order, between k_pcg_setup and the exchange / factorisation of the blocks.  (No status test: the E slots of a
+// track that failed are zero, as k_pcg_setup relies on.)  Launched only for a graph with a repeated key; E: the projection range's slots.
+__global__ __launch_bounds__(64) void k_pcg_setup_repeats(SmartRepeats t, const int32_t* __restrict__ red_index, const double* __restrict__ E,
+                                                          double* __restrict__ Mbj) {
+  const int gl = blockIdx.x * 64 + threadIdx.x;
+  const int v = gl / 36, e = gl - 36 * v;
+  if (v >= t.n_vars) return;
+  const int i = e / 6, j = e - 6 * i;
+  double acc = 0.0;
+  for (int g = t.grp_ptr[v]; g < t.grp_ptr[v + 1]; g++)
+    acc += smart_repeat_cross(E, kEStride, t.obs + t.obs_ptr[g], t.obs_ptr[g + 1] - t.obs_ptr[g], i, j);
+  Mbj[(int64_t)81 * red_index[t.var[v]] + i * 9 + j] -= acc;
+}
+
 __global__ __launch_bounds__(128) void k_pcg_factor(int32_t n_red_vars, const int32_t* __restrict__ red_dim, double* __restrict__ Mbj,
                                                     double* __restrict__ fail) {
   __shared__ double D[81], Ls[81];
@@ -436,6 +453,9 @@ int launch_pcg(gtg_context& c, double lambda, int diag, double dmin, double dmax
   hipLaunchKernelGGL(k_pcg_setup, dim3(std::max(nrv, 1)), dim3(64 * kSetupWaves), 0, s, nrv, c.red_inc_ptr.p, c.red_inc_kind.p, c.red_inc_idx.p,
                      c.red_dim.p, c.red_off.p, c.obs_lm.p, c.f.n_sfm, c.Hd.p, c.gred0.p, c.hdiag_red.p, c.E.p, c.ylm.p, is, diag,
                      dmin, dmax, first, b, c.pcg_bj.p);
+  if (c.smart_repeats && c.n_rep_vars)
+    hipLaunchKernelGGL(k_pcg_setup_repeats, dim3((unsigned)((36 * c.n_rep_vars + 63) / 64)), dim3(64), 0, s, smart_repeats(c), c.red_index.p,
+                       c.E.p + (int64_t)kEStride * c.f.n_sfm, c.pcg_bj.p);
   if (sharded) { exchange_sum(c, b, NP); exchange_sum(c, c.pcg_bj.p, 81 * (int64_t)nrv); }
   hipLaunchKernelGGL(k_pcg_factor, dim3(std::max(nrv, 1)), dim3(128), 0, s, nrv, c.red_dim.p, c.pcg_bj.p, c.scalars.p + SC_FAIL);
   ApplyArgs aa{c.red_inc_ptr.p, c.red_inc_kind.p, c.red_inc_idx.p, c.red_dim.p, c.red_off.p, c.obs_lm.p, c.red_index.p,

@@ -23,13 +23,16 @@ static_assert(kSamBearingRange == GTG_SAM_BEARING_RANGE && kSamRange == GTG_SAM_
 // Smart factors become what the rest of the library already knows: a hidden POINT3 variable per factor behind the caller's
 // variables and one observation per measurement behind the caller's -- a GeneralSFM observation for a camera-type factor
 // (SmartProjectionFactor<PinholeCamera<Cal3Bundler>>), a projection observation for a pose-type factor (SmartProjectionPoseFactor<Cal3_S2>:
-// smart_calib >= 0); every table is built from problem().  Without smart factors that is the caller's struct and nothing is owned.
+// smart_calib >= 0) or a rig-type factor (SmartProjectionRigFactor<PinholePose<Cal3_S2>>: smart_calib == GTG_SMART_RIG, calib and sensor
+// per measurement); every table is built from problem().  Without smart factors that is the caller's struct and nothing is owned.
 // Pure host code.
 struct SmartView {
   std::vector<int32_t> var_type, sfm_cam, sfm_point, sfm_noise, proj_pose, proj_point, proj_noise, proj_calib, proj_sensor;
   std::vector<int32_t> of_obs;   // per observation of the range the measurements joined in problem(): its smart factor, -1 for the caller's own factors
   std::vector<double> sfm_z, proj_z;
+  std::vector<uint8_t> is_rig;   // per smart factor: rig-type
   bool pose = false;             // the range is the projection range
+  bool repeats = false;          // some rig-type factor names a pose key more than once (the whole table: the same on every shard)
   explicit SmartView(const gtg_problem& user);
   SmartView(const SmartView&) = delete;   // (p may point at q)
   const gtg_problem& problem() const { return *p; }
@@ -37,6 +40,7 @@ struct SmartView {
   gtg_problem q; const gtg_problem* p;
   void expand_cameras(const gtg_problem& user, int64_t n_smart);
   void expand_poses(const gtg_problem& user, int64_t n_smart);
+  void expand_rig(const gtg_problem& user, int64_t i);
 };
 
 SmartView::SmartView(const gtg_problem& user) : q(user), p(&user) {
@@ -46,7 +50,7 @@ SmartView::SmartView(const gtg_problem& user) : q(user), p(&user) {
     throw std::invalid_argument("smart factor tables missing");
   const int64_t n_meas = user.smart_ptr[n_smart];
   int64_t n_pose = 0;
-  if (user.smart_calib) for (int64_t i = 0; i < n_smart; i++) n_pose += user.smart_calib[i] >= 0;
+  if (user.smart_calib) for (int64_t i = 0; i < n_smart; i++) n_pose += user.smart_calib[i] != -1;   // (pose-type and rig-type)
   if (n_pose != 0 && n_pose != n_smart)
     throw std::invalid_argument("smart factors: a graph that mixes camera-type (smart_calib -1) and pose-type (smart_calib >= 0) smart factors is not supported");
   pose = n_pose > 0;
@@ -99,6 +103,39 @@ void SmartView::expand_cameras(const gtg_problem& user, int64_t n_smart) {
   q.sfm_noise = sfm_noise.data(); q.sfm_z = sfm_z.data();
 }
 
+// rig-type factor i: as a pose-type factor, with the calib / sensor entry of every measurement; what the reference's constructor and
+// this library's scope rule out is refused, each with its own message
+void SmartView::expand_rig(const gtg_problem& user, int64_t i) {
+  const double* sp = user.smart_params + 8 * i;
+  if (sp[4] != 1.0) throw std::invalid_argument("smart factor: a rig-type smart factor needs degeneracyMode 1 (SmartProjectionRigFactor: degeneracyMode must be set to ZERO_ON_DEGENERACY)");
+  if (sp[5] != 0.0) throw std::invalid_argument("smart factor: a rig-type smart factor needs linearizationMode 0 (SmartProjectionRigFactor: linearizationMode must be set to HESSIAN)");
+  if (sp[6] != 0.0) throw std::invalid_argument("smart factor: enableEPI is not supported on a rig-type smart factor (the refinement is written for Cal3Bundler cameras)");
+  if (user.smart_sensor && user.smart_sensor[i] != -1)
+    throw std::invalid_argument("smart factor: smart_sensor must be -1 on a rig-type smart factor (its extrinsics are per measurement: smart_meas_sensor)");
+  if (!user.smart_meas_calib || !user.smart_meas_sensor)
+    throw std::invalid_argument("smart factor: a GTG_SMART_RIG factor needs the per-measurement tables smart_meas_calib and smart_meas_sensor");
+  std::vector<int32_t> keys;
+  for (int64_t k = user.smart_ptr[i]; k < user.smart_ptr[i + 1]; k++) {
+    const int v = user.smart_cam[k];
+    const int32_t ci = user.smart_meas_calib[k], si = user.smart_meas_sensor[k];
+    if (ci < 0 || ci >= user.n_calib || !user.calib) throw std::invalid_argument("smart factor: smart_meas_calib index out of range");
+    if (si < -1 || si >= user.n_sensor || (si >= 0 && !user.sensor)) throw std::invalid_argument("smart factor: smart_meas_sensor index out of range");
+    if (user.calib_distortion)
+      for (int j = 0; j < 4; j++)
+        if (user.calib_distortion[4 * (size_t)ci + j] != 0.0)
+          throw std::invalid_argument("smart factor: a calibration with Cal3DS2 distortion is not supported by a rig-type smart factor (SmartProjectionRigFactor<PinholePose<Cal3_S2>> only)");
+    if (v < 0 || v >= user.n_vars || user.var_type[v] != GTG_VAR_POSE3)
+      throw std::invalid_argument("smart factor: the keys of a rig-type smart factor must be POSE3 variables");
+    proj_pose.push_back(v); proj_point.push_back((int32_t)(user.n_vars + i)); proj_noise.push_back(user.smart_noise[i]);
+    proj_calib.push_back(ci); proj_sensor.push_back(si);
+    proj_z.push_back(user.smart_z[2 * k]); proj_z.push_back(user.smart_z[2 * k + 1]);
+    of_obs.push_back((int32_t)i);
+    keys.push_back(v);
+  }
+  std::sort(keys.begin(), keys.end());
+  if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) repeats = true;
+}
+
 // pose-type: one projection observation per measurement behind the caller's own GTG_FAC_PROJECTION observations, the way the stereo
 // factors joined that range
 void SmartView::expand_poses(const gtg_problem& user, int64_t n_smart) {
@@ -109,9 +146,11 @@ void SmartView::expand_poses(const gtg_problem& user, int64_t n_smart) {
   if (user.proj_sensor) proj_sensor.assign(user.proj_sensor, user.proj_sensor + user.n_proj); else proj_sensor.assign((size_t)user.n_proj, -1);
   proj_z.assign(user.proj_z, user.proj_z + 2 * user.n_proj);
   of_obs.assign((size_t)user.n_proj, -1);
+  is_rig.assign((size_t)n_smart, 0);
   for (int64_t i = 0; i < n_smart; i++) {
     const int32_t ci = user.smart_calib[i], si = user.smart_sensor ? user.smart_sensor[i] : -1;
-    if (ci >= user.n_calib || !user.calib) throw std::invalid_argument("smart factor: smart_calib index out of range");
+    if (ci == GTG_SMART_RIG) { is_rig[(size_t)i] = 1; expand_rig(user, i); continue; }
+    if (ci < 0 || ci >= user.n_calib || !user.calib) throw std::invalid_argument("smart factor: smart_calib index out of range");
     if (si < -1 || si >= user.n_sensor || (si >= 0 && !user.sensor)) throw std::invalid_argument("smart factor: smart_sensor index out of range");
     if (user.calib_distortion)
       for (int j = 0; j < 4; j++)
@@ -270,7 +309,7 @@ class SideUpload {
 // tracks it owns, in the order of the whole table.  The per-factor arrays keep the GLOBAL factor index (parameters, status,
 // cache); a factor of another shard has no measurements here (smart_ptr[i + 1] == smart_ptr[i]) and is skipped.
 // (n, point): the observation range the measurements joined -- GeneralSFM, or projection for pose-type factors.
-void upload_smart_tracks(gtg_context& c, int64_t n, const int32_t* point, const std::vector<int32_t>& of_obs, const ShardFilter& own) {
+std::vector<int32_t> upload_smart_tracks(gtg_context& c, int64_t n, const int32_t* point, const std::vector<int32_t>& of_obs, const ShardFilter& own) {
   std::vector<int64_t> rel((size_t)c.n_smart + 1, 0);
   std::vector<int32_t> of_local;
   int64_t obs0 = 0;
@@ -284,6 +323,39 @@ void upload_smart_tracks(gtg_context& c, int64_t n, const int32_t* point, const 
   c.smart_obs0 = obs0;
   up(c.smart_ptr, rel, c.stream);
   up(c.obs_smart, of_local, c.stream);
+  return of_local;
+}
+
+// The sightings of every (pose, rig-type track) group with more than one member among this shard's observations (a track lives on one
+// shard with all its measurements): sorted by (pose variable, track, observation), so that every sum over a group runs in range order.
+// pose / of_local: this shard's part of the projection range.
+void upload_smart_repeats(gtg_context& c, const std::vector<int32_t>& pose, const std::vector<int32_t>& of_local, const std::vector<uint8_t>& is_rig) {
+  c.n_rep_vars = 0;
+  c.rep_var.free(); c.rep_grp_ptr.free(); c.rep_obs_ptr.free(); c.rep_smart.free(); c.rep_obs.free();
+  if (!c.smart_repeats) return;
+  struct Sighting { int32_t var, track, obs; };
+  std::vector<Sighting> s;
+  for (size_t o = 0; o < of_local.size(); o++)
+    if (of_local[o] >= 0 && is_rig[(size_t)of_local[o]]) s.push_back({pose[o], of_local[o], (int32_t)o});
+  std::sort(s.begin(), s.end(), [](const Sighting& a, const Sighting& b) {
+    return a.var != b.var ? a.var < b.var : a.track != b.track ? a.track < b.track : a.obs < b.obs; });
+  std::vector<int32_t> var, grp_ptr{0}, obs_ptr{0}, track, obs;
+  for (size_t a = 0; a < s.size();) {
+    size_t b = a + 1;
+    while (b < s.size() && s[b].var == s[a].var && s[b].track == s[a].track) b++;
+    if (b - a > 1) {
+      if (var.empty() || var.back() != s[a].var) { if (!var.empty()) grp_ptr.push_back((int32_t)track.size()); var.push_back(s[a].var); }
+      track.push_back(s[a].track);
+      for (size_t k = a; k < b; k++) obs.push_back(s[k].obs);
+      obs_ptr.push_back((int32_t)obs.size());
+    }
+    a = b;
+  }
+  if (var.empty()) return;     // (the groups of the graph are on other shards)
+  grp_ptr.push_back((int32_t)track.size());
+  c.n_rep_vars = (int32_t)var.size();
+  up(c.rep_var, var, c.stream); up(c.rep_grp_ptr, grp_ptr, c.stream); up(c.rep_obs_ptr, obs_ptr, c.stream);
+  up(c.rep_smart, track, c.stream); up(c.rep_obs, obs, c.stream);
 }
 
 void upload_sfm(gtg_context& c, HostIndex& hi, const gtg_problem& p, const std::vector<int32_t>& of_obs, const ShardFilter& own, SideUpload& side) {
@@ -312,7 +384,7 @@ void upload_sfm(gtg_context& c, HostIndex& hi, const gtg_problem& p, const std::
   hi.sfm_cam = std::move(cam); hi.sfm_point = std::move(pt);
 }
 
-void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, const std::vector<int32_t>& of_obs, const ShardFilter& own) {
+void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, const std::vector<int32_t>& of_obs, const std::vector<uint8_t>& is_rig, const ShardFilter& own) {
   auto& f = c.f;
   std::vector<int32_t> pose, pt, nz, cal, sen; std::vector<double> z;
   const int64_t n_stereo = p.n_stereo > 0 ? p.n_stereo : 0, n_sam = p.n_sam > 0 ? p.n_sam : 0;
@@ -330,7 +402,8 @@ void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, cons
     if (proj_rows(f.form) == 3) z.push_back(0.0);   // a three-row graph keeps three measurement entries per camera observation
   }
   f.n_mono = (int64_t)pose.size();
-  if (c.smart_pose) upload_smart_tracks(c, p.n_proj, p.proj_point, of_obs, own);   // (their measurements are part of the range above)
+  if (c.smart_pose) upload_smart_repeats(c, pose, upload_smart_tracks(c, p.n_proj, p.proj_point, of_obs, own), is_rig);   // (their measurements are part of the range above)
+  else upload_smart_repeats(c, pose, {}, is_rig);
   // the stereo factors join the observation range behind the monocular ones: the symbolic analysis, the incidence lists, the E slots,
   // the Schur terms, PCG and the shard filter see more projection observations and nothing else
   if (n_stereo) {
@@ -448,7 +521,7 @@ void upload_problem(gtg_context& c, const gtg_problem& user, int shard, int n_sh
   c.fused_sfm = GTG_FUSED_SFM != 0 && c.n_smart == 0 && !(user.n_stereo > 0) && !(user.n_sam > 0);
   const SmartView view(user);
   const gtg_problem& p = view.problem();
-  c.smart_pose = view.pose; c.smart_obs0 = view.pose ? user.n_proj : user.n_sfm;
+  c.smart_pose = view.pose; c.smart_repeats = view.repeats; c.smart_obs0 = view.pose ? user.n_proj : user.n_sfm;
   upload_smart_state(c, user);
   layout_variables(c, p);
   upload_noise_table(c, p);
@@ -457,7 +530,7 @@ void upload_problem(gtg_context& c, const gtg_problem& user, int shard, int n_sh
   keep_whole_graph_keys(hi, p, n_shards);
   SideUpload side;   // started by upload_sfm for a whole, non-empty table
   upload_sfm(c, hi, p, view.of_obs, own, side);
-  upload_projection(c, hi, p, view.of_obs, own);
+  upload_projection(c, hi, p, view.of_obs, view.is_rig, own);
   upload_between(c, hi, p, own);
   upload_priors(c, hi, p, own);
   clk.lap("factor tables (shard filter + upload)");

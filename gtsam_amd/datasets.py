@@ -623,6 +623,148 @@ def smart_pose_scene(name, seed=0, scene=None, params=None):
     return smart_pose_graph(seed=seed, params=prm, **scene)
 
 
+def smart_rig_graph(rig, n_poses, tracks, seed=0, arc=0.4, radius=8.0, box=(2.0, 1.5, 2.0), sigma=1.0, pixel_noise=0.3, params=None,
+                    far_distance=(1500.0, 4000.0), outlier_shift=150.0, explicit_landmarks=0, see=0.6, between_chain=False, priors=(0,),
+                    init_noise=(0.004, 0.02)):
+    """A multi-camera visual-odometry scene whose landmarks live inside SmartProjectionRigFactors (SmartProjectionRigFactor<
+    PinholePose<Cal3_S2>>), built through the API mirror the way user code would.  `rig`: ((fx, fy, s, u0, v0), extrinsic) per camera,
+    extrinsic = None (identity) or (rotation vector, translation) of body_P_sensor.  `n_poses` BODY poses on an arc of half opening `arc`
+    and radius `radius` look inward at points in `box`.  `tracks`: one entry per smart factor, in graph order --
+      ("views", [(pose, camera id), ...])  a rig factor with exactly these sightings (a pose may occur several times);
+      ("random",)     a rig factor: every (pose, camera) sees the point with probability `see` (at least two sightings);
+      ("single",)     a rig factor with one sighting (DEGENERATE);
+      ("far",)        "random" on a point `far_distance` away (FAR_POINT under a landmarkDistanceThreshold);
+      ("outlier",)    "random" with the last measurement moved by `outlier_shift` pixels (OUTLIER under a
+                      dynamicOutlierRejectionThreshold);
+      ("pose",)       a SmartProjectionPose3Factor through camera 0 of the rig (its K, its extrinsic as body_P_sensor), seen from every
+                      pose with probability `see` (at least two).
+    `explicit_landmarks`: that many further points are Point3 variables with GenericProjectionFactors through camera 0;
+    `between_chain`: BetweenFactor<Pose3> along the arc; `priors`: the poses with a Diagonal prior.
+    Graph order: smart factors, projection factors, between factors, priors.  Returns (graph, initial values, info) with
+    info["kind"][t] the track's kind and info["points"] the true points."""
+    from . import api as A
+    rng = np.random.default_rng(seed)
+    ang = np.linspace(-arc, arc, n_poses)
+    tb = np.stack([radius * np.sin(ang), 0.02 * radius * rng.normal(size=n_poses), -radius * np.cos(ang)], 1)
+    Rb = _rodrigues(np.stack([0.02 * rng.normal(size=n_poses), -ang, 0.02 * rng.normal(size=n_poses)], 1))   # +z looks at the origin
+    cams = A.CameraSetPinholePoseCal3_S2()
+    ext = []
+    for K, e in rig:
+        pose = A.Pose3() if e is None else A.Pose3(A.Rot3(_rodrigues(np.array([e[0]]))[0]), np.array(e[1], np.float64))
+        cams.push_back(A.PinholePoseCal3_S2(pose, A.Cal3_S2(*K)))
+        ext.append(pose)
+    n_tracks = len(tracks)
+    pts = np.stack([rng.uniform(-b, b, n_tracks + explicit_landmarks) for b in box], 1)
+    model = A.noiseModel.Isotropic.Sigma(2, sigma)
+    X, L = A.symbol_shorthand.X, A.symbol_shorthand.L
+    params = params or A.SmartProjectionParams(degeneracyMode=1)     # (what the rig factor's constructor accepts)
+
+    def pixel(i, c, pt):
+        R = Rb[i] @ ext[c].R; t = tb[i] + Rb[i] @ ext[c].t
+        q = R.T @ (pt - t)
+        fx, fy, s, u0, v0 = cams[c].calibration().v
+        u, v = q[0] / q[2], q[1] / q[2]
+        return np.array([fx * u + s * v + u0, fy * v + v0]) + pixel_noise * rng.normal(size=2)
+
+    def random_views(n_cams_used):
+        seen = np.argwhere(rng.uniform(size=(n_poses, n_cams_used)) < see)
+        if seen.shape[0] < 2:
+            seen = np.array([[0, 0], [n_poses - 1, 0]])
+        return [(int(i), int(c)) for i, c in seen]
+
+    graph, initial = A.NonlinearFactorGraph(), A.Values()
+    for t, spec in enumerate(tracks):
+        kind = spec[0]
+        if kind == "far":
+            d = rng.uniform(*far_distance)
+            pts[t] = [d * rng.uniform(-0.15, 0.15), d * rng.uniform(-0.12, 0.12), d]
+        if kind == "pose":
+            f = A.SmartProjectionPose3Factor(model, cams[0].calibration(), None if rig[0][1] is None else ext[0], params)
+            for i, _ in random_views(1):
+                f.add(pixel(i, 0, pts[t]), X(i))
+            graph.add(f)
+            continue
+        views = list(spec[1]) if kind == "views" else random_views(len(rig))
+        if kind == "single":
+            views = views[:1]
+        f = A.SmartProjectionRigFactorPinholePoseCal3_S2(model, cams, params)
+        for n, (i, c) in enumerate(views):
+            z = pixel(i, c, pts[t])
+            if kind == "outlier" and n == len(views) - 1:
+                z = z + outlier_shift * np.array([0.8, -0.6])
+            f.add(z, X(i), c)
+        graph.add(f)
+    for j in range(explicit_landmarks):
+        views = np.flatnonzero(rng.uniform(size=n_poses) < see)
+        if views.size < 2:
+            views = np.arange(2)
+        for i in views:
+            graph.add(A.GenericProjectionFactorCal3_S2(pixel(int(i), 0, pts[n_tracks + j]), model, X(int(i)), L(j), cams[0].calibration(),
+                                                       None if rig[0][1] is None else ext[0]))
+    nm = A.noiseModel
+    if between_chain:
+        n6b = nm.Diagonal.Sigmas([0.02, 0.02, 0.03, 0.1, 0.1, 0.15])
+        for i in range(n_poses - 1):
+            Rz = Rb[i].T @ Rb[i + 1]; tz = Rb[i].T @ (tb[i + 1] - tb[i])
+            graph.add(A.BetweenFactorPose3(X(i), X(i + 1), A.Pose3(A.Rot3(Rz @ _rodrigues(rng.normal(0, 0.005, (1, 3)))[0]), tz + rng.normal(0, 0.02, 3)), n6b))
+    n6 = nm.Diagonal.Sigmas([0.1] * 3 + [0.3] * 3)
+    for i in priors:
+        graph.addPriorPose3(X(i), A.Pose3(A.Rot3(Rb[i]), tb[i]), n6)
+    Ri = Rb @ _rodrigues(rng.normal(0, init_noise[0], (n_poses, 3)))
+    ti = tb + rng.normal(0, init_noise[1], tb.shape)
+    for i in range(n_poses):
+        initial.insert(X(i), A.Pose3(A.Rot3(Ri[i]), ti[i]))
+    for j in range(explicit_landmarks):
+        initial.insert(L(j), pts[n_tracks + j] + rng.normal(0, 0.05, 3))
+    return graph, initial, {"kind": [s[0] for s in tracks], "points": pts[:n_tracks]}
+
+
+def _rig_pair_tracks():
+    both = lambda i: [(i, 0), (i, 1)]
+    # both cameras from all three poses (three of them, so that the third pose is held by more than one landmark); both cameras from
+    # ONE pose only (one unique key: the rig's baseline triangulates it); no repetition; DEGENERATE; FAR_POINT
+    return ([("views", both(0) + both(1) + both(2))] * 3 + [("views", both(1))] + [("views", [(0, 0), (1, 1), (2, 0)]), ("views", [(0, 1), (1, 0), (2, 1)])]
+            + [("single",), ("far",)])
+
+
+def _rig_mixed_tracks():
+    t = []
+    for k in range(151):
+        t.append(("pose",) if k % 9 == 4 else ("random",))
+    for k, kind in ((7, "single"), (38, "single"), (77, "far"), (90, "far"), (101, "far"), (120, "outlier"), (133, "outlier")):
+        t[k] = (kind,)
+    return t
+
+
+# The rig-type smart scenes the fixtures of tests/golden/make_golden_smart_rig.py are recorded on (a seed is part of the fixture, as for
+# SMART_POSE_SCENES).  smart_rig_pair: two cameras with different K (one with skew), camera 0 without an extrinsic, camera 1 rotated and
+# offset; smart_rig_mixed: three cameras, pose-type smart factors and explicit landmarks beside the rig factors.
+SMART_RIG_SCENES = {
+    "smart_rig_pair": dict(scene=dict(rig=(((520.0, 515.0, 0.4, 320.0, 240.0), None),
+                                           ((480.0, 490.0, 0.0, 300.0, 250.0), ((0.03, -0.06, 0.02), (0.6, -0.04, 0.05)))),
+                                      n_poses=3, tracks=_rig_pair_tracks(), arc=0.25, sigma=1.0, pixel_noise=0.3, priors=(0, 1),
+                                      init_noise=(0.004, 0.02)),
+                           params=dict(degeneracyMode=1, landmarkDistanceThreshold=100.0)),
+    "smart_rig_mixed": dict(scene=dict(rig=(((520.0, 515.0, 0.3, 320.0, 240.0), ((0.02, -0.03, 0.01), (0.1, -0.05, 0.2))),
+                                            ((500.0, 505.0, 0.0, 310.0, 245.0), ((0.01, 0.08, -0.02), (0.45, 0.0, 0.15))),
+                                            ((540.0, 530.0, -0.2, 330.0, 235.0), ((-0.02, -0.09, 0.01), (-0.4, 0.03, 0.18)))),
+                                       n_poses=20, tracks=_rig_mixed_tracks(), arc=0.5, sigma=1.5, pixel_noise=0.7, see=0.65,
+                                       explicit_landmarks=5, between_chain=True, priors=(0,), init_noise=(0.004, 0.02)),
+                            params=dict(degeneracyMode=1, landmarkDistanceThreshold=100.0, dynamicOutlierRejectionThreshold=40.0)),
+}
+
+
+def smart_rig_scene(name, seed=0, scene=None, params=None):
+    """(graph, initial values, info) of one of SMART_RIG_SCENES; `scene` / `params`: keyword arguments of smart_rig_graph /
+    SmartProjectionParams fields to replace."""
+    from . import api as A
+    spec = SMART_RIG_SCENES[name]
+    prm = A.SmartProjectionParams()
+    for k, v in {**spec["params"], **(params or {})}.items():
+        setattr(prm, k, v)
+    return smart_rig_graph(seed=seed, params=prm, **{**spec["scene"], **(scene or {})})
+
+
 def _noisy_bearing(rng, q, sigma):
     """The direction of the local point q with a tangent-plane error of `sigma` radians, as a Unit3."""
     from . import api as A

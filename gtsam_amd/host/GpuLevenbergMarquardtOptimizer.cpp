@@ -20,6 +20,7 @@
 #include <gtsam/slam/ProjectionFactor.h>
 #include <gtsam/slam/SmartProjectionFactor.h>
 #include <gtsam/slam/SmartProjectionPoseFactor.h>
+#include <gtsam/slam/SmartProjectionRigFactor.h>
 #include <gtsam/slam/StereoFactor.h>
 #include <gtsam/sam/BearingFactor.h>
 #include <gtsam/sam/BearingRangeFactor.h>
@@ -58,6 +59,7 @@
 #include <iostream>
 #include <limits>
 #include <map>
+#include <set>
 #include <new>
 #include <stdexcept>
 #include <thread>
@@ -94,6 +96,9 @@ struct SmartPoseAccess : SmartPoseFactor {
   static SmartProjectionParams SmartProjectionFactor<PoseCamera>::* params() { return &SmartPoseAccess::params_; }
   static std::optional<Pose3> SmartFactorBase<PoseCamera>::* sensor() { return &SmartPoseAccess::body_P_sensor_; }
 };
+// SmartProjectionRigFactor<PinholePose<Cal3_S2>>: the same bases, so the same accessors read its noise model and parameters; the rig,
+// the camera ids and the non-unique keys have accessors of their own (slam/SmartProjectionRigFactor.h:166-174)
+typedef SmartProjectionRigFactor<PoseCamera> SmartRigFactor;
 typedef internal::LevenbergMarquardtState State;
 
 // The States THIS class publishes have a dynamic type of their own: that -- not an address, which the allocator hands out again -- is
@@ -383,7 +388,12 @@ struct Extract {
   std::vector<const Cal3_S2Stereo*> st_cal;                                 // calibration object per stereo factor
   std::vector<const Cal3_S2*> sm_cal;                                       // per smart factor: the shared K of a pose-type factor, null for a camera-type one
   std::vector<int32_t> sm_sen;                                              // per smart factor: row of `sensor` (this chunk's) or -1
+  std::vector<const SmartRigFactor::Cameras*> sm_rig;                       // per smart factor: the rig of a rig-type factor, else null
+  std::vector<int32_t> sm_cid;                                              // per smart measurement: camera id in that rig (0 for other factors)
   std::vector<uint8_t> sensor_shared;                                       // per row of `sensor`: 1 = a smart factor's body_P_sensor, shared by value (mergeTables)
+  std::vector<std::pair<const void*, int>> cal_order;                       // the calibration objects the chunk's factors name, in the order they are first met (0 Cal3_S2, 1 Cal3DS2, 2 Cal3_S2Stereo):
+  std::set<const void*> cal_seen;                                           // the calib table gets its rows in GRAPH order, whichever factor type names an object first
+  void calibration(const void* K, int kind) { if (cal_seen.insert(K).second) cal_order.emplace_back(K, kind); }
   std::exception_ptr err;                                                   // what the chunk's first offending factor threw
   static void run(Runs& r, const SharedNoiseModel& nm) { if (!r.empty() && r.back().second.get() == nm.get()) r.back().first++; else r.emplace_back(1, nm); }
   static double* grow(std::vector<double>& v, size_t n) { v.resize(v.size() + n); return v.data() + v.size() - n; }   // n more doubles, zero-filled
@@ -402,6 +412,7 @@ template <class CAL> void addProjection(Extract& x, const GenericProjectionFacto
   x.pj_z.push_back(p.measured().x()); x.pj_z.push_back(p.measured().y());
   Extract::run(x.pj_nz, p.noiseModel());
   x.pj_cal.emplace_back(p.calibration().get(), std::is_same<CAL, Cal3DS2>::value ? 1 : 0);
+  x.calibration(p.calibration().get(), std::is_same<CAL, Cal3DS2>::value ? 1 : 0);
   if (p.body_P_sensor()) { x.pj_sen.push_back((int32_t)(x.sensor.size() / 12)); packPose(*p.body_P_sensor(), Extract::grow(x.sensor, 12)); x.sensor_shared.push_back(0); }
   else x.pj_sen.push_back(-1);
 }
@@ -413,7 +424,7 @@ void addStereo(Extract& x, const StereoFactor& p, const std::vector<Key>& keys) 
   x.st_pose.push_back(idOf(keys, p.key1())); x.st_pt.push_back(idOf(keys, p.key2()));
   x.st_z.push_back(p.measured().uL()); x.st_z.push_back(p.measured().uR()); x.st_z.push_back(p.measured().v());
   Extract::run(x.st_nz, p.noiseModel());
-  x.st_cal.push_back(p.calibration().get());
+  x.st_cal.push_back(p.calibration().get()); x.calibration(p.calibration().get(), 2);
   if (p.body_P_sensor()) { x.st_sen.push_back((int32_t)(x.sensor.size() / 12)); packPose(*p.body_P_sensor(), Extract::grow(x.sensor, 12)); x.sensor_shared.push_back(0); }
   else x.st_sen.push_back(-1);
 }
@@ -429,7 +440,7 @@ void addSam(Extract& x, int32_t kind, Key pose, Key point, const Unit3* bearing,
 }
 // the rows every smart factor has, whatever its camera type: parameters, noise model, keys and measurements
 template <class FACTOR>
-void addSmartRows(Extract& x, const FACTOR& sf, const SmartProjectionParams& sp, const SharedIsotropic& iso, const std::vector<Key>& keys, const char* what) {
+void addSmartRows(Extract& x, const FACTOR& sf, const KeyVector& fkeys, const SmartProjectionParams& sp, const SharedIsotropic& iso, const std::vector<Key>& keys, const char* what) {
   x.fac_map.emplace_back(-2, (int64_t)x.sm_prm.size() / 8);   // (no Jacobian record: its linearisation is a Hessian factor)
   const TriangulationParameters& tp = sp.triangulation;
   // HESSIAN, JACOBIAN_Q and JACOBIAN_SVD are the same normal equations (the device never forms the factor itself); an
@@ -439,8 +450,8 @@ void addSmartRows(Extract& x, const FACTOR& sf, const SmartProjectionParams& sp,
   if (tp.enableEPI && tp.noiseModel) throw std::invalid_argument(std::string(what) + ": enableEPI with a noise model in the triangulation parameters is not supported");
   Extract::run(x.sm_nz, iso);
   const auto& zs = sf.measured();
-  if (zs.size() != sf.keys().size() || zs.empty()) throw std::invalid_argument(std::string(what) + ": measurements and keys do not match");
-  for (size_t k = 0; k < zs.size(); k++) { x.sm_cam.push_back(idOf(keys, sf.keys()[k])); x.sm_z.push_back(zs[k].x()); x.sm_z.push_back(zs[k].y()); }
+  if (zs.size() != fkeys.size() || zs.empty()) throw std::invalid_argument(std::string(what) + ": measurements and keys do not match");
+  for (size_t k = 0; k < zs.size(); k++) { x.sm_cam.push_back(idOf(keys, fkeys[k])); x.sm_z.push_back(zs[k].x()); x.sm_z.push_back(zs[k].y()); }
   x.sm_ptr.push_back((int64_t)x.sm_cam.size());
   x.sm_prm.insert(x.sm_prm.end(), {tp.rankTolerance, tp.landmarkDistanceThreshold, tp.dynamicOutlierRejectionThreshold, sp.retriangulationThreshold,
                                    sp.degeneracyMode == ZERO_ON_DEGENERACY ? 1.0 : (sp.degeneracyMode == HANDLE_INFINITY ? 2.0 : 0.0),
@@ -449,19 +460,33 @@ void addSmartRows(Extract& x, const FACTOR& sf, const SmartProjectionParams& sp,
 // SmartProjectionFactor<SfmCamera>.  (throwCheirality / verboseCheirality are read by the pose-only smart factors, not by
 // SmartProjectionFactor<CAMERA>.)
 void addSmart(Extract& x, const SmartFactor& sf, const std::vector<Key>& keys) {
-  addSmartRows(x, sf, sf.*SmartAccess::params(), sf.*SmartAccess::noise(), keys, "SmartProjectionFactor");
-  x.sm_cal.push_back(nullptr); x.sm_sen.push_back(-1);
+  addSmartRows(x, sf, sf.keys(), sf.*SmartAccess::params(), sf.*SmartAccess::noise(), keys, "SmartProjectionFactor");
+  x.sm_cal.push_back(nullptr); x.sm_sen.push_back(-1); x.sm_rig.push_back(nullptr); x.sm_cid.resize(x.sm_cam.size(), 0);
 }
 // SmartProjectionPoseFactor<Cal3_S2>: the keys are Pose3 variables, one shared K (a row of the calib table) and an optional
 // body_P_sensor (a row of the sensor table, shared by value among the smart factors)
 void addSmartPose(Extract& x, const SmartPoseFactor& sf, const std::vector<Key>& keys) {
   if (!sf.calibration()) throw std::invalid_argument("SmartProjectionPoseFactor: no calibration");
   if ((sf.*SmartPoseAccess::params()).triangulation.enableEPI) throw std::invalid_argument("SmartProjectionPoseFactor: enableEPI is not supported");
-  addSmartRows(x, sf, sf.*SmartPoseAccess::params(), sf.*SmartPoseAccess::noise(), keys, "SmartProjectionPoseFactor");
-  x.sm_cal.push_back(sf.calibration().get());
+  addSmartRows(x, sf, sf.keys(), sf.*SmartPoseAccess::params(), sf.*SmartPoseAccess::noise(), keys, "SmartProjectionPoseFactor");
+  x.sm_cal.push_back(sf.calibration().get()); x.calibration(sf.calibration().get(), 0); x.sm_rig.push_back(nullptr); x.sm_cid.resize(x.sm_cam.size(), 0);
   const std::optional<Pose3>& bs = sf.*SmartPoseAccess::sensor();
   if (bs) { x.sm_sen.push_back((int32_t)(x.sensor.size() / 12)); packPose(*bs, Extract::grow(x.sensor, 12)); x.sensor_shared.push_back(1); }
   else x.sm_sen.push_back(-1);
+}
+// SmartProjectionRigFactor<PinholePose<Cal3_S2>>: the keys are the BODY poses, one per measurement and possibly repeated
+// (nonUniqueKeys(); keys() holds the unique ones); every measurement names a camera of the rig, whose K and extrinsic become one calib
+// and one sensor row per (rig object, camera id) in mergeTables.  (The constructor has refused every degeneracy / linearisation mode
+// but ZERO_ON_DEGENERACY / HESSIAN.)
+void addSmartRig(Extract& x, const SmartRigFactor& sf, const std::vector<Key>& keys) {
+  if (!sf.cameraRig()) throw std::invalid_argument("SmartProjectionRigFactor: no camera rig");
+  const SmartProjectionParams& sp = sf.*SmartPoseAccess::params();
+  if (sp.triangulation.enableEPI) throw std::invalid_argument("SmartProjectionRigFactor: enableEPI is not supported");
+  if (sf.cameraIds().size() != sf.nonUniqueKeys().size()) throw std::invalid_argument("SmartProjectionRigFactor: camera ids and keys do not match");
+  for (size_t id : sf.cameraIds()) if (id >= sf.cameraRig()->size()) throw std::invalid_argument("SmartProjectionRigFactor: camera id outside the rig");
+  addSmartRows(x, sf, sf.nonUniqueKeys(), sp, sf.*SmartPoseAccess::noise(), keys, "SmartProjectionRigFactor");
+  x.sm_cal.push_back(nullptr); x.sm_sen.push_back(-1); x.sm_rig.push_back(sf.cameraRig().get());
+  for (size_t id : sf.cameraIds()) { x.sm_cid.push_back((int32_t)id); x.calibration(&(*sf.cameraRig())[id].calibration(), 0); }
 }
 // BetweenFactor<Pose3>, and <Pose2> in the same table: the factor's type follows from its variables', (x, y, theta) in the first 3 of the 12 doubles
 template <class T> void addBetween(Extract& x, const BetweenFactor<T>& b, const std::vector<Key>& keys) {
@@ -486,6 +511,7 @@ void addFactor(Extract& x, const NonlinearFactor* f, const std::vector<Key>& key
   else if (auto bf = dynamic_cast<const SamBearingFactor*>(f)) addSam(x, GTG_SAM_BEARING, bf->keys()[0], bf->keys()[1], &bf->measured(), nullptr, bf->noiseModel(), keys);
   else if (auto sf = dynamic_cast<const SmartFactor*>(f)) addSmart(x, *sf, keys);
   else if (auto sp = dynamic_cast<const SmartPoseFactor*>(f)) addSmartPose(x, *sp, keys);
+  else if (auto sr = dynamic_cast<const SmartRigFactor*>(f)) addSmartRig(x, *sr, keys);
   else if (auto bb = dynamic_cast<const BetweenFactor<Pose3>*>(f)) addBetween(x, *bb, keys);
   else if (auto b2 = dynamic_cast<const BetweenFactor<Pose2>*>(f)) addBetween(x, *b2, keys);
   else if (auto q2 = dynamic_cast<const PriorFactor<Pose2>*>(f)) addPrior(x, *q2, keys);
@@ -494,7 +520,7 @@ void addFactor(Extract& x, const NonlinearFactor* f, const std::vector<Key>& key
   else if (auto p3 = dynamic_cast<const PriorFactor<Point3>*>(f)) addPrior(x, *p3, keys);
   else throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: factor type outside the GPU hot path "   // (anything else is a hard error)
                                    "(supported: GeneralSFMFactor<SfmCamera,Point3>, GenericProjectionFactor<Pose3,Point3,Cal3_S2|Cal3DS2>, "
-                                   "GenericStereoFactor<Pose3,Point3>, BearingRangeFactor|RangeFactor|BearingFactor<Pose3,Point3>, SmartProjectionFactor<SfmCamera>, SmartProjectionPoseFactor<Cal3_S2>, BetweenFactor<Pose3|Pose2>, PriorFactor<Pose3|Pose2|SfmCamera|Point3>)");
+                                   "GenericStereoFactor<Pose3,Point3>, BearingRangeFactor|RangeFactor|BearingFactor<Pose3,Point3>, SmartProjectionFactor<SfmCamera>, SmartProjectionPoseFactor<Cal3_S2>, SmartProjectionRigFactor<PinholePose<Cal3_S2>>, BetweenFactor<Pose3|Pose2>, PriorFactor<Pose3|Pose2|SfmCamera|Point3>)");
 }
 // The factors [b, e) of `graph` into x, each pointer also copied into `graphCopy`; the chunk stops at its first offending factor and keeps what that threw.
 void extractChunk(Extract& x, const NonlinearFactorGraph& graph, NonlinearFactorGraph& graphCopy, const std::vector<Key>& keys, size_t b, size_t e) {
@@ -528,10 +554,12 @@ struct HostProblem {
   NoiseTable nt;
   RawI sfm_cam, sfm_pt, sfm_nz;
   RawD sfm_z;
-  std::vector<int32_t> pj_pose, pj_pt, pj_nz, pj_cal, pj_sen, st_pose, st_pt, st_nz, st_cal, st_sen, sam_kind, sam_pose, sam_pt, sam_nz, bt_1, bt_2, bt_nz, pr_var, pr_nz, sm_cam, sm_nz, sm_cal, sm_sen;
-  std::vector<double> pj_z, st_z, sam_z, calib, sensor, bt_z, pr_data, sm_z, sm_prm;
+  std::vector<int32_t> pj_pose, pj_pt, pj_nz, pj_cal, pj_sen, st_pose, st_pt, st_nz, st_cal, st_sen, sam_kind, sam_pose, sam_pt, sam_nz, bt_1, bt_2, bt_nz, pr_var, pr_nz, sm_cam, sm_nz, sm_cal, sm_sen, sm_mcal, sm_msen;
+  std::vector<double> pj_z, st_z, sam_z, calib, sensor, rig_sensor, bt_z, pr_data, sm_z, sm_prm;   // (rig_sensor: the rigs' extrinsics, appended to `sensor` behind every chunk's rows)
   std::vector<int64_t> pr_off, sm_ptr{0};    // (smart factors: one track each)
   bool any_smart_pose = false;               // a SmartProjectionPoseFactor: the smart_calib / smart_sensor tables go to the library
+  bool any_smart_rig = false;                // a SmartProjectionRigFactor: sm_mcal / sm_msen (per smart measurement) go to the library too
+  std::map<std::pair<const void*, int32_t>, std::pair<int32_t, int32_t>> rig_rows;   // (rig object, camera id) -> (calib row, sensor row or -1)
   std::map<std::array<double, 12>, int32_t> shared_sensor;   // the body_P_sensor of smart factors -> row of the sensor table
   std::map<const void*, int32_t> calib_id;   // shared calibration objects (Cal3_S2 or Cal3DS2) -> row of the calibration table
   std::vector<double> calib_dist;            // k1 k2 p1 p2 per row (zero for a Cal3_S2)
@@ -547,6 +575,17 @@ struct HostProblem {
     else { pinhole(static_cast<const Cal3_S2*>(object)); calib_dist.insert(calib_dist.end(), {0.0, 0.0, 0.0, 0.0}); }
     calib_base.push_back(0.0);
     return it->second;
+  }
+  // the rows of camera `id` of a rig: its K like any shared calibration object, its extrinsic as a row of rig_sensor -- none (-1) for
+  // an identity pose, whose composition with the body pose returns the body pose's own numbers
+  std::pair<int32_t, int32_t> rigRows(const SmartRigFactor::Cameras* rig, int32_t id) {
+    auto it = rig_rows.find({rig, id});
+    if (it != rig_rows.end()) return it->second;
+    const PoseCamera& cam = (*rig)[(size_t)id];
+    const int32_t ci = calibRow(&cam.calibration(), 0);
+    int32_t si = -1;
+    if (!cam.pose().equals(Pose3(), 0.0)) { si = (int32_t)(rig_sensor.size() / 12); rig_sensor.resize(rig_sensor.size() + 12); packPose(cam.pose(), rig_sensor.data() + rig_sensor.size() - 12); }
+    return rig_rows.emplace(std::make_pair((const void*)rig, id), std::make_pair(ci, si)).first->second;
   }
   int32_t stereoCalibRow(const Cal3_S2Stereo* K) {
     auto it = calib_id.find(K);
@@ -575,6 +614,7 @@ struct HostProblem {
     pb.n_smart = (int64_t)sm_nz.size(); pb.smart_ptr = sm_ptr.data(); pb.smart_cam = sm_cam.data(); pb.smart_z = sm_z.data();
     pb.smart_noise = sm_nz.data(); pb.smart_params = sm_prm.data();
     pb.smart_calib = any_smart_pose ? sm_cal.data() : nullptr; pb.smart_sensor = any_smart_pose ? sm_sen.data() : nullptr;
+    pb.smart_meas_calib = any_smart_rig ? sm_mcal.data() : nullptr; pb.smart_meas_sensor = any_smart_rig ? sm_msen.data() : nullptr;
     pb.n_prior = (int64_t)pr_var.size(); pb.prior_var = pr_var.data(); pb.prior_off = pr_off.data(); pb.prior_data = pr_data.data(); pb.prior_noise = pr_nz.data();
     return pb;
   }
@@ -683,6 +723,7 @@ HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap
       sen_row[r] = (int32_t)(hp.sensor.size() / 12);
       hp.sensor.insert(hp.sensor.end(), sp, sp + 12);
     }
+    for (const auto& kc : x.cal_order) { if (kc.second == 2) hp.stereoCalibRow(static_cast<const Cal3_S2Stereo*>(kc.first)); else hp.calibRow(kc.first, kc.second); }
     place[pi].o_sfm = o_sfm_next; place[pi].o_pj = (int64_t)hp.pj_pose.size(); place[pi].o_st = (int64_t)hp.st_pose.size(); place[pi].o_sam = (int64_t)hp.sam_pose.size(); place[pi].o_bt = (int64_t)hp.bt_1.size();
     place[pi].o_pr = (int64_t)hp.pr_var.size(); place[pi].o_sm = (int64_t)hp.sm_nz.size();
     o_sfm_next += (int64_t)x.sfm_cam.size();
@@ -705,9 +746,21 @@ HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap
     cat(hp.sm_cam, x.sm_cam); cat(hp.sm_z, x.sm_z); cat(hp.sm_prm, x.sm_prm);
     for (size_t k = 1; k < x.sm_ptr.size(); k++) hp.sm_ptr.push_back(x.sm_ptr[k] + o_smc);
     rows(hp.sm_nz, x.sm_nz, nullptr);
-    for (const Cal3_S2* K : x.sm_cal) { hp.sm_cal.push_back(K ? hp.calibRow(K, 0) : -1); hp.any_smart_pose = hp.any_smart_pose || K; }
+    for (size_t f = 0; f < x.sm_cal.size(); f++) {
+      const Cal3_S2* K = x.sm_cal[f];
+      const SmartRigFactor::Cameras* rig = x.sm_rig[f];
+      hp.sm_cal.push_back(rig ? GTG_SMART_RIG : K ? hp.calibRow(K, 0) : -1);
+      hp.any_smart_pose = hp.any_smart_pose || K || rig; hp.any_smart_rig = hp.any_smart_rig || rig;
+      for (int64_t k = x.sm_ptr[f]; k < x.sm_ptr[f + 1]; k++) {      // the per-measurement rows: -1 at the measurements of other factors
+        const std::pair<int32_t, int32_t> rows = rig ? hp.rigRows(rig, x.sm_cid[(size_t)k]) : std::make_pair(-1, -1);
+        hp.sm_mcal.push_back(rows.first); hp.sm_msen.push_back(rows.second);
+      }
+    }
     for (int32_t sidx : x.sm_sen) hp.sm_sen.push_back(sidx < 0 ? -1 : sen_row[(size_t)sidx]);
   }
+  // the rigs' extrinsics behind the sensor rows of the other factors, whatever the number of chunks
+  for (int32_t& si : hp.sm_msen) if (si >= 0) si += (int32_t)(hp.sensor.size() / 12);
+  cat(hp.sensor, hp.rig_sensor);
   // the big tables, by threads, one chunk each, now that the offsets and the noise rows are handed out in graph order
   parallelRanges(part.size(), part.size(), [&](size_t pi, size_t, size_t) {
     const Extract& x = part[pi];

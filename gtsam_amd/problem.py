@@ -17,6 +17,7 @@ VAR_POSE3, VAR_SFM_CAMERA, VAR_POINT3, VAR_POSE2 = 0, 1, 2, 3
 FAC_GENERAL_SFM, FAC_PROJECTION, FAC_BETWEEN_POSE3, FAC_PRIOR, FAC_STEREO, FAC_SAM = 0, 1, 2, 3, 4, 5
 SAM_BEARING_RANGE, SAM_RANGE, SAM_BEARING = 0, 1, 2
 NOISE_UNIT, NOISE_ISOTROPIC, NOISE_DIAGONAL, NOISE_GAUSSIAN = 0, 1, 2, 3
+SMART_RIG = -2     # smart_calib of a SmartProjectionRigFactor (GTG_SMART_RIG): calib / sensor per measurement
 ROBUST_NONE, ROBUST_FAIR, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY, ROBUST_WELSCH, ROBUST_GEMANMCCLURE, ROBUST_DCS, ROBUST_L2WITHDEADZONE = range(9)
 
 STORAGE = {VAR_POSE3: 12, VAR_SFM_CAMERA: 17, VAR_POINT3: 3, VAR_POSE2: 3}    # Pose2 = (x, y, theta)
@@ -45,6 +46,7 @@ class gtg_problem(C.Structure):
         ("stereo_calib", _i32p), ("stereo_sensor", _i32p), ("calib_baseline", _f64p),
         ("smart_calib", _i32p), ("smart_sensor", _i32p),
         ("n_sam", C.c_int64), ("sam_kind", _i32p), ("sam_pose", _i32p), ("sam_point", _i32p), ("sam_z", _f64p), ("sam_noise", _i32p),
+        ("smart_meas_calib", _i32p), ("smart_meas_sensor", _i32p),
     ]
 
 
@@ -84,6 +86,10 @@ class Problem:
     # empty = every factor is camera-type (the C ABI's NULL)
     smart_calib: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     smart_sensor: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    # SmartProjectionRigFactor<PinholePose<Cal3_S2>> (smart_calib SMART_RIG): per smart MEASUREMENT an entry of `calib` and of `sensor`
+    # (-1: no extrinsic), read for the measurements of rig-type factors only; empty = no rig-type factor (the C ABI's NULL)
+    smart_meas_calib: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    smart_meas_sensor: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     # GenericStereoFactor<Pose3, Point3>: measurement (uL, uR, v), calibration = an entry of `calib` plus its `calib_baseline`
     stereo_pose: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     stereo_point: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
@@ -124,6 +130,7 @@ class Problem:
                          ("stereo_pose", np.int32), ("stereo_point", np.int32), ("stereo_z", np.float64),
                          ("stereo_noise", np.int32), ("stereo_calib", np.int32), ("stereo_sensor", np.int32),
                          ("calib_baseline", np.float64), ("smart_calib", np.int32), ("smart_sensor", np.int32),
+                         ("smart_meas_calib", np.int32), ("smart_meas_sensor", np.int32),
                          ("sam_kind", np.int32), ("sam_pose", np.int32), ("sam_point", np.int32), ("sam_z", np.float64),
                          ("sam_noise", np.int32)):
             setattr(self, name, _a(getattr(self, name), dt))
@@ -235,6 +242,8 @@ class Problem:
                 raise ValueError("inconsistent smart factor tables (smart_calib / smart_sensor hold one entry per smart factor, or none)")
             if self.smart_sensor.size and not self.smart_calib.size:
                 raise ValueError("smart_sensor without smart_calib: only pose-type smart factors have a body_P_sensor")
+            if self.smart_meas_calib.size not in (0, self.smart_cam.size) or self.smart_meas_sensor.size != self.smart_meas_calib.size:
+                raise ValueError("inconsistent smart factor tables (smart_meas_calib / smart_meas_sensor hold one entry per smart measurement, or none)")
         p.smart_ptr = ptr(np.ascontiguousarray(self.smart_ptr, np.int64), C.c_int64) if self.n_smart else C.cast(None, C.POINTER(C.c_int64))
         p.smart_cam = ptr(self.smart_cam, C.c_int32)
         p.smart_z = ptr(self.smart_z, C.c_double)
@@ -242,6 +251,8 @@ class Problem:
         p.smart_params = ptr(self.smart_params, C.c_double)
         p.smart_calib = ptr(self.smart_calib, C.c_int32)
         p.smart_sensor = ptr(self.smart_sensor, C.c_int32)
+        p.smart_meas_calib = ptr(self.smart_meas_calib, C.c_int32)
+        p.smart_meas_sensor = ptr(self.smart_meas_sensor, C.c_int32)
         p.n_stereo = self.n_stereo
         if self.n_stereo:
             if self.stereo_sensor.size == 0:
@@ -270,10 +281,12 @@ class Problem:
     # ---- smart factors -----------------------------------------------------------------------
     def add_smart(self, cams, zs, noise_idx: int, rank_tolerance=1.0, landmark_distance_threshold=-1.0,
                   dynamic_outlier_rejection_threshold=-1.0, retriangulation_threshold=1e-5, degeneracy_mode=0,
-                  linearization_mode=0, enable_epi=False, calib=-1, sensor=-1):
+                  linearization_mode=0, enable_epi=False, calib=-1, sensor=-1, meas_calib=None, meas_sensor=None):
         """One SmartProjectionFactor<PinholeCamera<Cal3Bundler>>: camera variable ids + their pixel measurements -- or, with calib >= 0
         (an entry of the calib table; sensor: an entry of the sensor table or -1), one SmartProjectionPoseFactor<Cal3_S2>: POSE3
-        variable ids + their pixel measurements; defaults =
+        variable ids + their pixel measurements -- or, with meas_calib (an entry of the calib table per measurement; meas_sensor: an entry
+        of the sensor table or -1 per measurement, default all -1), one SmartProjectionRigFactor<PinholePose<Cal3_S2>>: the NON-unique
+        POSE3 ids in measurement order, smart_calib = SMART_RIG; defaults =
         SmartProjectionParams() / TriangulationParameters() (slam/SmartFactorParams.h:58-66, geometry/triangulation.h:583-600).
         degeneracy_mode 0 IGNORE_DEGENERACY, 1 ZERO_ON_DEGENERACY, 2 HANDLE_INFINITY; linearization_mode 0 HESSIAN, 2 JACOBIAN_Q,
         3 JACOBIAN_SVD (1 = IMPLICIT_SCHUR cannot be eliminated by the reference's direct solvers and is refused); enable_epi =
@@ -281,13 +294,29 @@ class Problem:
         cams = _a(cams, np.int32); zs = _a(zs, np.float64)
         if zs.size != 2 * cams.size or cams.size < 1:
             raise ValueError("a smart factor needs one 2-vector per camera")
+        rig = meas_calib is not None
+        if meas_sensor is not None and not rig:
+            raise ValueError("meas_sensor without meas_calib: a rig-type smart factor names a calibration per measurement")
+        if rig:
+            if calib != -1 or sensor != -1:
+                raise ValueError("a rig-type smart factor has no calib / sensor of its own (meas_calib / meas_sensor per measurement)")
+            mc = _a(meas_calib, np.int32)
+            ms = np.full(cams.size, -1, np.int32) if meas_sensor is None else _a(meas_sensor, np.int32)
+            if mc.size != cams.size or ms.size != cams.size:
+                raise ValueError("a rig-type smart factor needs one calib and one sensor entry per measurement")
+            calib = SMART_RIG
         self.smart_cam = np.concatenate([self.smart_cam, cams]); self.smart_z = np.concatenate([self.smart_z, zs])
         self.smart_ptr = np.concatenate([np.asarray(self.smart_ptr, np.int64), [int(self.smart_ptr[-1]) + cams.size]]).astype(np.int64)
         self.smart_noise = np.concatenate([self.smart_noise, np.array([noise_idx], np.int32)])
         self.smart_params = np.concatenate([self.smart_params, [rank_tolerance, landmark_distance_threshold,
                                                                 dynamic_outlier_rejection_threshold, retriangulation_threshold,
                                                                 float(degeneracy_mode), float(linearization_mode), 1.0 if enable_epi else 0.0, 0.0]])
-        if calib >= 0 or sensor >= 0 or self.smart_calib.size:      # the two tables exist once a pose-type factor does
+        if rig or self.smart_meas_calib.size:                        # the two tables exist once a rig-type factor does
+            n = self.smart_cam.size - cams.size
+            padm = lambda a: np.concatenate([a, np.full(n - a.size, -1, np.int32)])
+            self.smart_meas_calib = np.concatenate([padm(self.smart_meas_calib), mc if rig else np.full(cams.size, -1, np.int32)])
+            self.smart_meas_sensor = np.concatenate([padm(self.smart_meas_sensor), ms if rig else np.full(cams.size, -1, np.int32)])
+        if rig or calib >= 0 or sensor >= 0 or self.smart_calib.size:      # the two tables exist once a pose-type factor does
             n = self.smart_noise.size - 1
             pad = lambda a: np.concatenate([a, np.full(n - a.size, -1, np.int32)])
             self.smart_calib = np.append(pad(self.smart_calib), np.int32(calib))

@@ -133,14 +133,15 @@ typedef struct gtg_problem {
                                      against the older struct must be recompiled.) */
 
   /* SmartProjectionFactor<PinholeCamera<Cal3Bundler>> (slam/SmartProjectionFactor.h, the factor of timing/timeSFMBALsmart.cpp), or --
-   * with smart_calib at the end of this struct -- SmartProjectionPoseFactor<Cal3_S2>:
+   * with smart_calib at the end of this struct -- SmartProjectionPoseFactor<Cal3_S2> or SmartProjectionRigFactor<PinholePose<Cal3_S2>>:
    * one factor = one track; its landmark is NOT a variable but re-triangulated from the cameras at every linearisation / error
    * evaluation (DLT, geometry/triangulation.cpp:27-57, checks of triangulateSafe triangulation.h:697-752, cached while no camera
    * pose moves by more than retriangulationThreshold, SmartProjectionFactor.h:127-183) and eliminated without damping (the Schur
    * complement of the point, :190-233; JacobianFactorQ / JacobianFactorSVD are the same normal equations).  NULL / 0: no smart factors. */
   int64_t n_smart;
   const int64_t* smart_ptr;       /* [n_smart+1] offsets of a factor's measurements in smart_cam / smart_z (>= 1 measurement each) */
-  const int32_t* smart_cam;       /* variable id (SFM_CAMERA; POSE3 for a pose-type factor) of every measurement */
+  const int32_t* smart_cam;       /* variable id (SFM_CAMERA; POSE3 for a pose-type or rig-type factor, where a rig-type factor may
+                                     name a pose several times) of every measurement */
   const double* smart_z;          /* 2 per measurement */
   const int32_t* smart_noise;     /* [n_smart] index into the noise table (dim 2, Unit or Isotropic as the reference requires) */
   const double* smart_params;     /* [n_smart*8] rankTolerance, landmarkDistanceThreshold, dynamicOutlierRejectionThreshold,
@@ -175,7 +176,8 @@ typedef struct gtg_problem {
    * Refused by gtg_upload_problem (out of scope, not computed as something else): camera-type and pose-type smart factors in one
    * graph; pose-type smart factors beside GenericStereoFactors; a calib entry with Cal3DS2 distortion; enableEPI on a pose-type factor.
    * (Appended after the stereo tables: a caller built against the older struct must be recompiled.) */
-  const int32_t* smart_calib;     /* [n_smart] index into the calib table, or -1 for a camera-type smart factor; NULL: all -1 */
+  const int32_t* smart_calib;     /* [n_smart] index into the calib table, -1 for a camera-type smart factor, or GTG_SMART_RIG (-2,
+                                     the tables at the end of this struct) for a rig-type one; NULL: all -1 */
   const int32_t* smart_sensor;    /* [n_smart] index into the sensor table or -1 (no body_P_sensor); NULL: none */
 
   /* GTG_FAC_SAM: BearingRangeFactor<Pose3, Point3>, RangeFactor<Pose3, Point3> and BearingFactor<Pose3, Point3> (gtsam/sam), the
@@ -190,7 +192,25 @@ typedef struct gtg_problem {
   const double* sam_z;            /* [n_sam*4] the measured Unit3's three stored doubles (a unit vector, as the reference holds it),
                                      then the measured range; the entries a kind does not use are 0 */
   const int32_t* sam_noise;       /* [n_sam] index into the noise table (dim 3, 1 or 2 by kind) */
+
+  /* SmartProjectionRigFactor<PinholePose<Cal3_S2>> (slam/SmartProjectionRigFactor.h: stereo, surround and multi-camera front ends): a
+   * smart factor whose keys are the BODY poses and whose measurements each look through one camera of a fixed rig.  Factor i is
+   * rig-type when smart_calib[i] == GTG_SMART_RIG: measurement k (an index into smart_cam / smart_z) then uses calib row
+   * smart_meas_calib[k] and sensor row smart_meas_sensor[k] (-1: no extrinsic), its camera is PinholePose<Cal3_S2>(pose * body_P_sensor,
+   * K) (:209-222).  smart_cam holds the NON-unique POSE3 ids in measurement order: the same pose may occur several times in one track
+   * (two cameras of the rig seeing the landmark from one body pose), and the factor's Hessian is the reference's, on the unique keys
+   * (:312-322).  The entries of both tables at the measurements of other factors are not read.  Both NULL and no GTG_SMART_RIG entry:
+   * no rig-type factors.  Rig-type and pose-type factors may share a graph.
+   * Refused by gtg_upload_problem: smart_params other than degeneracyMode 1 (ZERO_ON_DEGENERACY) and linearizationMode 0 (HESSIAN) on a
+   * rig-type factor (the reference's constructor throws, :100-107); enableEPI on it; a named calib row with Cal3DS2 distortion;
+   * smart_sensor[i] != -1 on it; a GTG_SMART_RIG entry with either table NULL; indices out of range; keys that are not POSE3; and what is
+   * refused for pose-type factors (camera-type factors, stereo or bearing / range factors in the same graph).
+   * (Appended after the bearing / range tables: a caller built against the older struct must be recompiled.) */
+  const int32_t* smart_meas_calib;   /* [smart_ptr[n_smart]] index into the calib table, read for the measurements of rig-type factors */
+  const int32_t* smart_meas_sensor;  /* [smart_ptr[n_smart]] index into the sensor table or -1, read for the same measurements */
 } gtg_problem;
+/* smart_calib[i] of a rig-type smart factor */
+enum { GTG_SMART_RIG = -2 };
 
 /* ---- lifetime -------------------------------------------------------------------------------- */
 int gtg_create(gtg_handle* out, int device_id);
@@ -324,6 +344,10 @@ double gtg_cholesky_flops_executed(gtg_handle h);
  * reports the same value; gtg_upload_problem verifies that through the all-reduce callback and fails if they differ. */
 int64_t gtg_structure_hash(gtg_handle h);
 double gtg_linearize_bytes(gtg_handle h);
+/* 1 when some rig-type smart factor of the uploaded graph names a pose key more than once (the kernels that complete the Hessian
+ * diagonal and the block-Jacobi blocks on the unique keys are launched for such graphs only), 0 when none does, -1 without a problem.
+ * Derived from the WHOLE graph: every shard reports the same value. */
+int gtg_smart_repeated_keys(gtg_handle h);
 
 /* standalone kernels exposed for unit parity tests (tests/ only): dense FP64 Cholesky of an
  * n x n row-major SPD matrix (lower triangle) held in host memory; returns GTG_INDETERMINATE on a
