@@ -9,23 +9,21 @@
 #include <algorithm>
 #include <atomic>
 #include <exception>
-#include <functional>
 #include <cmath>
 #include <cstring>
 #include <limits>
 #include <memory>
 #include <mutex>
 #include <new>
-#include <set>
 #include <string>
 #include <stdexcept>
-#include <cstring>
 #include <sys/mman.h>
 #include <thread>
 
 #include "analysis.h"
 #include "factors.h"
 #include "kernels.h"
+#include "ordering.h"
 
 namespace gt {
 
@@ -372,22 +370,19 @@ void analyze(gtg_context& c) {
     for (size_t i = 0; i < hoff_row.size(); i++) f(hoff_row[i], hoff_col[i]);
   };
 
-  // ---- fill-reducing ordering of the reduced variables (reverse Cuthill-McKee on the block graph) -------------
-  // The reference gets its elimination order from COLAMD (inference/Ordering.cpp:42-124) unless the user passes
-  // one; here the order only decides where each camera/pose block sits in S.  A banded / loop-closing block
-  // pattern then leaves most 128x128 tiles of the factor empty, and the tile schedule skips them.
-  // ---- ordering of the reduced variables + Cholesky schedule.  RCM gives ONE serial chain of diagonal tiles; nested dissection
+  // ---- ordering of the reduced variables (ordering.h, device_ordering.hip) + Cholesky schedule.  RCM gives ONE serial chain of diagonal tiles; nested dissection
   // (GTG_ND_DEPTH=n levels; default: 2 levels where the criterion below holds, 0 switches it off) gives the elimination tree independent
   // subtrees, which the dataflow kernels run as several chains side by side (chol_dataflow.hip::build_df_plan) -- the reference's
   // parallel elimination of independent cliques (inference/ClusterTree-inst.h:218-317).  It pays in the latency-bound regime only:
   // the separators cost fill (L1723 shape: +60 % flops for a 30 % shorter chain), so it is TRIED where the block structure is very
   // sparse (pose graphs: < 1 % of the reduced system's entries) and KEPT where the longest chain gets >= 30 % shorter. ----
   const char* nd_env = std::getenv("GTG_ND_DEPTH");
-  const bool nd_forced = nd_env != nullptr;
+  const char* ord_env = std::getenv("GTG_ORDERING");   // an explicitly requested ordering method (rcm, mindegree, auto; natural = the caller's order) is one chain
+  const struct { bool nd_forced; int nd_depth; bool method_given; std::string method; bool on_host; } req =   // the environment's request, read once
+      {nd_env != nullptr, nd_env ? std::atoi(nd_env) : 0, ord_env != nullptr, ord_env ? ord_env : "", std::getenv("GTG_HOST_ORDERING") != nullptr};
+  const bool nd_forced = req.nd_forced, keep_order = req.method == "natural";
   int nd_auto = 0;
-  const char* ord_req = std::getenv("GTG_ORDERING");   // an explicitly requested ordering method (rcm, mindegree, auto; natural = the caller's order) is one chain
-  const bool keep_order = ord_req && std::string(ord_req) == "natural";
-  if (!nd_forced && hi.user_order.empty() && c.n_red >= 24 * (int64_t)kTile && !ord_req) {
+  if (!nd_forced && hi.user_order.empty() && c.n_red >= 24 * (int64_t)kTile && !req.method_given) {
     double nnz = 0.0;
     for_each_block([&](int ra, int rb) { if (ra != rb) nnz += 2.0 * c.h_red_dim[ra] * c.h_red_dim[rb]; });
     // 16 leaves on 8 chain slots (round 4, with the accumulator lanes of chol_dataflow.hip): sphere2500 1.07 ms, w20000 2.70 ms
@@ -397,241 +392,50 @@ void analyze(gtg_context& c) {
   join_block_level(c);      // the flop count of a previous analysis of this handle (below) may still be running
   for (int attempt = 0; attempt < 2; attempt++) {
   join_block_level(c);
-  const int nd_depth_try = attempt == 0 ? (nd_env ? std::atoi(nd_env) : nd_auto) : 0;
+  const int nd_depth = attempt == 0 ? (nd_forced ? req.nd_depth : nd_auto) : 0;
   // (no nested dissection = one chain = two chain workgroups: that plan's masked stream pair can be on its way before the ordering)
-  if (nd_depth_try == 0 && kernels_can_run && dataflow_schedule_selected()) df_prepare_streams_async(c.device, 2);
+  if (nd_depth == 0 && kernels_can_run && dataflow_schedule_selected()) df_prepare_streams_async(c.device, 2);
   bool retry_rcm = false;
   std::vector<int32_t> part_of_pos;          // nested-dissection part of every position (empty: one part)
   std::vector<int32_t> part_parent;          // parent part (-1: root) of every part, parts numbered in elimination order
   if (hi.user_order.empty() && c.n_red_vars >= 16 && !keep_order) {
-    const int nrv2 = c.n_red_vars;
-    std::vector<std::vector<int32_t>> adj(nrv2);
-    bool have_adj = false;
-    auto ensure_adj = [&] {   // the host's adjacency lists (sorted, unique): not built when the ordering runs on the device
-      if (have_adj) return;
-      auto edge = [&](int a, int b) { if (a != b) { adj[a].push_back(b); adj[b].push_back(a); } };
-      for_each_block(edge);
-      for (auto& a : adj) { std::sort(a.begin(), a.end()); a.erase(std::unique(a.begin(), a.end()), a.end()); }
-      have_adj = true;
-    };
-    std::vector<int32_t> level(nrv2, -1);
-    std::vector<char> active(nrv2, 0);     // node belongs to the subgraph being processed and is not ordered yet
-    auto bfs_levels = [&](int start, std::vector<int32_t>& q) {   // BFS over active nodes, fills level[], returns order
-      q.assign(1, start);
-      for (int32_t v = 0; v < nrv2; v++) level[v] = -1;
-      level[start] = 0;
-      for (size_t h = 0; h < q.size(); h++)
-        for (int32_t w : adj[q[h]]) if (active[w] && level[w] < 0) { level[w] = level[q[h]] + 1; q.push_back(w); }
-    };
-    auto far_node = [&](int start) {
-      std::vector<int32_t> q; bfs_levels(start, q);
-      int best = q.back();
-      for (int32_t v : q) if (level[v] == level[q.back()] && adj[v].size() < adj[best].size()) best = v;
-      return best;
-    };
-    // reverse Cuthill-McKee of a node set (all its components)
-    auto rcm = [&](const std::vector<int32_t>& nodes, std::vector<int32_t>& out) {
-      for (int32_t v : nodes) active[v] = 1;
-      std::vector<int32_t> ord; ord.reserve(nodes.size());
-      for (int32_t seed : nodes) {
-        if (!active[seed]) continue;
-        const int start = far_node(far_node(seed));   // two sweeps towards a pseudo-peripheral node of the component
-        std::vector<int32_t> q{start}; active[start] = 0;
-        for (size_t h = 0; h < q.size(); h++) {
-          std::vector<int32_t> nb;
-          for (int32_t w : adj[q[h]]) if (active[w]) { active[w] = 0; nb.push_back(w); }
-          std::sort(nb.begin(), nb.end(), [&](int32_t a, int32_t b) { return adj[a].size() < adj[b].size() || (adj[a].size() == adj[b].size() && a < b); });
-          q.insert(q.end(), nb.begin(), nb.end());
-        }
-        ord.insert(ord.end(), q.begin(), q.end());
-      }
-      std::reverse(ord.begin(), ord.end());
-      out.insert(out.end(), ord.begin(), ord.end());
-    };
-    // Nested dissection by level-set separators: the elimination tree gets independent subtrees, i.e. the tile
-    // Cholesky gets several serial chains that run side by side instead of one (cholesky.hip).  A separator is the
-    // smallest BFS level (from a pseudo-peripheral node) that leaves at least a quarter of the nodes on each side.
-    struct PartRec { std::vector<int32_t> nodes; int parent; };
-    std::vector<PartRec> parts;
-    std::function<int(const std::vector<int32_t>&, int)> dissect = [&](const std::vector<int32_t>& nodes, int depth) -> int {
-      // returns the index of the part that roots this subtree (its last part in elimination order)
-      if (depth > 0 && nodes.size() >= 256) {
-        for (int32_t v : nodes) active[v] = 1;
-        std::vector<int32_t> q;
-        const int start = far_node(far_node(nodes[0]));
-        bfs_levels(start, q);
-        const int L = level[q.back()];
-        std::vector<int64_t> cnt(L + 2, 0);
-        for (int32_t v : q) cnt[level[v]]++;
-        const int64_t n = (int64_t)nodes.size();
-        int best = -1; int64_t below = 0;
-        std::vector<int64_t> pre(L + 2, 0);
-        for (int l = 0; l <= L; l++) pre[l + 1] = pre[l] + cnt[l];
-        // balance first (the parts become chains of diagonal tiles that run side by side: the longest one is the critical path), then
-        // the smallest separator among the balanced cuts; a cut that leaves a quarter on each side is the fallback
-        for (int64_t share : {10, 8, 5})
-          if (best < 0)
-            for (int l = 1; l < L; l++) {
-              below = pre[l];
-              const int64_t above = n - pre[l + 1];   // nodes not reached by the BFS count as "above"
-              if (std::min(below, above) * 20 < n * share) continue;
-              if (best < 0 || cnt[l] < cnt[best]) best = l;
-            }
-        for (int32_t v : nodes) active[v] = 0;
-        if (best > 0 && cnt[best] * 3 < n) {
-          std::vector<int32_t> A, Bn, Sn;
-          for (int32_t v : nodes) {
-            if (level[v] >= 0 && level[v] < best) A.push_back(v);
-            else if (level[v] == best) Sn.push_back(v);
-            else Bn.push_back(v);
-          }
-          const int ra = dissect(A, depth - 1);
-          const int rb = dissect(Bn, depth - 1);
-          PartRec sp; sp.parent = -1;
-          rcm(Sn, sp.nodes);
-          parts.push_back(std::move(sp));
-          const int me = (int)parts.size() - 1;
-          parts[ra].parent = me; parts[rb].parent = me;
-          return me;
-        }
-      }
-      PartRec leaf; leaf.parent = -1;
-      rcm(nodes, leaf.nodes);
-      parts.push_back(std::move(leaf));
-      return (int)parts.size() - 1;
-    };
-    const int nd_depth = nd_depth_try;
-    std::vector<int32_t> all(nrv2);
-    for (int i = 0; i < nrv2; i++) all[i] = i;
+    std::vector<int32_t> ea, eb;   // the off-diagonal blocks as an edge list: not built where the device orders its own block list
+    auto edge_list = [&] { if (ea.empty()) for_each_block([&](int a, int b) { if (a != b) { ea.push_back(a); eb.push_back(b); } }); };
     // One part (no nested dissection) on a single shard with a real runtime: reverse Cuthill-McKee runs on the DEVICE
     // (device_ordering.hip: the same ordering position for position; GTG_HOST_ORDERING=1 keeps the host queue as the A/B).
-    bool ordered_on_device = false;
-    {
-      const bool plain_rcm = !ord_req || std::string(ord_req) == "rcm";
-      if (nd_depth == 0 && plain_rcm && kernels_can_run && c.n_shards == 1 && !std::getenv("GTG_HOST_ORDERING")) {
-        StageClock sub;
-        std::vector<int32_t> ea, eb;
-        const bool edges_on_device = device_terms && hoff_row.empty();    // the device's own block list is the edge list
-        if (!edges_on_device) { for_each_block([&](int a, int b) { if (a != b) { ea.push_back(a); eb.push_back(b); } }); sub.lap("  (ordering: edge list, host)"); }
-        PartRec leaf; leaf.parent = -1;
-        if (device_rcm(c, nrv2, ea, eb, leaf.nodes, edges_on_device ? c.pair_row.p : nullptr, edges_on_device ? c.pair_col.p : nullptr, (int64_t)pair_row.size())) {
-          parts.push_back(std::move(leaf)); ordered_on_device = true;
-        }
-        sub.lap("  (ordering: device RCM)");
-      }
+    std::vector<OrderingPart> tree;            // the parts in elimination order
+    if (nd_depth == 0 && (!req.method_given || req.method == "rcm") && kernels_can_run && c.n_shards == 1 && !req.on_host) {
+      StageClock sub;
+      const bool edges_on_device = device_terms && hoff_row.empty();    // the device's own block list is the edge list
+      if (!edges_on_device) { edge_list(); sub.lap("  (ordering: edge list, host)"); }
+      OrderingPart leaf;
+      if (device_rcm(c, nrv, ea, eb, leaf.nodes, edges_on_device ? c.pair_row.p : nullptr, edges_on_device ? c.pair_col.p : nullptr, (int64_t)pair_row.size()))
+        tree.push_back(std::move(leaf));
+      sub.lap("  (ordering: device RCM)");
     }
-    if (!ordered_on_device) { ensure_adj(); dissect(all, nd_depth); }
+    const bool ordered_on_device = !tree.empty();
+    BlockGraph graph;                          // the host's adjacency lists: not built when the ordering ran on the device
+    if (!ordered_on_device) { edge_list(); graph = BlockGraph(nrv, ea, eb); tree = nested_dissection(graph, nd_depth); }
     if (clk.on) std::fprintf(stderr, "[gtsam_amd setup] ordering computed on the %s\n", ordered_on_device ? "device" : "host");
-    std::vector<int32_t> order; order.reserve(nrv2);
-    for (size_t pi = 0; pi < parts.size(); pi++) {
-      for (int32_t v : parts[pi].nodes) { order.push_back(v); part_of_pos.push_back((int32_t)pi); }
-      part_parent.push_back(parts[pi].parent);
-    }
-    if (parts.size() == 1) { part_of_pos.clear(); part_parent.clear(); }
+    PartOrder po = flatten_parts(tree);
+    part_of_pos = std::move(po.part_of_pos); part_parent = std::move(po.part_parent);
     // ---- minimum-degree alternative (GTG_ORDERING=mindegree | auto; default rcm).  The reference orders with COLAMD
     // (inference/Ordering.cpp:42-124), a minimum-degree method; on a reduced camera system it competes with the band ordering
-    // above.  Both are scored by the block-level flops of the symbolic factorisation; "auto" keeps the cheaper one.  Measured on
+    // above.  "auto" keeps the one that is cheaper over the tiles it would store (ordering.h::tile_level_flops).  Measured on
     // the L1723 shape (cameras on a closed path: a cyclic band): RCM 136 GFLOP, minimum degree 145 GFLOP, natural order 782 --
     // the band wins there and its tiles are dense, so RCM stays the default and the 0.2 s of this search are opt-in.
-    const std::string ord_mode = ord_req ? ord_req : "rcm";
-    if (parts.size() == 1 && (ord_mode == "mindegree" || ord_mode == "auto")) {
-      ensure_adj();
-      auto block_flops = [&](const std::vector<int32_t>& ord) {
-        std::vector<int32_t> pos(nrv2);
-        for (int i = 0; i < nrv2; i++) pos[ord[i]] = i;
-        std::vector<std::vector<int32_t>> below(nrv2), kids(nrv2);
-        for (int v = 0; v < nrv2; v++) for (int32_t w : adj[v]) if (pos[w] > pos[v]) below[pos[v]].push_back(pos[w]);
-        std::vector<int32_t> merged;
-        double fl = 0.0;
-        for (int j = 0; j < nrv2; j++) {
-          auto& sj = below[j];
-          std::sort(sj.begin(), sj.end()); sj.erase(std::unique(sj.begin(), sj.end()), sj.end());
-          for (int32_t ch : kids[j]) {
-            merged.clear();
-            std::set_union(sj.begin(), sj.end(), below[ch].begin(), below[ch].end(), std::back_inserter(merged));
-            merged.erase(std::remove(merged.begin(), merged.end(), (int32_t)j), merged.end());
-            sj.swap(merged); std::vector<int32_t>().swap(below[ch]);
-          }
-          double sdim = 0.0;
-          for (int32_t q : sj) sdim += c.h_red_dim[ord[q]];
-          const double f = c.h_red_dim[ord[j]];
-          fl += f * f * f / 3.0 + f * f * sdim + f * sdim * sdim;
-          if (!sj.empty()) kids[sj.front()].push_back(j);
-        }
-        return fl;
-      };
-      auto min_degree = [&]() {   // plain minimum degree on the elimination graph (ties: lowest index): what COLAMD approximates
-        std::vector<std::set<int32_t>> g(nrv2);
-        for (int v = 0; v < nrv2; v++) g[v].insert(adj[v].begin(), adj[v].end());
-        std::set<std::pair<int32_t, int32_t>> heap;
-        for (int v = 0; v < nrv2; v++) heap.emplace((int32_t)g[v].size(), v);
-        std::vector<int32_t> ord; ord.reserve(nrv2);
-        while (!heap.empty()) {
-          const int v = heap.begin()->second; heap.erase(heap.begin());
-          ord.push_back(v);
-          const std::vector<int32_t> nb(g[v].begin(), g[v].end());
-          for (int32_t w : nb) { heap.erase({(int32_t)g[w].size(), w}); g[w].erase(v); }
-          for (int32_t w : nb) for (int32_t u : nb) if (u != w) g[w].insert(u);
-          for (int32_t w : nb) heap.emplace((int32_t)g[w].size(), w);
-          std::set<int32_t>().swap(g[v]);
-        }
-        return ord;
-      };
-      // What the kernels execute is decided at TILE granularity: whole 128 x 128 tiles, fill included.  "auto" therefore scores the two
-      // orderings by the flops over the tiles they would store (the count of chol_dataflow.hip::build_df_plan), not by the block-level
-      // count: on the street-network shape (datasets.py::synthetic_bal_streets, random long-range loop closures) minimum degree needs
-      // FEWER flops at block level (42 against 57 GFLOP) and 12 x MORE at tile level (1 170 against 101: its fill is scattered, 96 % of
-      // the tiles are touched) -- the first version of "auto" compared block-level counts and picked it.
-      auto tile_flops = [&](const std::vector<int32_t>& ord) {
-        std::vector<int64_t> off(nrv2 + 1, 0);
-        std::vector<int32_t> pos(nrv2);
-        for (int i = 0; i < nrv2; i++) { pos[ord[i]] = i; off[i + 1] = off[i] + c.h_red_dim[ord[i]]; }
-        const int ntl = (int)((off[nrv2] + kTile - 1) / kTile);
-        std::vector<uint8_t> Bt((size_t)ntl * ntl, 0);
-        auto mark = [&](int pa, int pb) {
-          for (int64_t a = off[pa] / kTile; a <= (off[pa + 1] - 1) / kTile; a++)
-            for (int64_t b = off[pb] / kTile; b <= (off[pb + 1] - 1) / kTile; b++) Bt[(size_t)std::max(a, b) * ntl + std::min(a, b)] = 1;
-        };
-        for (int v = 0; v < nrv2; v++) { mark(pos[v], pos[v]); for (int32_t w : adj[v]) if (pos[w] < pos[v]) mark(pos[v], pos[w]); }
-        for (int k = 0; k < ntl; k++) {
-          std::vector<int> r;
-          for (int i = k + 1; i < ntl; i++) if (Bt[(size_t)i * ntl + k]) r.push_back(i);
-          for (size_t a = 0; a < r.size(); a++) for (size_t b = 0; b <= a; b++) Bt[(size_t)r[a] * ntl + r[b]] = 1;
-        }
-        const double t3 = (double)kTile * kTile * kTile;
-        double fl = 0.0;
-        std::vector<int> cnt(ntl, 0);
-        for (int i = 0; i < ntl; i++) for (int k = 0; k < i; k++) cnt[i] += Bt[(size_t)i * ntl + k];
-        for (int J = 0; J < ntl; J++) {
-          fl += t3 / 3.0 + cnt[J] * t3;
-          for (int I = J + 1; I < ntl; I++) {
-            if (!Bt[(size_t)I * ntl + J]) continue;
-            int both = 0;
-            for (int k = 0; k < J; k++) both += Bt[(size_t)I * ntl + k] & Bt[(size_t)J * ntl + k];
-            fl += t3 + 2.0 * both * t3;
-          }
-        }
-        return fl;
-      };
-      const std::vector<int32_t> md = min_degree();
-      const double f_rcm = block_flops(order), f_md = block_flops(md);
-      const double t_rcm = tile_flops(order), t_md = tile_flops(md);
+    if (!ordered_on_device && tree.size() == 1 && (req.method == "mindegree" || req.method == "auto")) {
+      const std::vector<int32_t> md = min_degree_order(graph);
+      const double f_rcm = block_level_flops(ea, eb, po.order, c.h_red_dim), f_md = block_level_flops(ea, eb, md, c.h_red_dim);
+      const double t_rcm = tile_level_flops(graph, po.order, c.h_red_dim, kTile), t_md = tile_level_flops(graph, md, c.h_red_dim, kTile);
       if (clk.on) std::fprintf(stderr, "[gtsam_amd setup] ordering: GFLOP at block level rcm %.1f, minimum degree %.1f; over 128 x 128 tiles rcm %.1f, minimum degree %.1f (%s)\n",
-                               f_rcm / 1e9, f_md / 1e9, t_rcm / 1e9, t_md / 1e9, ord_mode.c_str());
-      if (ord_mode == "mindegree" || t_md < t_rcm) order = md;
+                               f_rcm / 1e9, f_md / 1e9, t_rcm / 1e9, t_md / 1e9, req.method.c_str());
+      if (req.method == "mindegree" || t_md < t_rcm) po.order = md;
     }
-    for (int i = 0; i < nrv2; i++) { c.h_red_pos[order[i]] = i; pos_to_red[i] = order[i]; }
+    for (int i = 0; i < nrv; i++) { c.h_red_pos[po.order[i]] = i; pos_to_red[i] = po.order[i]; }
     // offsets: every part starts on a 256-column pair boundary, so that a pair of block columns belongs to one part
-    int64_t o2 = 0;
-    c.h_pad_index.clear();
-    for (int pp = 0; pp < nrv2; pp++) {
-      if (!part_of_pos.empty() && (pp == 0 || part_of_pos[pp] != part_of_pos[pp - 1]))
-        while (o2 % (2 * kTile)) c.h_pad_index.push_back(o2++);
-      const int r = pos_to_red[pp]; c.h_red_off[r] = o2; o2 += c.h_red_dim[r];
-    }
-    const int64_t align = part_of_pos.empty() ? kTile : 2 * kTile;
-    while (o2 % align) c.h_pad_index.push_back(o2++);
-    c.NP = (int)o2;
+    Placement place = place_variables(po.order, part_of_pos, c.h_red_dim, kTile);
+    c.h_red_off = std::move(place.off); c.h_pad_index = std::move(place.pad); c.NP = (int)place.NP;
     // re-orient the blocks: the row variable is the one placed later
     // (device-built lists: c.pair_row / c.pair_col and the terms are re-oriented in place by one kernel; the host's copy of the block list
     // keeps the orientation it has -- every host pass that still reads it looks at the positions itself)
@@ -648,8 +452,8 @@ void analyze(gtg_context& c) {
         for (int64_t t = hoff_ptr[i]; t < hoff_ptr[i + 1]; t++) hoff_fac[t] ^= (1 << 30);
       }
     if (clk.on) {
-      std::fprintf(stderr, "[gtsam_amd setup] nested dissection: %zu parts:", parts.size());
-      for (size_t pi = 0; pi < parts.size(); pi++) std::fprintf(stderr, " %zu(^%d)", parts[pi].nodes.size(), parts[pi].parent);
+      std::fprintf(stderr, "[gtsam_amd setup] nested dissection: %zu parts:", tree.size());
+      for (const OrderingPart& part : tree) std::fprintf(stderr, " %zu(^%d)", part.nodes.size(), part.parent);
       std::fprintf(stderr, "\n");
     }
     clk.lap("ordering (nested dissection + RCM)");
@@ -666,44 +470,15 @@ void analyze(gtg_context& c) {
   // list and the ordering, and is joined by whoever needs it next: the getter, the next analysis of the handle, gtg_destroy (round 5:
   // analyze() used to wait 1.3 ms for it on the L1723 shape).
   {
-  // (its own copies of the block list: plain vector copies -- the loop that turns them into positions runs on the thread as well)
+  // (its own copies of the block list, the order and the dimensions: plain vector copies -- ordering.h::block_level_flops turns them into positions on the thread)
   std::vector<int32_t> bl_a, bl_b;                      // the off-diagonal blocks (reduced indices)
   if (c.n_shards > 1) { bl_a = sb_row; bl_b = sb_col; }
   else { bl_a = pair_row; bl_b = pair_col; bl_a.insert(bl_a.end(), hoff_row.begin(), hoff_row.end()); bl_b.insert(bl_b.end(), hoff_col.begin(), hoff_col.end()); }
-  std::vector<int32_t> dim_at_pos(c.n_red_vars);
-  for (int r = 0; r < c.n_red_vars; r++) dim_at_pos[c.h_red_pos[r]] = c.h_red_dim[r];
   gtg_context* cp = &c;
   c.block_level_err = nullptr;
   c.chol_flops_block = 0.0;      // (never the previous analysis's number while the new count runs)
-  c.block_level_thread = std::thread([cp, bl_a = std::move(bl_a), bl_b = std::move(bl_b), dim_at = std::move(dim_at_pos), red_pos = c.h_red_pos] { try {
-    const int n = (int)dim_at.size();
-    std::vector<std::vector<int32_t>> below(n);          // positions > own position
-    for (size_t i = 0; i < bl_a.size(); i++) {
-      if (bl_a[i] == bl_b[i]) continue;
-      const int pa = red_pos[bl_a[i]], pb = red_pos[bl_b[i]];
-      below[std::min(pa, pb)].push_back(std::max(pa, pb));
-    }
-    std::vector<std::vector<int32_t>> children(n);
-    std::vector<int32_t> merged;
-    double fl = 0.0;
-    for (int j = 0; j < n; j++) {
-      std::vector<int32_t>& sj = below[j];
-      std::sort(sj.begin(), sj.end()); sj.erase(std::unique(sj.begin(), sj.end()), sj.end());
-      for (int32_t ch : children[j]) {                   // struct(j) |= struct(child) \ {j}
-        merged.clear();
-        std::set_union(sj.begin(), sj.end(), below[ch].begin(), below[ch].end(), std::back_inserter(merged));
-        merged.erase(std::remove(merged.begin(), merged.end(), (int32_t)j), merged.end());
-        sj.swap(merged);
-        std::vector<int32_t>().swap(below[ch]);
-      }
-      double sdim = 0.0;
-      for (int32_t q : sj) sdim += dim_at[q];
-      const double f = dim_at[j];
-      fl += f * f * f / 3.0 + f * f * sdim + f * sdim * sdim;
-      if (!sj.empty()) children[sj.front()].push_back(j);
-    }
-    cp->chol_flops_block = fl;
-  } catch (...) { cp->block_level_err = std::current_exception(); } });
+  c.block_level_thread = std::thread([cp, bl_a = std::move(bl_a), bl_b = std::move(bl_b), order = pos_to_red, dims = c.h_red_dim] {
+    try { cp->chol_flops_block = block_level_flops(bl_a, bl_b, order, dims); } catch (...) { cp->block_level_err = std::current_exception(); } });
   }
 
   // ---- tile structure of the reduced system -> Cholesky schedule ------------------------------------------------
