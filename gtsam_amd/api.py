@@ -338,12 +338,36 @@ class SmartProjectionParams:
         self.degeneracyMode, self.retriangulationThreshold = degeneracyMode, retriangulationThreshold
         self.rankTolerance, self.landmarkDistanceThreshold, self.dynamicOutlierRejectionThreshold = 1.0, -1.0, -1.0
         self.enableEPI = False
+        # TriangulationParameters::useLOST / ::noiseModel (geometry/triangulation.h:571-579), flat as enableEPI is
+        self.useLOST, self.triangulationNoiseModel = False, None
 
     def setLinearizationMode(self, m): self.linearizationMode = m
     def setDegeneracyMode(self, m): self.degeneracyMode = m
     def setRetriangulationThreshold(self, t): self.retriangulationThreshold = t
     def setRankTolerance(self, t): self.rankTolerance = t
     def setEnableEPI(self, b): self.enableEPI = bool(b)
+    def setUseLOST(self, b): self.useLOST = bool(b)
+
+    def lostSigma(self):
+        """What triangulatePoint3 hands to triangulateLOST (triangulation.h:503): the mean of the model's sigmas, 1e-4 without one."""
+        m = self.triangulationNoiseModel
+        if m is None:
+            return 1e-4
+        if m.robust[0]:
+            raise RuntimeError("noiseModel::Base::sigmas: sigmas() not implemented")   # (Robust does not override it: the reference throws)
+        if m.kind == NOISE_UNIT:
+            s = np.ones(m.dim())
+        elif m.kind == NOISE_ISOTROPIC:
+            s = np.full(m.dim(), m.params[0])
+        elif m.kind == NOISE_DIAGONAL:
+            s = m.params
+        else:                                  # Gaussian::sigmas (NoiseModel.cpp:131-134): sqrt of the covariance's diagonal
+            R = m.params.reshape(m.dim(), m.dim())
+            s = np.sqrt(np.diag(np.linalg.inv(R.T @ R)))
+        total = 0.0
+        for x in s:
+            total += float(x)
+        return total / len(s)
     def setLandmarkDistanceThreshold(self, t): self.landmarkDistanceThreshold = t
     def setDynamicOutlierRejectionThreshold(self, t): self.dynamicOutlierRejectionThreshold = t
 
@@ -531,7 +555,8 @@ def extract(graph: NonlinearFactorGraph, values: Values):
         elif isinstance(f, SmartProjectionFactorPinholeCameraCal3Bundler):
             sp = f.params
             p.add_smart([vid(k) for k in f.keys_], np.concatenate(f.zs), nid(f.model, 2), sp.rankTolerance, sp.landmarkDistanceThreshold,
-                        sp.dynamicOutlierRejectionThreshold, sp.retriangulationThreshold, sp.degeneracyMode, sp.linearizationMode, sp.enableEPI)
+                        sp.dynamicOutlierRejectionThreshold, sp.retriangulationThreshold, sp.degeneracyMode, sp.linearizationMode, sp.enableEPI,
+                        use_lost=sp.useLOST, lost_sigma=sp.lostSigma() if sp.useLOST else 1e-4)
         elif isinstance(f, SmartProjectionPose3Factor):
             ck = f.K.v.tobytes()
             if ck not in calibs:
@@ -545,7 +570,7 @@ def extract(graph: NonlinearFactorGraph, values: Values):
             sp = f.params
             p.add_smart([vid(k) for k in f.keys_], np.concatenate(f.zs), nid(f.model, 2), sp.rankTolerance, sp.landmarkDistanceThreshold,
                         sp.dynamicOutlierRejectionThreshold, sp.retriangulationThreshold, sp.degeneracyMode, sp.linearizationMode, sp.enableEPI,
-                        calib=calibs[ck][0], sensor=si)
+                        calib=calibs[ck][0], sensor=si, use_lost=sp.useLOST, lost_sigma=sp.lostSigma() if sp.useLOST else 1e-4)
         elif isinstance(f, SmartProjectionRigFactorPinholePoseCal3_S2):
             mc, ms = [], []
             for cid in f.cameraIds_:
@@ -565,7 +590,7 @@ def extract(graph: NonlinearFactorGraph, values: Values):
             sp = f.params
             p.add_smart([vid(k) for k in f.nonUniqueKeys_], np.concatenate(f.zs), nid(f.model, 2), sp.rankTolerance, sp.landmarkDistanceThreshold,
                         sp.dynamicOutlierRejectionThreshold, sp.retriangulationThreshold, sp.degeneracyMode, sp.linearizationMode, sp.enableEPI,
-                        meas_calib=mc, meas_sensor=ms)
+                        meas_calib=mc, meas_sensor=ms, use_lost=sp.useLOST, lost_sigma=sp.lostSigma() if sp.useLOST else 1e-4)
             rig_factors.append(p.n_smart - 1)
         elif isinstance(f, BetweenFactorPose3):
             btw.append((vid(f.keys_[0]), vid(f.keys_[1]), f.z.packed(), nid(f.model, 6)))

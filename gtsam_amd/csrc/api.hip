@@ -628,6 +628,26 @@ double gtg_cholesky_flops_block_level(gtg_handle c) {
 }
 int64_t gtg_structure_hash(gtg_handle c) { return c ? (int64_t)(c->structure_hash & 0x7FFFFFFFFFFFFFFFull) : -1; }
 int gtg_smart_repeated_keys(gtg_handle c) { return c && c->uploaded ? (c->smart_repeats ? 1 : 0) : -1; }
+int64_t gtg_smart_lost_workspace(gtg_handle c) { return c && c->uploaded ? (int64_t)c->smart_lost_rows.n : -1; }
+
+// TriangulationResult of every smart factor as the last gtg_error / gtg_linearize left it (SmartProjectionFactor::point()): the status
+// word of that call and the hidden landmark's value slot, which the triangulation kernel wrote (zeros for a track without a point)
+int gtg_get_smart_triangulation(gtg_handle c, int32_t* status, double* points3, int64_t n_smart) {
+  GTG_TRY
+  if (!c || !c->uploaded || !status || !points3 || n_smart != c->n_smart) throw std::invalid_argument("gtg_get_smart_triangulation: wrong size or no problem uploaded");
+  if (!n_smart) return GTG_OK;
+  if (!c->smart_last_status) throw std::invalid_argument("gtg_get_smart_triangulation: call gtg_error or gtg_linearize first");
+  DeviceGuard on_device(c->device);
+  std::vector<int64_t> ptr((size_t)n_smart + 1);
+  check_hip(hipMemcpyAsync(status, c->smart_last_status, sizeof(int32_t) * n_smart, hipMemcpyDeviceToHost, c->stream), "D2H");
+  check_hip(hipMemcpyAsync(points3, c->values.p + c->user_val_size, sizeof(double) * 3 * n_smart, hipMemcpyDeviceToHost, c->stream), "D2H");
+  check_hip(hipMemcpyAsync(ptr.data(), c->smart_ptr.p, sizeof(int64_t) * (n_smart + 1), hipMemcpyDeviceToHost, c->stream), "D2H");
+  check_hip(hipStreamSynchronize(c->stream), "sync");
+  for (int64_t i = 0; i < n_smart; i++)
+    if (ptr[(size_t)i + 1] == ptr[(size_t)i]) { status[i] = -1; points3[3 * i] = points3[3 * i + 1] = points3[3 * i + 2] = 0.0; }   // a track of another shard
+  return GTG_OK;
+  GTG_CATCH
+}
 double gtg_linearize_bytes(gtg_handle c) { return c ? c->lin_bytes : 0.0; }
 
 // debug only (not in the public header): ms per K=256 trailing update over an m x m tile grid, with ablations

@@ -209,6 +209,11 @@ struct gtg_context {
   gt::DevBuf<int32_t> smart_cache_state;    // per factor: -1 nothing cached, else the cached status
   gt::DevBuf<double> smart_cache_pose;      // 12 per measurement: the camera poses of the cached triangulation
   gt::DevBuf<double> smart_cache_point;     // 3 per factor
+  // TriangulationParameters::useLOST (smart_params[8 i + 7] > 0 on some factor of the WHOLE graph): the LOST form of the triangulation
+  // kernel is launched, and smart_lost_rows holds its work space -- 8 doubles per smart measurement of this shard.  Empty otherwise.
+  bool smart_lost = false;
+  gt::DevBuf<double> smart_lost_rows;
+  const int32_t* smart_last_status = nullptr;   // smart_status or smart_lin_status: what the last gtg_error / gtg_linearize wrote (gtg_get_smart_triangulation)
   // SmartProjectionPoseFactor<Cal3_S2> (gtg_problem.smart_calib >= 0): the measurements are PROJECTION observations smart_obs0 .. of
   // the proj tables instead (keys POSE3, one shared Cal3_S2, optional body_P_sensor); a graph has smart factors of one kind only.  f.form is ProjForm::Rows2Smart exactly when this is set
   bool smart_pose = false;

@@ -453,13 +453,16 @@ struct SmartArgs {
   const int64_t* ptr; const int32_t *cam, *point; const double* z; const int64_t* val_off; const double* params;
   int32_t *status, *cache_state; double *cache_pose, *cache_point;
   const int32_t *calib_idx, *sensor_idx; const double *calib, *sensor;
+  double* lost_rows;   // LOST only: 8 doubles per measurement of this shard (geom.h::triangulate_lost), else null
 };
 template <bool POSE>
 __device__ __forceinline__ auto smart_cams(const SmartArgs& a, const double* values, int64_t o0) {
   if constexpr (POSE) return PoseCams{a.cam + o0, a.calib_idx + o0, a.sensor_idx + o0, a.calib, a.sensor, a.val_off, values};
   else return BundlerCams{a.cam + o0, a.val_off, values};
 }
-template <bool POSE>
+// LOST: some smart factor of the graph has useLOST set (params[7] > 0 is the sigma of triangulateLOST); the choice between the two linear
+// methods is made per factor.  <POSE, false> is the kernel of every graph without such a factor.
+template <bool POSE, bool LOST>
 __global__ __launch_bounds__(kBlock) void k_smart_triangulate(SmartArgs a, double* __restrict__ values, const double* __restrict__ gate,
                                                               double* __restrict__ scalars, int for_linearize) {
   // (a try whose factorisation timed out is repeated, api.hip: its garbage trial point must not touch the triangulation cache)
@@ -489,8 +492,13 @@ __global__ __launch_bounds__(kBlock) void k_smart_triangulate(SmartArgs a, doubl
           cs.pose(k, pose);
           for (int e = 0; e < 12; e++) a.cache_pose[12 * (k0 + k) + e] = pose[e];
         }
-        if constexpr (POSE) st = smart_triangulate(m, cs, a.z + 2 * o0, prm[0], prm[1], prm[2], pt);   // (enableEPI is refused at upload)
-        else st = smart_triangulate(m, a.cam + o0, a.val_off, values, a.z + 2 * o0, prm[0], prm[1], prm[2], pt, prm[6] != 0.0);
+        if constexpr (LOST) {
+          if constexpr (POSE) st = smart_triangulate(m, cs, a.z + 2 * o0, prm[0], prm[1], prm[2], pt, prm[7], a.lost_rows + 8 * k0);
+          else st = smart_triangulate(m, a.cam + o0, a.val_off, values, a.z + 2 * o0, prm[0], prm[1], prm[2], pt, prm[6] != 0.0, prm[7], a.lost_rows + 8 * k0);
+        } else {
+          if constexpr (POSE) st = smart_triangulate(m, cs, a.z + 2 * o0, prm[0], prm[1], prm[2], pt);   // (enableEPI is refused at upload)
+          else st = smart_triangulate(m, a.cam + o0, a.val_off, values, a.z + 2 * o0, prm[0], prm[1], prm[2], pt, prm[6] != 0.0);
+        }
         a.cache_state[sf] = st;
         for (int e = 0; e < 3; e++) a.cache_point[3 * sf + e] = pt[e];
       } else {
@@ -623,16 +631,19 @@ void launch_smart_triangulate(gtg_context& c, double* values, const double* gate
   if (!c.n_smart) return;
   auto& f = c.f;
   int32_t* status = for_linearize ? c.smart_lin_status.p : c.smart_status.p;
+  if (!gate) c.smart_last_status = status;   // (at the current values: gtg_error / gtg_linearize)
   if (c.smart_pose) {
     SmartArgs a{c.n_smart, c.smart_obs0, c.smart_ptr.p, f.proj_pose.p, f.proj_point.p, f.proj_z.p, c.val_off.p, c.smart_params.p,
-                status, c.smart_cache_state.p, c.smart_cache_pose.p, c.smart_cache_point.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.sensor.p};
-    hipLaunchKernelGGL(k_smart_triangulate<true>, dim3(grid_for(c.n_smart)), dim3(kBlock), 0, c.stream, a, values, gate, c.scalars.p,
-                       for_linearize ? 1 : 0);
+                status, c.smart_cache_state.p, c.smart_cache_pose.p, c.smart_cache_point.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.sensor.p,
+                c.smart_lost_rows.p};
+    const auto kernel = c.smart_lost ? k_smart_triangulate<true, true> : k_smart_triangulate<true, false>;   // (the LOST form only for a graph that uses it)
+    hipLaunchKernelGGL(kernel, dim3(grid_for(c.n_smart)), dim3(kBlock), 0, c.stream, a, values, gate, c.scalars.p, for_linearize ? 1 : 0);
   } else {
     SmartArgs a{c.n_smart, c.smart_obs0, c.smart_ptr.p, f.sfm_cam.p, f.sfm_point.p, f.sfm_z.p, c.val_off.p, c.smart_params.p,
-                status, c.smart_cache_state.p, c.smart_cache_pose.p, c.smart_cache_point.p, nullptr, nullptr, nullptr, nullptr};
-    hipLaunchKernelGGL(k_smart_triangulate<false>, dim3(grid_for(c.n_smart)), dim3(kBlock), 0, c.stream, a, values, gate, c.scalars.p,
-                       for_linearize ? 1 : 0);
+                status, c.smart_cache_state.p, c.smart_cache_pose.p, c.smart_cache_point.p, nullptr, nullptr, nullptr, nullptr,
+                c.smart_lost_rows.p};
+    const auto kernel = c.smart_lost ? k_smart_triangulate<false, true> : k_smart_triangulate<false, false>;   // (the LOST form only for a graph that uses it)
+    hipLaunchKernelGGL(kernel, dim3(grid_for(c.n_smart)), dim3(kBlock), 0, c.stream, a, values, gate, c.scalars.p, for_linearize ? 1 : 0);
   }
   check_hip(hipGetLastError(), "smart_triangulate");
 }
@@ -774,7 +785,8 @@ void prewarm_factors(int) {
                    (const void*)k_lin_between, (const void*)k_lin_prior, (const void*)k_error<kErrSfm>, (const void*)k_error<kErrRest>,
                    (const void*)k_error<kErrRest | kErrSmartProj>, (const void*)k_error_rows3<false>, (const void*)k_error_rows3<true>, (const void*)k_final_sum,
                    (const void*)k_linear_error<true, 2>, (const void*)k_linear_error<false, 2>, (const void*)k_linear_error<false, 3>, (const void*)k_retract,
-                   (const void*)k_sumsq, (const void*)k_smart_triangulate<false>, (const void*)k_smart_triangulate<true>, (const void*)k_lin_smart_at_infinity,
+                   (const void*)k_sumsq, (const void*)k_smart_triangulate<false, false>, (const void*)k_smart_triangulate<true, false>,
+                   (const void*)k_smart_triangulate<false, true>, (const void*)k_smart_triangulate<true, true>, (const void*)k_lin_smart_at_infinity,
                    (const void*)k_error_smart_at_infinity, (const void*)k_sfm_value_offsets, (const void*)k_lin_smart_pose_at_infinity,
                    (const void*)k_error_smart_pose_at_infinity});
 }

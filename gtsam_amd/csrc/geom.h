@@ -496,7 +496,8 @@ GT_HD bool triangulate_refine(int m, const int32_t* cams, const int64_t* val_off
 //   rank < 3 -> DEGENERATE, a camera with the point not in front -> BEHIND_CAMERA (:536-541), then per camera the distance
 //   threshold (FAR_POINT) and the largest reprojection error against the outlier threshold (OUTLIER).
 // One code for both smart factors: the camera model comes in through an accessor.  z = 2 per measurement.
-// The cameras of one track as the triangulation sees them -- pose, pinhole K, "undistort this pixel", "project":
+// The cameras of one track as the triangulation sees them -- pose, pinhole K, "undistort this pixel" (DLT), "calibrate this pixel"
+// (LOST), "project":
 //   BundlerCams  PinholeCamera<Cal3Bundler> variables (17 doubles: pose, f, k1, k2, u0, v0), SmartProjectionFactor<PinholeCamera<Cal3Bundler>>;
 //   PoseCams     (behind s2_project) PinholePose<Cal3_S2>(pose * body_P_sensor, K), SmartProjectionPoseFactor<Cal3_S2>.
 struct BundlerCams {
@@ -513,6 +514,11 @@ struct BundlerCams {
     if (!bundler_calibrate(f, c[13], c[14], u0, v0, z, pn)) return false;
     zu[0] = f * pn[0] + u0; zu[1] = f * pn[1] + v0;
     return true;
+  }
+  // Cal3Bundler::calibrate alone: the intrinsic point of a pixel (calibrateMeasurements, triangulation.h:380-393); false: no convergence
+  GT_HD bool calibrate(int k, const double* z, double* pn) const {
+    const double* c = cam(k);
+    return bundler_calibrate(c[12], c[13], c[14], c[15], c[16], z, pn);
   }
   GT_HD bool project(int k, const double* pw, double* pi) const {
     const double* c = cam(k);
@@ -589,16 +595,144 @@ GT_HD int smart_triangulate_checks(int m, const Cams& cs, const double* z, doubl
   if (outlier_thr > 0 && max_err > outlier_thr) return kTriOutlier;
   return kTriValid;
 }
+// ---- TriangulationParameters::useLOST: gtsam::triangulateLOST (geometry/triangulation.cpp:86-147) behind triangulatePoint3
+// (triangulation.h:500-518) -- Linear Optimal Sine Triangulation.  Per camera i the calibrated measurement z_i = (calibrate(pixel), 1),
+// its world direction wZ_i = R_i z_i and a partner j = (i + 1) % m give the weight
+//   q_i = |wZ_i x wZ_j| / (sigma |(t_j - t_i) x wZ_j|);
+// where a numerator or denominator is exactly 0 (coinciding directions, coinciding centres) the partners (i + k) % m, k = 2 .. m - 1, are
+// searched for the first with both > 0, and a track without one is a TriangulationUnderconstrainedException: DEGENERATE.  The two rows
+// of camera i are q_i skew(z_i)[0:2, :] R_i^T, the right side those rows times t_i.  The 2m x 3 system is solved as the reference
+// solves it: Eigen::ColPivHouseholderQR (Householder reflections, at every step the remaining column of largest norm first) with
+// setThreshold(rank_tol), whose rank() counts the pivots |R_kk| > rank_tol * max_k |R_kk| -- a RELATIVE test (the DLT path compares
+// singular values with rank_tol itself).  Reproduced on purpose: with the default rankTolerance = 1.0 no pivot exceeds the largest one,
+// the rank is 0 and EVERY LOST track is DEGENERATE.  Not through the normal equations: a tolerance of 1e-9 on R is 1e-18 on A^T A, below
+// what a double resolves.  The column norms are recomputed at every step where Eigen downdates them (ColPivHouseholderQR.h); the two
+// differ in which of two (nearly) equal columns goes first, never in the rank of a matrix whose pivots are away from the threshold.
+// `rows`: 8 doubles of work space per measurement (2 rows of [A | b]); there is no per-track array whose size depends on m.
+// Contraction is off: the zero tests above are exact in the reference (its cross products of identical vectors cancel to 0.0; a
+// contracted multiply-add would leave the rounding error of one product).
 template <class Cams>
-GT_HD int smart_triangulate(int m, const Cams& cs, const double* z, double rank_tol, double dist_thr, double outlier_thr, double* point) {
-  const int st = triangulate_dlt(m, cs, z, rank_tol, point);
+GT_HD int triangulate_lost(int m, const Cams& cs, const double* z, double sigma, double rank_tol, double* rows, double* point) {
+  _Pragma("clang fp contract(off)")
+  point[0] = point[1] = point[2] = 0.0;
+  if (m < 2) return kTriDegenerate;
+  // 1. calibrate every measurement first, as the reference does (a pixel that does not calibrate throws before anything else):
+  //    slot k holds wZ_k in [0..2] and the intrinsic point in [4..5] until its rows are written
+  for (int k = 0; k < m; k++) {
+    double T[12], pn[2];
+    cs.pose(k, T);
+    if (!cs.calibrate(k, z + 2 * k, pn)) return kTriNoConvergence;
+    double* s = rows + 8 * k;
+    for (int r = 0; r < 3; r++) s[r] = T[3 * r] * pn[0] + T[3 * r + 1] * pn[1] + T[3 * r + 2] * 1.0;
+    s[4] = pn[0]; s[5] = pn[1];
+  }
+  // 2. the weights q_i, kept in [6]
+  for (int i = 0; i < m; i++) {
+    double Ti[12];
+    cs.pose(i, Ti);
+    const double* wi = rows + 8 * i;
+    double num = 0.0, den = 0.0;
+    bool found = false;
+    for (int k = 1; k < m && !found; k++) {
+      const int j = (i + k) % m;
+      double Tj[12];
+      cs.pose(j, Tj);
+      const double* wj = rows + 8 * j;
+      const double d[3] = {Tj[9] - Ti[9], Tj[10] - Ti[10], Tj[11] - Ti[11]};
+      const double a0 = wi[1] * wj[2] - wi[2] * wj[1], a1 = wi[2] * wj[0] - wi[0] * wj[2], a2 = wi[0] * wj[1] - wi[1] * wj[0];
+      const double b0 = d[1] * wj[2] - d[2] * wj[1], b1 = d[2] * wj[0] - d[0] * wj[2], b2 = d[0] * wj[1] - d[1] * wj[0];
+      num = sqrt(a0 * a0 + a1 * a1 + a2 * a2); den = sqrt(b0 * b0 + b1 * b1 + b2 * b2);
+      // the first partner is taken unless one of the two is exactly 0 (a NaN goes through, as in the reference); the others need both > 0
+      found = k == 1 ? !(num == 0 || den == 0) : (num > 0 && den > 0);
+    }
+    if (!found) return kTriDegenerate;
+    rows[8 * i + 6] = num / (sigma * den);
+  }
+  // 3. the rows [q S R^T | q S R^T t], S = skew(z)[0:2, :] = [0 -1 zy; 1 0 -zx]
+  for (int i = 0; i < m; i++) {
+    double T[12];
+    cs.pose(i, T);
+    double* s = rows + 8 * i;
+    const double zx = s[4], zy = s[5], q = s[6];
+    double r0[3], r1[3];
+    _Pragma("unroll") for (int c = 0; c < 3; c++) {   // R^T(r, c) = T[3 c + r]
+      r0[c] = -q * T[3 * c + 1] + (q * zy) * T[3 * c + 2];
+      r1[c] = q * T[3 * c] + (q * -zx) * T[3 * c + 2];
+    }
+    s[0] = r0[0]; s[1] = r0[1]; s[2] = r0[2]; s[3] = r0[0] * T[9] + r0[1] * T[10] + r0[2] * T[11];
+    s[4] = r1[0]; s[5] = r1[1]; s[6] = r1[2]; s[7] = r1[0] * T[9] + r1[1] * T[10] + r1[2] * T[11];
+  }
+  // 4. ColPivHouseholderQR in place on the n x 4 array [A | b]: row r is rows + 4 r
+  const int n = 2 * m;
+  int p0 = 0, p1 = 1, p2 = 2;                       // the column of the point that stands in position 0, 1, 2
+  double max_pivot = 0.0, threshold_helper = 0.0, diag[3] = {0.0, 0.0, 0.0};
+  int nonzero_pivots = 3;
+  _Pragma("unroll") for (int k = 0; k < 3; k++) {
+    double head[3] = {0.0, 0.0, 0.0}, tail[3] = {0.0, 0.0, 0.0};
+    for (int r = k; r < n; r++)
+      _Pragma("unroll") for (int c = k; c < 3; c++) { const double v = rows[4 * r + c]; if (r == k) head[c] = v * v; else tail[c] += v * v; }
+    int piv = k;
+    double biggest = head[k] + tail[k];
+    _Pragma("unroll") for (int c = k + 1; c < 3; c++) if (head[c] + tail[c] > biggest) { biggest = head[c] + tail[c]; piv = c; }
+    if (k == 0) { const double e = sqrt(biggest) * kEps / n; threshold_helper = e * e; }
+    if (nonzero_pivots == 3 && biggest < threshold_helper * (n - k)) nonzero_pivots = k;
+    if (piv != k) {
+      for (int r = 0; r < n; r++) { const double v = rows[4 * r + k]; rows[4 * r + k] = rows[4 * r + piv]; rows[4 * r + piv] = v; }
+      if (k == 0) { const int t = p0; if (piv == 1) { p0 = p1; p1 = t; } else { p0 = p2; p2 = t; } }
+      else { const int t = p1; p1 = p2; p2 = t; }
+    }
+    // makeHouseholderInPlace on rows k .. n-1 of column k (Householder.h): the essential part stays below the diagonal
+    const double c0 = rows[4 * k + k];
+    double tail_sq = 0.0;
+    for (int r = k + 1; r < n; r++) tail_sq += rows[4 * r + k] * rows[4 * r + k];
+    double tau = 0.0, beta = c0;
+    if (tail_sq <= 2.2250738585072014e-308) {
+      for (int r = k + 1; r < n; r++) rows[4 * r + k] = 0.0;
+    } else {
+      beta = sqrt(c0 * c0 + tail_sq);
+      if (c0 >= 0) beta = -beta;
+      const double dn = c0 - beta;
+      for (int r = k + 1; r < n; r++) rows[4 * r + k] /= dn;
+      tau = (beta - c0) / beta;
+    }
+    rows[4 * k + k] = beta;
+    diag[k] = fabs(beta);
+    if (diag[k] > max_pivot) max_pivot = diag[k];
+    // applyHouseholderOnTheLeft to the remaining columns and to b
+    double tmp[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int r = k + 1; r < n; r++) {
+      const double e = rows[4 * r + k];
+      _Pragma("unroll") for (int c = k + 1; c < 4; c++) tmp[c] += e * rows[4 * r + c];
+    }
+    _Pragma("unroll") for (int c = k + 1; c < 4; c++) { tmp[c] += rows[4 * k + c]; rows[4 * k + c] -= tau * tmp[c]; }
+    for (int r = k + 1; r < n; r++) {
+      const double te = tau * rows[4 * r + k];
+      _Pragma("unroll") for (int c = k + 1; c < 4; c++) rows[4 * r + c] -= te * tmp[c];
+    }
+  }
+  int rank = 0;
+  _Pragma("unroll") for (int k = 0; k < 3; k++) if (k < nonzero_pivots && diag[k] > rank_tol * max_pivot) rank++;
+  if (rank < 3) return kTriDegenerate;
+  // R x = Q^T b, then the permutation back
+  const double x2 = rows[4 * 2 + 3] / rows[4 * 2 + 2];
+  const double x1 = (rows[4 * 1 + 3] - rows[4 * 1 + 2] * x2) / rows[4 * 1 + 1];
+  const double x0 = (rows[3] - rows[1] * x1 - rows[2] * x2) / rows[0];
+  _Pragma("unroll") for (int e = 0; e < 3; e++) point[e] = p0 == e ? x0 : (p1 == e ? x1 : x2);
+  return kTriValid;
+}
+// lost_sigma > 0: LOST with that sigma (lost_rows: its work space), else the DLT
+template <class Cams>
+GT_HD int smart_triangulate(int m, const Cams& cs, const double* z, double rank_tol, double dist_thr, double outlier_thr, double* point,
+                            double lost_sigma = 0.0, double* lost_rows = nullptr) {
+  const int st = lost_sigma > 0.0 ? triangulate_lost(m, cs, z, lost_sigma, rank_tol, lost_rows, point) : triangulate_dlt(m, cs, z, rank_tol, point);
   return st != kTriValid ? st : smart_triangulate_checks(m, cs, z, dist_thr, outlier_thr, point);
 }
-// PinholeCamera<Cal3Bundler> cameras: cams[k] -> values + val_off[cams[k]]; enable_epi: the DLT point refined (triangulate_refine)
+// PinholeCamera<Cal3Bundler> cameras: cams[k] -> values + val_off[cams[k]]; enable_epi: the linear point refined (triangulate_refine)
 GT_HD int smart_triangulate(int m, const int32_t* cams, const int64_t* val_off, const double* values, const double* z,
-                            double rank_tol, double dist_thr, double outlier_thr, double* point, bool enable_epi = false) {
+                            double rank_tol, double dist_thr, double outlier_thr, double* point, bool enable_epi = false,
+                            double lost_sigma = 0.0, double* lost_rows = nullptr) {
   const BundlerCams cs{cams, val_off, values};
-  const int st = triangulate_dlt(m, cs, z, rank_tol, point);
+  const int st = lost_sigma > 0.0 ? triangulate_lost(m, cs, z, lost_sigma, rank_tol, lost_rows, point) : triangulate_dlt(m, cs, z, rank_tol, point);
   if (st != kTriValid) return st;
   if (enable_epi && !triangulate_refine(m, cams, val_off, values, z, point)) return kTriCheiralityThrown;   // (triangulation.h:531-534)
   return smart_triangulate_checks(m, cs, z, dist_thr, outlier_thr, point);
@@ -684,6 +818,13 @@ struct PoseCams {
     pinhole(k, K);
     s2_calibrate(K, z, pn);
     s2_uncalibrate(K, pn, zu);
+    return true;
+  }
+  // Cal3_S2::calibrate alone (calibrateMeasurements, triangulation.h:380-393): no round trip through uncalibrate
+  GT_HD bool calibrate(int k, const double* z, double* pn) const {
+    double K[5];
+    pinhole(k, K);
+    s2_calibrate(K, z, pn);
     return true;
   }
   GT_HD bool project(int k, const double* pw, double* pi) const {

@@ -75,6 +75,8 @@ SmartView::SmartView(const gtg_problem& user) : q(user), p(&user) {
     // rankTolerance, landmarkDistanceThreshold, dynamicOutlierRejectionThreshold (negative = off, as in the reference),
     // retriangulationThreshold: numbers, not NaN / inf (a NaN threshold silently disables the test it guards)
     for (int e = 0; e < 4; e++) if (!std::isfinite(sp[e])) throw std::invalid_argument("smart factor: a threshold is not finite");
+    // useLOST: 0 = DLT, > 0 = LOST with that measurement sigma (triangulation.h:503)
+    if (!(std::isfinite(sp[7]) && sp[7] >= 0.0)) throw std::invalid_argument("smart factor: the useLOST sigma (smart_params[8 i + 7]) must be 0 (DLT) or a positive finite number");
     // the reference requires an isotropic model (SmartFactorBase.h:107-114: "SmartFactorBase: needs isotropic")
     const int32_t nz = user.smart_noise[i];
     if (nz < 0 || nz >= user.n_noise || user.noise_dim[nz] != 2 ||
@@ -179,10 +181,13 @@ void upload_smart_state(gtg_context& c, const gtg_problem& user) {
   if (!n_smart) {
     c.smart_ptr.free(); c.smart_params.free(); c.obs_smart.free(); c.lm_smart.free(); c.smart_status.free(); c.smart_lin_status.free();
     c.smart_cache_state.free(); c.smart_cache_pose.free(); c.smart_cache_point.free();
+    c.smart_lost = false; c.smart_lost_rows.free(); c.smart_last_status = nullptr;
     return;
   }
   const int64_t n_meas = user.smart_ptr[n_smart];
   std::vector<double> prm(user.smart_params, user.smart_params + 8 * n_smart);
+  c.smart_lost = false; c.smart_last_status = nullptr;
+  for (int64_t i = 0; i < n_smart; i++) c.smart_lost = c.smart_lost || prm[8 * (size_t)i + 7] > 0.0;
   up(c.smart_params, prm, c.stream);
   std::vector<int32_t> none((size_t)n_smart, -1);
   up(c.smart_cache_state, none, c.stream);
@@ -321,6 +326,7 @@ std::vector<int32_t> upload_smart_tracks(gtg_context& c, int64_t n, const int32_
   }
   for (int64_t i = 0; i < c.n_smart; i++) rel[(size_t)i + 1] += rel[(size_t)i];
   c.smart_obs0 = obs0;
+  if (c.smart_lost) c.smart_lost_rows.alloc(8 * (size_t)std::max<int64_t>(rel.back(), 1)); else c.smart_lost_rows.free();   // (geom.h::triangulate_lost)
   up(c.smart_ptr, rel, c.stream);
   up(c.obs_smart, of_local, c.stream);
   return of_local;

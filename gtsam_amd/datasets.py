@@ -765,6 +765,179 @@ def smart_rig_scene(name, seed=0, scene=None, params=None):
     return smart_rig_graph(seed=seed, params=prm, **{**spec["scene"], **(scene or {})})
 
 
+def smart_lost_graph(kind, tracks, n_poses=10, seed=0, arc=0.5, radius=8.0, box=(2.0, 1.5, 2.0), sigma=1.0, pixel_noise=0.3, params=None,
+                     dlt_params=None, K=(520.0, 515.0, 0.3, 320.0, 240.0), bundler=(560.0, -0.04, 0.006, 320.0, 240.0), sensor=None, rig=(),
+                     see=0.6, far_distance=(150.0, 400.0), thin_distance=(2.0e6, 4.0e6), outlier_shift=150.0, priors=(0, 1),
+                     between_chain=False, init_noise=(0.004, 0.02)):
+    """A visual-odometry scene for TriangulationParameters::useLOST, built through the API mirror.  `kind`: "camera"
+    (SmartProjectionFactor<PinholeCamera<Cal3Bundler>>: the variables are cameras with the calibration `bundler` = f, k1, k2, u0, v0),
+    "pose" (SmartProjectionPose3Factor with `K` and the body_P_sensor `sensor`) or "rig" (SmartProjectionRigFactor over `rig`, as
+    smart_rig_graph takes it).  `n_poses` bodies on an arc of half opening `arc` and radius `radius` look inward at points in `box`.
+    `tracks`: one (kind, lost) per smart factor in graph order; lost False gives the factor `dlt_params` in place of `params` --
+      "random"    every (pose, camera) sees the point with probability `see` (at least two sightings);
+      "single"    one sighting (DEGENERATE);
+      "far"       "random" on a point `far_distance` away (FAR_POINT under a landmarkDistanceThreshold);
+      "thin"      "random" on a point `thin_distance` away, seen from the INITIAL poses without pixel noise: at the initial values its rays
+                  are parallel to a few parts in 1e6 (DEGENERATE by LOST's rank test; with pixel noise, or from the true poses, the
+                  rays of any far point differ by the angle of that noise, about 1e-3);
+      "outlier"   "random" with the last measurement moved by `outlier_shift` pixels;
+      "coincide"  two sightings, the second a copy of the first: same pose, camera and pixel (LOST finds no partner: DEGENERATE);
+      "dup_first" three sightings, the second a copy of the first (LOST searches a partner for both and finds the third).
+    Only a rig factor takes the same key twice (SmartFactorBase::add refuses it), so for the other two kinds the copy is seen from a TWIN
+    of pose 0: one more variable, X(n_poses), with the same true and the same initial value and a prior of its own.
+    Graph order: between factors, priors, smart factors (the order in which the C++ shim's extractor meets the noise models of a graph
+    without projection factors, so that both extractors number them alike).  Returns (graph, initial values, info)."""
+    from . import api as A
+    rng = np.random.default_rng(seed)
+    ang = np.linspace(-arc, arc, n_poses)
+    tb = np.stack([radius * np.sin(ang), 0.02 * radius * rng.normal(size=n_poses), -radius * np.cos(ang)], 1)
+    Rb = _rodrigues(np.stack([0.02 * rng.normal(size=n_poses), -ang, 0.02 * rng.normal(size=n_poses)], 1))   # +z looks at the origin
+    as_pose = lambda e: A.Pose3() if e is None else A.Pose3(A.Rot3(_rodrigues(np.array([e[0]]))[0]), np.array(e[1], np.float64))
+    if kind == "rig":
+        cams = A.CameraSetPinholePoseCal3_S2()
+        for Kc, e in rig:
+            cams.push_back(A.PinholePoseCal3_S2(as_pose(e), A.Cal3_S2(*Kc)))
+        ext = [c.pose() for c in cams]
+        cals = [c.calibration().v for c in cams]
+    else:
+        ext = [as_pose(sensor if kind == "pose" else None)]
+        cals = [np.array(K, np.float64)]
+        Kc = A.Cal3_S2(*K)
+    model = A.noiseModel.Isotropic.Sigma(2, sigma)
+    X = A.symbol_shorthand.X
+    pts = np.stack([rng.uniform(-b, b, len(tracks)) for b in box], 1)
+    Ri = Rb @ _rodrigues(rng.normal(0, init_noise[0], (n_poses, 3)))
+    ti = tb + rng.normal(0, init_noise[1], tb.shape)
+
+    noise_of = []          # the noise of the pixels of the track in hand, in the order they were drawn
+
+    def pixel(i, c, pt, initial=False):
+        Rw, tw = (Ri, ti) if initial else (Rb, tb)
+        R = Rw[i] @ ext[c].R; t = tw[i] + Rw[i] @ ext[c].t
+        q = R.T @ (pt - t)
+        u, v = q[0] / q[2], q[1] / q[2]
+        if kind == "camera":
+            f, k1, k2, u0, v0 = bundler
+            g = 1.0 + (k1 + k2 * (u * u + v * v)) * (u * u + v * v)
+            z = np.array([f * g * u + u0, f * g * v + v0])
+        else:
+            fx, fy, s, u0, v0 = cals[c]
+            z = np.array([fx * u + s * v + u0, fy * v + v0])
+        noise_of.append(pixel_noise * rng.normal(size=2))
+        return z + noise_of[-1]
+
+    def random_views():
+        seen = np.argwhere(rng.uniform(size=(n_poses, len(ext))) < see)
+        if seen.shape[0] < 2:
+            seen = np.array([[0, 0], [n_poses - 1, 0]])
+        return [(int(i), int(c)) for i, c in seen]
+
+    graph, initial, smart = A.NonlinearFactorGraph(), A.Values(), []
+    for t, (what, lost) in enumerate(tracks):
+        noise_of = []
+        if what in ("far", "thin"):
+            d = rng.uniform(*(far_distance if what == "far" else thin_distance))
+            pts[t] = [d * rng.uniform(-0.15, 0.15), d * rng.uniform(-0.12, 0.12), d]
+        views = random_views()
+        if what == "single":
+            views = views[:1]
+        if what in ("coincide", "dup_first"):
+            views = [views[0] if kind == "rig" else (0, 0), views[-1] if views[-1][0] != 0 else (n_poses - 1, 0)]
+        zs = [pixel(i, c, pts[t], what == "thin") for i, c in views]
+        if what == "thin":
+            zs = [z - e for z, e in zip(zs, noise_of)]
+        if what == "outlier":
+            zs[-1] = zs[-1] + outlier_shift * np.array([0.8, -0.6])
+        copy = views[0] if kind == "rig" else (n_poses, 0)
+        if what == "coincide":
+            views, zs = [views[0], copy], [zs[0], zs[0]]
+        if what == "dup_first":
+            views, zs = [views[0], copy, views[1]], [zs[0], zs[0], zs[1]]
+        prm = params if lost else dlt_params
+        if kind == "camera":
+            f = A.SmartProjectionFactorPinholeCameraCal3Bundler(model, prm)
+        elif kind == "pose":
+            f = A.SmartProjectionPose3Factor(model, Kc, ext[0] if sensor is not None else None, prm)
+        else:
+            f = A.SmartProjectionRigFactorPinholePoseCal3_S2(model, cams, prm)
+        for z, (i, c) in zip(zs, views):
+            f.add(z, X(i), c) if kind == "rig" else f.add(z, X(i))
+        smart.append(f)
+    nm = A.noiseModel
+    if between_chain and kind != "camera":
+        n6b = nm.Diagonal.Sigmas([0.02, 0.02, 0.03, 0.1, 0.1, 0.15])
+        for i in range(n_poses - 1):
+            Rz = Rb[i].T @ Rb[i + 1]; tz = Rb[i].T @ (tb[i + 1] - tb[i])
+            graph.add(A.BetweenFactorPose3(X(i), X(i + 1), A.Pose3(A.Rot3(Rz @ _rodrigues(rng.normal(0, 0.005, (1, 3)))[0]), tz + rng.normal(0, 0.02, 3)), n6b))
+    if kind != "rig":                                    # the twin of pose 0
+        Rb, tb, Ri, ti = (np.concatenate([a, a[:1]]) for a in (Rb, tb, Ri, ti))
+        priors = tuple(priors) + (n_poses,)
+        n_poses += 1
+    if kind == "camera":
+        n9 = nm.Diagonal.Sigmas([0.1] * 3 + [0.3] * 3 + [5.0, 0.002, 0.002])
+        for i in priors:
+            graph.addPriorPinholeCameraCal3Bundler(X(i), A.PinholeCameraCal3Bundler(A.Pose3(A.Rot3(Rb[i]), tb[i]), A.Cal3Bundler(*bundler)), n9)
+        for i in range(n_poses):
+            initial.insert(X(i), A.PinholeCameraCal3Bundler(A.Pose3(A.Rot3(Ri[i]), ti[i]), A.Cal3Bundler(*bundler)))
+    else:
+        n6 = nm.Diagonal.Sigmas([0.1] * 3 + [0.3] * 3)
+        for i in priors:
+            graph.addPriorPose3(X(i), A.Pose3(A.Rot3(Rb[i]), tb[i]), n6)
+        for i in range(n_poses):
+            initial.insert(X(i), A.Pose3(A.Rot3(Ri[i]), ti[i]))
+    for f in smart:
+        graph.add(f)
+    return graph, initial, {"kind": [w for w, _ in tracks], "lost": np.array([l for _, l in tracks]), "points": pts}
+
+
+def _lost_tracks(n, mixed=False):
+    """n tracks with every special kind of smart_lost_graph among them; mixed: every third random track is a DLT factor"""
+    t = [("random", True)] * n
+    for k, what in ((3, "coincide"), (5, "dup_first"), (8, "single"), (11, "far"), (14, "thin"), (17, "outlier"), (20, "far"), (23, "thin"),
+                    (26, "dup_first"), (29, "outlier")):
+        t[k] = (what, True)
+    if mixed:
+        t = [(w, not (w == "random" and k % 3 == 1)) for k, (w, _) in enumerate(t)]
+    return t
+
+
+# The LOST scenes the fixtures of tests/golden/make_golden_smart_lost.py are recorded on (a seed is part of the fixture, as for
+# SMART_POSE_SCENES).  rankTolerance 1e-4: LOST's rank test is relative to the largest pivot, so the "thin" tracks (rays parallel to a
+# few parts in 1e6) fail it and the near and the merely far ones pass.  The camera scene has a prior on every camera: few tracks leave
+# the distortion coefficients of a camera weakly determined, and a step that moves them far makes Cal3Bundler::calibrate diverge.  `variants`: further fixtures <name>_<variant> on the same scene with
+# these SmartProjectionParams fields replaced.
+_LOST_PARAMS = dict(degeneracyMode=1, rankTolerance=1e-4, landmarkDistanceThreshold=100.0, dynamicOutlierRejectionThreshold=40.0, useLOST=True)
+SMART_LOST_SCENES = {
+    "smart_lost_cam": dict(scene=dict(kind="camera", tracks=_lost_tracks(37), n_poses=7, sigma=1.0, pixel_noise=0.3, see=0.55, priors=tuple(range(7))),
+                           params=_LOST_PARAMS, variants={"epi": dict(enableEPI=True)}),
+    "smart_lost_pose": dict(scene=dict(kind="pose", tracks=_lost_tracks(83, mixed=True), n_poses=9, sigma=1.5, pixel_noise=0.5, see=0.6,
+                                       sensor=((0.02, -0.03, 0.01), (0.1, -0.05, 0.2)), between_chain=True, priors=(0,)),
+                            params=_LOST_PARAMS, variants={}),
+    "smart_lost_rig": dict(scene=dict(kind="rig", tracks=_lost_tracks(45), n_poses=6, sigma=1.0, pixel_noise=0.4, see=0.5,
+                                      rig=(((520.0, 515.0, 0.3, 320.0, 240.0), ((0.02, -0.03, 0.01), (0.1, -0.05, 0.2))),
+                                           ((500.0, 505.0, 0.0, 310.0, 245.0), ((0.01, 0.08, -0.02), (0.45, 0.0, 0.15)))),
+                                      between_chain=True, priors=(0,)),
+                           # a triangulation noise model: LOST's sigma is the mean of its sigmas, 0.4
+                           params={**_LOST_PARAMS, "triangulationNoiseModel": (0.3, 0.5)}, variants={}),
+}
+
+
+def smart_lost_scene(name, seed=0, variant=None, scene=None, params=None):
+    """(graph, initial values, info) of one of SMART_LOST_SCENES (or of its variant); LOST factors get the scene's parameters, DLT
+    factors of a mixed scene the same with useLOST off.  `scene` / `params`: keyword arguments / parameter fields to replace."""
+    from . import api as A
+    spec = SMART_LOST_SCENES[name]
+    fields = {**spec["params"], **(spec["variants"][variant] if variant else {}), **(params or {})}
+    prm, dlt = A.SmartProjectionParams(), A.SmartProjectionParams()
+    for k, v in fields.items():
+        if k == "triangulationNoiseModel":
+            v = A.noiseModel.Diagonal.Sigmas(v)
+        setattr(prm, k, v)
+        setattr(dlt, k, v)
+    dlt.useLOST = False
+    return smart_lost_graph(seed=seed, params=prm, dlt_params=dlt, **{**spec["scene"], **(scene or {})})
+
+
 def _noisy_bearing(rng, q, sigma):
     """The direction of the local point q with a tangent-plane error of `sigma` radians, as a Unit3."""
     from . import api as A

@@ -446,7 +446,9 @@ void addSmartRows(Extract& x, const FACTOR& sf, const KeyVector& fkeys, const Sm
   // HESSIAN, JACOBIAN_Q and JACOBIAN_SVD are the same normal equations (the device never forms the factor itself); an
   // IMPLICIT_SCHUR factor cannot be eliminated by the reference's direct solvers either.
   if (sp.linearizationMode == IMPLICIT_SCHUR) throw std::invalid_argument(std::string(what) + ": the IMPLICIT_SCHUR linearisation is not supported");
-  if (tp.useLOST) throw std::invalid_argument(std::string(what) + ": useLOST is not supported");
+  // useLOST: the sigma triangulatePoint3 hands to triangulateLOST (geometry/triangulation.h:503) -- the mean of the triangulation noise
+  // model's sigmas, 1e-4 without one; what sigmas() throws (a Robust model) leaves the constructor as it leaves the reference's optimizer
+  const double lost_sigma = tp.useLOST ? (tp.noiseModel ? tp.noiseModel->sigmas().mean() : 1e-4) : 0.0;
   if (tp.enableEPI && tp.noiseModel) throw std::invalid_argument(std::string(what) + ": enableEPI with a noise model in the triangulation parameters is not supported");
   Extract::run(x.sm_nz, iso);
   const auto& zs = sf.measured();
@@ -455,7 +457,7 @@ void addSmartRows(Extract& x, const FACTOR& sf, const KeyVector& fkeys, const Sm
   x.sm_ptr.push_back((int64_t)x.sm_cam.size());
   x.sm_prm.insert(x.sm_prm.end(), {tp.rankTolerance, tp.landmarkDistanceThreshold, tp.dynamicOutlierRejectionThreshold, sp.retriangulationThreshold,
                                    sp.degeneracyMode == ZERO_ON_DEGENERACY ? 1.0 : (sp.degeneracyMode == HANDLE_INFINITY ? 2.0 : 0.0),
-                                   sp.linearizationMode == JACOBIAN_Q ? 2.0 : (sp.linearizationMode == JACOBIAN_SVD ? 3.0 : 0.0), tp.enableEPI ? 1.0 : 0.0, 0.0});
+                                   sp.linearizationMode == JACOBIAN_Q ? 2.0 : (sp.linearizationMode == JACOBIAN_SVD ? 3.0 : 0.0), tp.enableEPI ? 1.0 : 0.0, lost_sigma});
 }
 // SmartProjectionFactor<SfmCamera>.  (throwCheirality / verboseCheirality are read by the pose-only smart factors, not by
 // SmartProjectionFactor<CAMERA>.)

@@ -27,7 +27,7 @@ SYMBOLS = ["gtg_create", "gtg_destroy", "gtg_prewarm", "gtg_last_error", "gtg_ve
            "gtg_accept", "gtg_get_delta", "gtg_get_gradient", "gtg_get_hessian_diagonal",
            "gtg_get_jacobians", "gtg_reduced_dim", "gtg_get_reduced_matrix", "gtg_set_allreduce",
            "gtg_enable_timing", "gtg_get_phase_ms", "gtg_reset_timing", "gtg_phase_name",
-           "gtg_cholesky_flops", "gtg_cholesky_flops_block_level", "gtg_cholesky_flops_executed", "gtg_linearize_bytes", "gtg_dense_cholesky_host", "gtg_structure_hash", "gtg_smart_repeated_keys",
+           "gtg_cholesky_flops", "gtg_cholesky_flops_block_level", "gtg_cholesky_flops_executed", "gtg_linearize_bytes", "gtg_dense_cholesky_host", "gtg_structure_hash", "gtg_smart_repeated_keys", "gtg_smart_lost_workspace", "gtg_get_smart_triangulation",
            "gtg_debug_plan_sizes", "gtg_debug_plan_lists", "gtg_debug_df_plan", "gtg_debug_df_device_tables", "gtg_debug_df_chains", "gtg_debug_reduced_order", "gtg_debug_df_ctrl", "gtg_debug_df_poll_stats", "gtg_debug_df_trace", "gtg_release_cached_memory", "gtg_cached_memory_bytes", "gtg_values_device_ptr", "gtg_values_changed",
            "gtg_io_last_error", "gtg_io_bal_sizes", "gtg_io_read_bal", "gtg_io_write_bal",
            "gtg_io_g2o_sizes", "gtg_io_read_g2o", "gtg_io_write_g2o",
@@ -62,6 +62,9 @@ def load():
         getattr(lib, name).restype = C.c_int64
         getattr(lib, name).argtypes = [C.c_void_p]
     lib.gtg_smart_repeated_keys.argtypes = [C.c_void_p]
+    lib.gtg_smart_lost_workspace.restype = C.c_int64
+    lib.gtg_smart_lost_workspace.argtypes = [C.c_void_p]
+    lib.gtg_get_smart_triangulation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     lib.gtg_cholesky_flops.restype = C.c_double
     lib.gtg_cholesky_flops.argtypes = [C.c_void_p]
     lib.gtg_cholesky_flops_block_level.restype = C.c_double
@@ -248,7 +251,15 @@ class DeviceGraph:
     def cholesky_flops_executed(self): return self.lib.gtg_cholesky_flops_executed(self.h)
     def structure_hash(self): return int(self.lib.gtg_structure_hash(self.h))
     def smart_repeated_keys(self): return int(self.lib.gtg_smart_repeated_keys(self.h))   # 1: a rig-type smart factor names a pose twice
+    def smart_lost_workspace(self): return int(self.lib.gtg_smart_lost_workspace(self.h))    # doubles of LOST work space on this shard (0: LOST not in use)
     def linearize_bytes(self): return self.lib.gtg_linearize_bytes(self.h)
+
+    def smart_triangulation(self):
+        """(status [n_smart] int32, points [n_smart, 3]) of the last error() / linearize(): see gtg_get_smart_triangulation."""
+        n = int(self.problem.n_smart)
+        st, pts = np.zeros(n, np.int32), np.zeros((n, 3))
+        _check(self.lib.gtg_get_smart_triangulation(self.h, st.ctypes.data, pts.ctypes.data, n), "gtg_get_smart_triangulation")
+        return st, pts
 
     def cholesky_plan(self):
         """Test hook: the tile schedule (dict of numpy index arrays), see gtg_debug_plan_lists."""

@@ -281,7 +281,8 @@ class Problem:
     # ---- smart factors -----------------------------------------------------------------------
     def add_smart(self, cams, zs, noise_idx: int, rank_tolerance=1.0, landmark_distance_threshold=-1.0,
                   dynamic_outlier_rejection_threshold=-1.0, retriangulation_threshold=1e-5, degeneracy_mode=0,
-                  linearization_mode=0, enable_epi=False, calib=-1, sensor=-1, meas_calib=None, meas_sensor=None):
+                  linearization_mode=0, enable_epi=False, calib=-1, sensor=-1, meas_calib=None, meas_sensor=None,
+                  use_lost=False, lost_sigma=1e-4):
         """One SmartProjectionFactor<PinholeCamera<Cal3Bundler>>: camera variable ids + their pixel measurements -- or, with calib >= 0
         (an entry of the calib table; sensor: an entry of the sensor table or -1), one SmartProjectionPoseFactor<Cal3_S2>: POSE3
         variable ids + their pixel measurements -- or, with meas_calib (an entry of the calib table per measurement; meas_sensor: an entry
@@ -290,8 +291,12 @@ class Problem:
         SmartProjectionParams() / TriangulationParameters() (slam/SmartFactorParams.h:58-66, geometry/triangulation.h:583-600).
         degeneracy_mode 0 IGNORE_DEGENERACY, 1 ZERO_ON_DEGENERACY, 2 HANDLE_INFINITY; linearization_mode 0 HESSIAN, 2 JACOBIAN_Q,
         3 JACOBIAN_SVD (1 = IMPLICIT_SCHUR cannot be eliminated by the reference's direct solvers and is refused); enable_epi =
-        TriangulationParameters::enableEPI (the DLT point refined by the reference's LM on TriangulationFactors)."""
+        TriangulationParameters::enableEPI (the DLT point refined by the reference's LM on TriangulationFactors); use_lost =
+        TriangulationParameters::useLOST (triangulateLOST in place of the DLT) with lost_sigma the sigma triangulatePoint3 hands to it: the
+        mean of the triangulation noise model's sigmas, 1e-4 without one (geometry/triangulation.h:503)."""
         cams = _a(cams, np.int32); zs = _a(zs, np.float64)
+        if use_lost and not (np.isfinite(lost_sigma) and lost_sigma > 0):
+            raise ValueError("use_lost needs a positive finite lost_sigma")
         if zs.size != 2 * cams.size or cams.size < 1:
             raise ValueError("a smart factor needs one 2-vector per camera")
         rig = meas_calib is not None
@@ -310,7 +315,8 @@ class Problem:
         self.smart_noise = np.concatenate([self.smart_noise, np.array([noise_idx], np.int32)])
         self.smart_params = np.concatenate([self.smart_params, [rank_tolerance, landmark_distance_threshold,
                                                                 dynamic_outlier_rejection_threshold, retriangulation_threshold,
-                                                                float(degeneracy_mode), float(linearization_mode), 1.0 if enable_epi else 0.0, 0.0]])
+                                                                float(degeneracy_mode), float(linearization_mode), 1.0 if enable_epi else 0.0,
+                                                                float(lost_sigma) if use_lost else 0.0]])
         if rig or self.smart_meas_calib.size:                        # the two tables exist once a rig-type factor does
             n = self.smart_cam.size - cams.size
             padm = lambda a: np.concatenate([a, np.full(n - a.size, -1, np.int32)])

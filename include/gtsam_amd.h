@@ -149,10 +149,14 @@ typedef struct gtg_problem {
                                      2 HANDLE_INFINITY), linearizationMode (0 HESSIAN, 2 JACOBIAN_Q, 3 JACOBIAN_SVD; 1 =
                                      IMPLICIT_SCHUR is refused: the reference's direct solvers cannot eliminate it either),
                                      enableEPI (0 / 1: the DLT point refined by the reference's LM on TriangulationFactors,
-                                     triangulation.h:211-221, 531-534), 1 reserved.  A track that does not triangulate is what SmartProjectionFactor.h makes of it:
+                                     triangulation.h:211-221, 531-534), useLOST (0: DLT; > 0: triangulateLOST, geometry/triangulation.cpp:86-147,
+                                     and the value is its measurement sigma -- the mean of the triangulation noise model's sigmas, or
+                                     1e-4 without one, triangulation.h:503; negative or non-finite: refused.  The rank test of LOST
+                                     is RELATIVE to the largest pivot of the reference's column-pivoted QR: with rankTolerance 1.0
+                                     every LOST track is DEGENERATE, as in the reference).  A track that does not triangulate is what SmartProjectionFactor.h makes of it:
                                      nothing (ZERO_ON_DEGENERACY; the Jacobian modes when linearising), a point at infinity
                                      (:356-371 when linearising in HESSIAN mode, :419-427 in the error under HANDLE_INFINITY), error
-                                     0.0 otherwise.  useLOST is not supported.  Where the reference THROWS out of
+                                     0.0 otherwise.  Where the reference THROWS out of
                                      linearize() / error() -- the point at infinity behind one of the track's cameras
                                      or the enableEPI refinement linearising behind a camera (CheiralityException),
                                      Cal3Bundler::calibrate not converging -- the call returns an error */
@@ -348,6 +352,15 @@ double gtg_linearize_bytes(gtg_handle h);
  * diagonal and the block-Jacobi blocks on the unique keys are launched for such graphs only), 0 when none does, -1 without a problem.
  * Derived from the WHOLE graph: every shard reports the same value. */
 int gtg_smart_repeated_keys(gtg_handle h);
+/* doubles of work space the LOST triangulation holds on this handle: 8 per smart measurement of this shard when some smart factor
+ * of the graph has useLOST on, 0 otherwise (-1: nothing uploaded) */
+int64_t gtg_smart_lost_workspace(gtg_handle h);
+/* The TriangulationResult of every smart factor (SmartProjectionFactor::point()) as the last gtg_error / gtg_linearize left it, in
+ * the caller's factor order: status[i] = 0 VALID, 1 DEGENERATE, 2 BEHIND_CAMERA, 3 OUTLIER, 4 FAR_POINT, 5 / 6 the two cases in which
+ * the reference throws (see smart_params), + 16 when that call replaced the failed track's landmark by a point at infinity;
+ * points3[3 i ..] the point (the direction with + 16; zeros for a failed track otherwise).  A track owned by another shard reports
+ * status -1 and zeros.  n_smart must be gtg_problem.n_smart. */
+int gtg_get_smart_triangulation(gtg_handle h, int32_t* status, double* points3, int64_t n_smart);
 
 /* standalone kernels exposed for unit parity tests (tests/ only): dense FP64 Cholesky of an
  * n x n row-major SPD matrix (lower triangle) held in host memory; returns GTG_INDETERMINATE on a
