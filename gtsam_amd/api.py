@@ -18,8 +18,8 @@ import numpy as np
 
 from .optimizer import DeviceLevenbergMarquardt
 from .params import LevenbergMarquardtParams
-from .problem import (NOISE_DIAGONAL, NOISE_GAUSSIAN, NOISE_ISOTROPIC, NOISE_UNIT, SAM_BEARING, SAM_BEARING_RANGE, SAM_RANGE, STORAGE, TANGENT,
-                      VAR_POINT3, VAR_POSE2, VAR_POSE3, VAR_SFM_CAMERA, Problem)
+from .problem import (NOISE_DIAGONAL, NOISE_GAUSSIAN, NOISE_ISOTROPIC, NOISE_UNIT, POSE_PARTIAL_ROTATION, POSE_PARTIAL_TRANSLATION, SAM_BEARING,
+                      SAM_BEARING_RANGE, SAM_RANGE, STORAGE, TANGENT, VAR_POINT3, VAR_POSE2, VAR_POSE3, VAR_SFM_CAMERA, Problem)
 
 
 # ---- keys ---------------------------------------------------------------------------------------------------
@@ -87,6 +87,31 @@ class Pose3:
     def from_packed(p): return Pose3(Rot3(np.asarray(p[:9]).reshape(3, 3)), p[9:12])
 
 
+class Rot2:
+    """gtsam.Rot2 (geometry/Rot2.h): stored as the (c, s) the reference holds -- cos and sin of the angle it was made from
+    (Rot2.h:58-59), or what fromCosSin's normalize() leaves of the pair it was given (Rot2.cpp:27-30, 56-64)."""
+
+    def __init__(self, theta=0.0):
+        self.c_, self.s_ = float(np.cos(theta)), float(np.sin(theta))
+
+    @staticmethod
+    def fromAngle(theta): return Rot2(theta)
+
+    @staticmethod
+    def fromCosSin(c, s):
+        r = Rot2()
+        scale = c * c + s * s
+        if abs(scale - 1.0) > 1e-10:
+            scale = 1.0 / np.sqrt(scale)
+            c, s = c * scale, s * scale
+        r.c_, r.s_ = float(c), float(s)
+        return r
+
+    def c(self): return self.c_
+    def s(self): return self.s_
+    def theta(self): return float(np.arctan2(self.s_, self.c_))
+
+
 class Pose2:
     """gtsam.Pose2(x, y, theta) (geometry/Pose2.h); packed as (x, y, theta)."""
 
@@ -96,6 +121,8 @@ class Pose2:
     def x(self): return self.v[0]
     def y(self): return self.v[1]
     def theta(self): return self.v[2]
+    def translation(self): return self.v[:2].copy()
+    def rotation(self): return Rot2(self.v[2])
     def packed(self): return self.v.copy()
 
     @staticmethod
@@ -452,6 +479,55 @@ class PriorFactorPoint3(_Prior): pass
 class PriorFactorPinholeCameraCal3Bundler(_Prior): pass
 
 
+class _PosePartial:
+    """PoseTranslationPrior<POSE> / PoseRotationPrior<POSE> (slam/PoseTranslationPrior.h, slam/PoseRotationPrior.h; wrapped in
+    slam/slam.i:197-220 with the constructor (key, pose_z, noiseModel)): z = the measurement doubles of Problem.add_pose_partial."""
+    kind, var_type, rows = None, None, None
+
+    def __init__(self, key, pose_z, noiseModel):
+        self.keys_, self.model, self.z = (key,), noiseModel, self._measured(pose_z)
+
+    def measured(self): return self.z.copy()
+
+
+class PoseTranslationPrior3D(_PosePartial):
+    """PoseTranslationPrior<Pose3>: pose_z a Pose3 (its translation is taken) or a Point3."""
+    kind, var_type, rows = POSE_PARTIAL_TRANSLATION, VAR_POSE3, 3
+
+    @staticmethod
+    def _measured(pose_z):
+        return np.asarray(pose_z.translation() if isinstance(pose_z, Pose3) else pose_z, np.float64).reshape(3).copy()
+
+
+class PoseRotationPrior3D(_PosePartial):
+    """PoseRotationPrior<Pose3>: pose_z a Pose3 (its rotation is taken) or a Rot3; z = the rotation matrix, row-major."""
+    kind, var_type, rows = POSE_PARTIAL_ROTATION, VAR_POSE3, 3
+
+    @staticmethod
+    def _measured(pose_z):
+        R = pose_z.rotation().matrix() if isinstance(pose_z, Pose3) else pose_z.matrix() if isinstance(pose_z, Rot3) else pose_z
+        return np.asarray(R, np.float64).reshape(9).copy()
+
+
+class PoseTranslationPrior2D(_PosePartial):
+    """PoseTranslationPrior<Pose2>: pose_z a Pose2 (its translation is taken) or a Point2."""
+    kind, var_type, rows = POSE_PARTIAL_TRANSLATION, VAR_POSE2, 2
+
+    @staticmethod
+    def _measured(pose_z):
+        return np.asarray(pose_z.translation() if isinstance(pose_z, Pose2) else pose_z, np.float64).reshape(2).copy()
+
+
+class PoseRotationPrior2D(_PosePartial):
+    """PoseRotationPrior<Pose2>: pose_z a Pose2 (its rotation is taken), a Rot2 or an angle; z = (c, s) as the Rot2 holds them."""
+    kind, var_type, rows = POSE_PARTIAL_ROTATION, VAR_POSE2, 1
+
+    @staticmethod
+    def _measured(pose_z):
+        r = pose_z.rotation() if isinstance(pose_z, Pose2) else pose_z if isinstance(pose_z, Rot2) else Rot2(float(pose_z))
+        return np.array([r.c(), r.s()], np.float64)
+
+
 class Values:
     def __init__(self): self._d = {}
 
@@ -596,6 +672,11 @@ def extract(graph: NonlinearFactorGraph, values: Values):
             btw.append((vid(f.keys_[0]), vid(f.keys_[1]), f.z.packed(), nid(f.model, 6)))
         elif isinstance(f, BetweenFactorPose2):   # same table: the measurement sits in the first 3 of the 12 doubles
             btw.append((vid(f.keys_[0]), vid(f.keys_[1]), np.concatenate([f.z.packed(), np.zeros(9)]), nid(f.model, 3)))
+        elif isinstance(f, _PosePartial):
+            v = vid(f.keys_[0])
+            if vt[v] != f.var_type:
+                raise ValueError(f"{type(f).__name__}: the value of its key is not a {'Pose3' if f.var_type == VAR_POSE3 else 'Pose2'}")
+            p.add_pose_partial(f.kind, v, f.z, nid(f.model, f.rows))
         elif isinstance(f, _Prior):
             v = vid(f.keys_[0]); t = vt[v]
             data = f.prior.packed() if hasattr(f.prior, "packed") else np.asarray(f.prior, np.float64)

@@ -514,6 +514,61 @@ int gtg_get_gradient(gtg_handle c, double* g, int64_t n) {
   GTG_CATCH
 }
 
+// -gradientAtZero() of the caller's linearised graph: gtg_get_gradient, where every smart factor contributes as the Hessian factor it
+// is in the reference -- its landmark eliminated WITHOUT damping (SmartProjectionFactor.h:190-233): the camera blocks lose
+// F^T E (E^T E)^-1 E^T b.  Host arithmetic on the stored records of the smart measurements, in observation order; a failed track has
+// zero records and contributes nothing, a point at infinity has a 2 x 2 landmark block (third row and column zero).
+int gtg_get_graph_gradient(gtg_handle c, double* g, int64_t n) {
+  const int rc = gtg_get_gradient(c, g, n);
+  if (rc != GTG_OK || !c->n_smart) return rc;
+  GTG_TRY
+  DeviceGuard on_device(c->device);
+  const HostIndex& hi = host_index(c);
+  const bool pose = c->smart_pose;
+  const int rec = pose ? kProjRec : kSfmRec, dc = pose ? 6 : 9, a2 = 2 * dc, bo = a2 + 6;
+  const int64_t n_obs = pose ? c->f.n_proj : c->f.n_sfm, first = c->smart_obs0;
+  if (pose && proj_rows(c->f.form) != 2) throw std::logic_error("gtg_get_graph_gradient: smart measurements in a three-row range");
+  if (n_obs <= first) return GTG_OK;     // (the tracks of this graph live on other shards)
+  std::vector<double> J((size_t)rec * (n_obs - first)), V(9 * (size_t)std::max(c->n_lm, 1)), gp(3 * (size_t)std::max(c->n_lm, 1));
+  check_hip(hipMemcpy(J.data(), (pose ? c->f.proj_J.p : c->f.sfm_J.p) + (int64_t)rec * first, sizeof(double) * J.size(), hipMemcpyDeviceToHost), "D2H");
+  check_hip(hipMemcpy(V.data(), c->V.p, sizeof(double) * V.size(), hipMemcpyDeviceToHost), "D2H");
+  check_hip(hipMemcpy(gp.data(), c->gp.p, sizeof(double) * gp.size(), hipMemcpyDeviceToHost), "D2H");
+  const std::vector<int32_t>& cam = pose ? hi.proj_pose : hi.sfm_cam;
+  const std::vector<int32_t>& pt = pose ? hi.proj_point : hi.sfm_point;
+  // x_l = (E^T E)^-1 E^T b per hidden landmark: Cholesky of the 3 x 3 (or leading 2 x 2) block
+  std::vector<double> x(3 * (size_t)std::max(c->n_lm, 1), 0.0);
+  for (int64_t i = 0; i < c->n_smart; i++) {
+    const int l = c->h_lm_index[c->n_user_vars + i];
+    const double* A = V.data() + 9 * (size_t)l; const double* b = gp.data() + 3 * (size_t)l; double* xl = x.data() + 3 * (size_t)l;
+    const int d = (A[8] == 0.0 && A[2] == 0.0 && A[5] == 0.0) ? 2 : 3;
+    if (A[0] == 0.0) continue;            // a track without a point: zero records
+    double L[9] = {0};
+    bool ok = true;
+    for (int r = 0; r < d && ok; r++)
+      for (int k = 0; k <= r; k++) {
+        double s = A[3 * r + k];
+        for (int m = 0; m < k; m++) s -= L[3 * r + m] * L[3 * k + m];
+        if (k == r) { if (!(s > 0.0)) { ok = false; break; } L[3 * r + r] = std::sqrt(s); } else L[3 * r + k] = s / L[3 * k + k];
+      }
+    if (!ok) throw std::runtime_error("gtg_get_graph_gradient: the landmark block of a smart factor is not positive definite");
+    double y[3] = {0, 0, 0};
+    for (int r = 0; r < d; r++) { double s = b[r]; for (int m = 0; m < r; m++) s -= L[3 * r + m] * y[m]; y[r] = s / L[3 * r + r]; }
+    for (int r = d - 1; r >= 0; r--) { double s = y[r]; for (int m = r + 1; m < d; m++) s -= L[3 * m + r] * xl[m]; xl[r] = s / L[3 * r + r]; }
+  }
+  for (int64_t o = first; o < n_obs; o++) {
+    const double* R = J.data() + (size_t)rec * (o - first);
+    const double* xl = x.data() + 3 * (size_t)c->h_lm_index[pt[(size_t)o]];
+    double* d = g + c->h_dim_off[cam[(size_t)o]];
+    for (int r = 0; r < 2; r++) {
+      const double e = R[a2 + 3 * r] * xl[0] + R[a2 + 3 * r + 1] * xl[1] + R[a2 + 3 * r + 2] * xl[2];   // row r of E x
+      for (int k = 0; k < dc; k++) d[k] -= R[dc * r + k] * e;
+    }
+  }
+  (void)bo;
+  return GTG_OK;
+  GTG_CATCH
+}
+
 int gtg_get_hessian_diagonal(gtg_handle c, double* out, int64_t n) {
   GTG_TRY
   if (!c || !c->linearized || n != c->user_dim_size) throw std::invalid_argument("gtg_get_hessian_diagonal: linearize first / wrong size");
@@ -539,7 +594,8 @@ int gtg_get_jacobians(gtg_handle c, int type, double* out, int64_t n) {
     case GTG_FAC_GENERAL_SFM: src = c->f.sfm_J.p; cnt = (c->n_smart && !c->smart_pose ? c->smart_obs0 : c->f.n_sfm) * kSfmRec; break;   // (not the observations of smart factors)
     case GTG_FAC_PROJECTION: src = c->f.proj_J.p; cnt = (c->smart_pose ? c->smart_obs0 : c->f.n_mono) * kProjRec; break;   // (not the observations of pose-type smart factors)
     case GTG_FAC_BETWEEN_POSE3: src = c->f.between_J.p; cnt = c->f.n_between * kBetweenRec; break;
-    case GTG_FAC_PRIOR: src = c->f.prior_J.p; cnt = c->f.n_prior * kPriorRec; break;
+    case GTG_FAC_PRIOR: src = c->f.prior_J.p; cnt = c->f.n_user_prior * kPriorRec; break;   // (not the partial pose priors behind them)
+    case GTG_FAC_POSE_PARTIAL: src = c->f.prior_J.p + (int64_t)kPriorRec * c->f.n_user_prior; cnt = (c->f.n_prior - c->f.n_user_prior) * kPriorRec; break;
     case GTG_FAC_STEREO: src = c->f.proj_J.p + (int64_t)kStereoRec * c->f.n_mono; cnt = (c->f.n_cam - c->f.n_mono) * kStereoRec; break;
     case GTG_FAC_SAM: src = c->f.proj_J.p + (int64_t)kStereoRec * c->f.n_cam; cnt = (c->f.n_proj - c->f.n_cam) * kStereoRec; break;
     default: throw std::invalid_argument("unknown factor type");

@@ -151,6 +151,15 @@ struct FactorTables {
   DevBuf<int32_t> prior_var, prior_noise;
   DevBuf<int64_t> prior_off;
   DevBuf<double> prior_data, prior_J;
+  // PoseTranslationPrior / PoseRotationPrior <Pose3 | Pose2> (GTG_FAC_POSE_PARTIAL): the factors [n_user_prior, n_prior) of the prior
+  // range, behind the caller's PriorFactors.  Their records are prior records of the pose's tangent dimension with the rows they do not
+  // have exactly 0, so every reader of prior_var / prior_J (assembly, linear error, Hessian diagonal, PCG, the incidence lists) sees more
+  // priors and nothing else; prior_off / prior_data have no entry for them.  Only k_lin_pose_partial and k_error_pose_partial evaluate
+  // them: partial_kind[i - n_user_prior] GTG_POSE_PARTIAL_*, partial_z[9 (i - n_user_prior)] the measurement.  Without such factors
+  // n_user_prior == n_prior and both buffers are empty.
+  int64_t n_user_prior = 0;
+  DevBuf<int32_t> partial_kind;
+  DevBuf<double> partial_z;
 };
 
 }  // namespace gt

@@ -482,6 +482,81 @@ GT_HD double prior_error(int vtype, const double* x, const double* z, const Nois
   return factor_loss(n, e);
 }
 
+// ---- PoseTranslationPrior<POSE> / PoseRotationPrior<POSE>, POSE = Pose3 | Pose2 -----------------
+// The absolute fix of part of a pose (slam/PoseTranslationPrior.h:65-77, slam/PoseRotationPrior.h:81-90).  The kind and the variable's
+// type give the form:
+//   translation, Pose3: r = t - z (traits<Point3>::Local(z, t)), H = [0 | R]
+//   rotation,    Pose3: r = Z.localCoordinates(R) = SO3::Logmap(Z^T R) (GTSAM_ROT3_EXPMAP), H = [I | 0] -- the identity block the
+//                       reference writes, NOT the derivative of Logmap
+//   translation, Pose2: r = t - z, H = [[c -s], [s c] | 0]
+//   rotation,    Pose2: r = theta of Rot2(c_z, -s_z) * Rot2(c, s) (Rot2::localCoordinates: between, then atan2; the product goes through
+//                       Rot2::fromCosSin, which re-normalises only beyond 1e-10, Rot2.cpp:56-64), H = [0 0 1]
+// then b = -r and WhitenSystem on the whole system.  z: 9 doubles per factor (the measured Point3 | Rot3 row-major | Point2 | c_z, s_z),
+// the rest 0.  The record is the PRIOR record of the pose's tangent dimension D ([A D x D | b at 81]) with the factor's R rows first and
+// every other entry exactly 0.  Contraction is off where t - z and the entries of Z^T R are formed: the Taylor branch of Logmap sees
+// differences of entries that are equal up to rounding, and the record must not depend on which compiler inlined this.
+enum { kPartialTranslation = 0, kPartialRotation = 1 };   // = GTG_POSE_PARTIAL_*
+constexpr int kPosePartialZ = 9;                          // measurement doubles per factor
+GT_HD int pose_partial_rows(int kind, int vtype) { return vtype == 0 ? 3 : kind == kPartialTranslation ? 2 : 1; }
+// FORM: 0 translation / Pose3, 1 rotation / Pose3, 2 translation / Pose2, 3 rotation / Pose2
+constexpr int pose_partial_form_rows(int form) { return form < 2 ? 3 : form == 2 ? 2 : 1; }
+template <int FORM>
+GT_HD void pose_partial_residual(const double* x, const double* z, double* r) {
+  _Pragma("clang fp contract(off)")
+  if (FORM == 0) {
+    for (int k = 0; k < 3; k++) r[k] = x[9 + k] - z[k];
+  } else if (FORM == 1) {
+    double M[9];   // Z^T R (Rot3::between)
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) M[3 * i + j] = z[i] * x[j] + z[3 + i] * x[3 + j] + z[6 + i] * x[6 + j];
+    so3_logmap(M, r);
+  } else if (FORM == 2) {
+    r[0] = x[0] - z[0]; r[1] = x[1] - z[1];
+  } else {
+    const double c = cos(x[2]), s = sin(x[2]), cz = z[0], sz = -z[1];   // Rot2::inverse of the measurement
+    double cc = cz * c - sz * s, ss = sz * c + cz * s;                   // Rot2::operator* (Rot2.h:116-118)
+    rot2_normalize(cc, ss);
+    r[0] = atan2(ss, cc);
+  }
+}
+template <int FORM>
+GT_HD void pose_partial_linearize_form(const double* x, const double* z, const NoiseRef& n, double* J) {
+  constexpr int R = pose_partial_form_rows(FORM), D = FORM < 2 ? 6 : 3;
+  double r[R];
+  pose_partial_residual<FORM>(x, z, r);
+  for (int i = 0; i < kPriorRec; i++) J[i] = 0.0;
+  if (FORM == 0) { for (int i = 0; i < 3; i++) for (int k = 0; k < 3; k++) J[6 * i + 3 + k] = x[3 * i + k]; }
+  else if (FORM == 1) { for (int i = 0; i < 3; i++) J[6 * i + i] = 1.0; }
+  else if (FORM == 2) { const double c = cos(x[2]), s = sin(x[2]); J[0] = c; J[1] = -s; J[3] = s; J[4] = c; }
+  else J[2] = 1.0;
+  for (int i = 0; i < R; i++) J[81 + i] = -r[i];
+  whiten_cols<R>(n.kind, n.data, J, D);
+  whiten_cols<R>(n.kind, n.data, J + 81, 1);
+  if (n.rkind) {
+    const double w = reweight_factor(n, J + 81, R);
+    for (int i = 0; i < R * D; i++) J[i] *= w;
+    for (int i = 0; i < R; i++) J[81 + i] *= w;
+  }
+}
+GT_HD void pose_partial_linearize(int kind, int vtype, const double* x, const double* z, const NoiseRef& n, double* J) {
+  if (vtype == 0) { if (kind == kPartialTranslation) pose_partial_linearize_form<0>(x, z, n, J); else pose_partial_linearize_form<1>(x, z, n, J); }
+  else { if (kind == kPartialTranslation) pose_partial_linearize_form<2>(x, z, n, J); else pose_partial_linearize_form<3>(x, z, n, J); }
+}
+template <int FORM>
+GT_HD double pose_partial_error_form(const double* x, const double* z, const NoiseRef& n) {
+  constexpr int R = pose_partial_form_rows(FORM);
+  double r[R];
+  pose_partial_residual<FORM>(x, z, r);
+  whiten_cols<R>(n.kind, n.data, r, 1);
+  double e = 0.0;
+  for (int i = 0; i < R; i++) e += r[i] * r[i];
+  return factor_loss(n, e);
+}
+GT_HD double pose_partial_error(int kind, int vtype, const double* x, const double* z, const NoiseRef& n) {
+  if (vtype == 0) return kind == kPartialTranslation ? pose_partial_error_form<0>(x, z, n) : pose_partial_error_form<1>(x, z, n);
+  return kind == kPartialTranslation ? pose_partial_error_form<2>(x, z, n) : pose_partial_error_form<3>(x, z, n);
+}
+
 // ---- a pose named several times in one smart track (SmartProjectionRigFactor) ------------------------------------
 // The reference builds that factor's Hessian on the UNIQUE keys (CameraSet::SchurComplementAndRearrangeBlocks,
 // slam/SmartProjectionRigFactor.h:312-322): the sightings o_0 .. o_{n-1} of one track made from one pose are one block row

@@ -201,6 +201,25 @@ __global__ __launch_bounds__(kBlock) void k_lin_prior(int64_t n, const int32_t* 
   }
 }
 
+// The partial pose priors (PoseTranslationPrior / PoseRotationPrior on a POSE3 or POSE2 variable): the factors [first, first + n) of
+// the prior range, behind the caller's PriorFactors that k_lin_prior linearises.  One factor per lane, grid-stride; the record is a
+// prior record (kPriorRec) with the rows the factor does not have exactly 0.  Launched only for a graph with such factors.
+__global__ __launch_bounds__(kBlock) void k_lin_pose_partial(int64_t n, int64_t first, const int32_t* __restrict__ var,
+    const int32_t* __restrict__ kind, const double* __restrict__ z, const int32_t* __restrict__ nz,
+    const int32_t* __restrict__ var_type, const double* __restrict__ values,
+    const int64_t* __restrict__ val_off, NoiseTab nt, double* __restrict__ J) {
+  for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    const int v = var[first + i];
+    const int ni = nz[first + i];
+    const int vt = var_type[v];
+    const double* xp = values + val_off[v];
+    double x[12], zz[kPosePartialZ];
+    for (int k = 0; k < 12; k++) x[k] = (vt == 0 || k < 3) ? xp[k] : 0.0;   // (a POSE2 holds three doubles)
+    for (int k = 0; k < kPosePartialZ; k++) zz[k] = z[kPosePartialZ * i + k];
+    pose_partial_linearize(kind[i], vt, x, zz, nt.ref(ni), J + (int64_t)kPriorRec * (first + i));
+  }
+}
+
 // ---- nonlinear error --------------------------------------------------------------------------------
 struct ErrArgs {
   int64_t n_sfm, n_proj, n_between, n_prior;
@@ -308,6 +327,27 @@ __global__ __launch_bounds__(kBlock) void k_error_rows3(int64_t n, int64_t n_mon
       if (i < n_mono) acc += proj_error(T, K, si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]));
       else acc += stereo_error(T, K, baseline[ci], si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]));
     }
+  }
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// The partial pose priors (the range of k_lin_pose_partial): k_error<kErrRest> is launched with the caller's PriorFactors alone.
+// Fixed slices per block as above; the block partials go behind those of the other error kernels, where k_final_sum picks them up.
+__global__ __launch_bounds__(kBlock) void k_error_pose_partial(int64_t n, int64_t first, const int32_t* __restrict__ var,
+    const int32_t* __restrict__ kind, const double* __restrict__ z, const int32_t* __restrict__ nz,
+    const int32_t* __restrict__ var_type, const double* __restrict__ values, const int64_t* __restrict__ val_off, NoiseTab nt,
+    double* __restrict__ partials) {
+  double acc = 0.0;
+  const int64_t tid = blockIdx.x * (int64_t)kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = tid; i < n; i += stride) {
+    const int v = var[first + i];
+    const int vt = var_type[v];
+    const double* xp = values + val_off[v];
+    double x[12], zz[kPosePartialZ];
+    for (int k = 0; k < 12; k++) x[k] = (vt == 0 || k < 3) ? xp[k] : 0.0;   // (a POSE2 holds three doubles)
+    for (int k = 0; k < kPosePartialZ; k++) zz[k] = z[kPosePartialZ * i + k];
+    acc += pose_partial_error(kind[i], vt, x, zz, nt.ref(nz[first + i]));
   }
   const double s = block_sum(acc);
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
@@ -685,10 +725,14 @@ void launch_linearize(gtg_context& c) {
     hipLaunchKernelGGL(k_lin_between, dim3(grid_for(f.n_between)), dim3(kBlock), 0, c.stream, f.n_between,
                        f.between_v1.p, f.between_v2.p, f.between_z.p, f.between_noise.p, c.var_type.p, c.values.p,
                        c.val_off.p, nt, f.between_J.p);
-  if (f.n_prior)
-    hipLaunchKernelGGL(k_lin_prior, dim3(grid_for(f.n_prior)), dim3(kBlock), 0, c.stream, f.n_prior, f.prior_var.p,
+  if (f.n_user_prior)
+    hipLaunchKernelGGL(k_lin_prior, dim3(grid_for(f.n_user_prior)), dim3(kBlock), 0, c.stream, f.n_user_prior, f.prior_var.p,
                        f.prior_off.p, f.prior_data.p, f.prior_noise.p, c.var_type.p, c.values.p, c.val_off.p, nt,
                        f.prior_J.p);
+  if (f.n_prior > f.n_user_prior)   // the partial pose priors behind them (context.h)
+    hipLaunchKernelGGL(k_lin_pose_partial, dim3(grid_for(f.n_prior - f.n_user_prior)), dim3(kBlock), 0, c.stream, f.n_prior - f.n_user_prior,
+                       f.n_user_prior, f.prior_var.p, f.partial_kind.p, f.partial_z.p, f.prior_noise.p, c.var_type.p, c.values.p,
+                       c.val_off.p, nt, f.prior_J.p);
   check_hip(hipGetLastError(), "linearize");
 }
 
@@ -721,7 +765,8 @@ void launch_sfm_records(gtg_context& c, double* dst) {
 void launch_error(gtg_context& c, const double* values, int slot, const double* gate) {
   auto& f = c.f;
   const bool three = proj_rows(f.form) == 3;   // (its projection range goes to k_error_rows3, the third group of block partials)
-  ErrArgs a{f.n_sfm, three ? 0 : f.n_proj, f.n_between, f.n_prior,
+  const int64_t n_partial = f.n_prior - f.n_user_prior;   // (the partial pose priors go to k_error_pose_partial, the last group of block partials)
+  ErrArgs a{f.n_sfm, three ? 0 : f.n_proj, f.n_between, f.n_user_prior,
             f.sfm_cam.p, f.sfm_point.p, f.sfm_noise.p, f.sfm_z.p,
             f.proj_pose.p, f.proj_point.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.proj_z.p, f.calib.p, f.sensor.p,
             f.between_v1.p, f.between_v2.p, f.between_noise.p, f.between_z.p,
@@ -730,8 +775,8 @@ void launch_error(gtg_context& c, const double* values, int slot, const double* 
   ErrArgs a_sfm = a;
   if (c.smart_pose) a_sfm.smart_of = nullptr;
   // the GeneralSFM factors and the other types in a kernel each, their block partials one behind the other
-  const int64_t nrest = std::max(a.n_proj, std::max(f.n_between, f.n_prior));
-  const int gmax = three ? kMaxBlocks / 4 : kMaxBlocks / 2;
+  const int64_t nrest = std::max(a.n_proj, std::max(f.n_between, f.n_user_prior));
+  const int gmax = three || n_partial ? kMaxBlocks / 4 : kMaxBlocks / 2;
   const int g1 = f.n_sfm ? std::min(grid_for(f.n_sfm), gmax) : 0, g2 = (nrest || !g1) ? std::min(grid_for(nrest), gmax) : 0;
   const int g3 = three && f.n_proj ? std::min(grid_for(f.n_proj), gmax) : 0;
   const auto k_rest = f.form == ProjForm::Rows2Smart ? k_error<kErrRest | kErrSmartProj> : k_error<kErrRest>;
@@ -741,7 +786,10 @@ void launch_error(gtg_context& c, const double* values, int slot, const double* 
   if (g3) hipLaunchKernelGGL(k_three, dim3(g3), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.n_cam, f.proj_pose.p, f.proj_point.p,
                              f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_baseline.p, f.sensor.p,
                              f.sam_kind.p, f.sam_z.p, values, c.val_off.p, noise_tab(c), c.partials.p + g1 + g2);
-  hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(kBlock), 0, c.stream, c.partials.p, g1 + g2 + g3, 1, c.scalars.p, slot);
+  const int g4 = n_partial ? std::min(grid_for(n_partial), gmax) : 0;
+  if (g4) hipLaunchKernelGGL(k_error_pose_partial, dim3(g4), dim3(kBlock), 0, c.stream, n_partial, f.n_user_prior, f.prior_var.p, f.partial_kind.p,
+                             f.partial_z.p, f.prior_noise.p, c.var_type.p, values, c.val_off.p, noise_tab(c), c.partials.p + g1 + g2 + g3);
+  hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(kBlock), 0, c.stream, c.partials.p, g1 + g2 + g3 + g4, 1, c.scalars.p, slot);
   if (c.n_smart && c.smart_pose)
     hipLaunchKernelGGL(k_error_smart_pose_at_infinity, dim3(1), dim3(kBlock), 0, c.stream, f.n_proj - c.smart_obs0, c.smart_obs0,
                        smart_proj_tabs(c, c.smart_status.p), values, noise_tab(c), gate, c.scalars.p, slot);
@@ -782,7 +830,7 @@ namespace {
 void prewarm_factors(int) {
   using namespace gt;
   prewarm_kernels({(const void*)k_lin_sfm, (const void*)k_lin_proj<false>, (const void*)k_lin_proj<true>, (const void*)k_lin_rows3<false>, (const void*)k_lin_rows3<true>,
-                   (const void*)k_lin_between, (const void*)k_lin_prior, (const void*)k_error<kErrSfm>, (const void*)k_error<kErrRest>,
+                   (const void*)k_lin_between, (const void*)k_lin_prior, (const void*)k_lin_pose_partial, (const void*)k_error_pose_partial, (const void*)k_error<kErrSfm>, (const void*)k_error<kErrRest>,
                    (const void*)k_error<kErrRest | kErrSmartProj>, (const void*)k_error_rows3<false>, (const void*)k_error_rows3<true>, (const void*)k_final_sum,
                    (const void*)k_linear_error<true, 2>, (const void*)k_linear_error<false, 2>, (const void*)k_linear_error<false, 3>, (const void*)k_retract,
                    (const void*)k_sumsq, (const void*)k_smart_triangulate<false, false>, (const void*)k_smart_triangulate<true, false>,

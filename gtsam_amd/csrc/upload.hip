@@ -19,6 +19,7 @@
 namespace gt {
 namespace {
 static_assert(kSamBearingRange == GTG_SAM_BEARING_RANGE && kSamRange == GTG_SAM_RANGE && kSamBearing == GTG_SAM_BEARING, "factors.h names the sam kinds of the C ABI");
+static_assert(kPartialTranslation == GTG_POSE_PARTIAL_TRANSLATION && kPartialRotation == GTG_POSE_PARTIAL_ROTATION, "factors.h names the partial pose prior kinds of the C ABI");
 
 // Smart factors become what the rest of the library already knows: a hidden POINT3 variable per factor behind the caller's
 // variables and one observation per measurement behind the caller's -- a GeneralSFM observation for a camera-type factor
@@ -494,6 +495,28 @@ void upload_priors(gtg_context& c, HostIndex& hi, const gtg_problem& p, const Sh
     const double* d = p.prior_data + p.prior_off[i];
     for (int k = 0; k < storage_size(p.var_type[v]); k++) data.push_back(d[k]);
   }
+  f.n_user_prior = (int64_t)var.size();
+  // the partial pose priors (PoseTranslationPrior / PoseRotationPrior) join the prior range behind the caller's priors, the way the
+  // smart measurements join the projection range: the symbolic analysis, the assembly, the linear error, PCG and the shard filter see
+  // more priors and nothing else.  Dealt round-robin like the other non-landmark factors.
+  const int64_t n_partial = p.n_pose_partial > 0 ? p.n_pose_partial : 0;
+  if (n_partial && (!p.pose_partial_kind || !p.pose_partial_var || !p.pose_partial_z || !p.pose_partial_noise))
+    throw std::invalid_argument("partial pose prior tables missing");
+  std::vector<int32_t> partial_kind; std::vector<double> partial_z;
+  for (int64_t i = 0; i < n_partial; i++) {
+    const int kind = p.pose_partial_kind[i], v = p.pose_partial_var[i];
+    if (kind != GTG_POSE_PARTIAL_TRANSLATION && kind != GTG_POSE_PARTIAL_ROTATION)
+      throw std::invalid_argument("partial pose prior: unknown pose_partial_kind (GTG_POSE_PARTIAL_TRANSLATION or GTG_POSE_PARTIAL_ROTATION)");
+    const char* what = kind == GTG_POSE_PARTIAL_TRANSLATION ? "PoseTranslationPrior" : "PoseRotationPrior";
+    if (v < 0 || v >= p.n_vars || (p.var_type[v] != GTG_VAR_POSE3 && p.var_type[v] != GTG_VAR_POSE2))
+      throw std::invalid_argument(std::string(what) + ": its key must be a POSE3 or POSE2 variable in Values");
+    check_noise(p, p.pose_partial_noise[i], pose_partial_rows(kind, p.var_type[v]), what);
+    if (own.n_shards > 1 && !own.owns_round_robin(i)) continue;
+    var.push_back(v); nz.push_back(p.pose_partial_noise[i]);
+    partial_kind.push_back(kind);
+    for (int k = 0; k < kPosePartialZ; k++) partial_z.push_back(p.pose_partial_z[kPosePartialZ * i + k]);
+  }
+  if (n_partial) { up(f.partial_kind, partial_kind, c.stream); up(f.partial_z, partial_z, c.stream); } else { f.partial_kind.free(); f.partial_z.free(); }
   f.n_prior = (int64_t)var.size();
   up(f.prior_var, var, c.stream); up(f.prior_noise, nz, c.stream); up(f.prior_off, poff, c.stream); up(f.prior_data, data, c.stream);
   f.prior_J.alloc(std::max<size_t>((size_t)kPriorRec * f.n_prior, 1));

@@ -1063,3 +1063,165 @@ def landmark_slam3d_graph(n_poses=40, n_points=300, seed=11, views=10, bearing_s
     for j in range(n_points):
         initial.insert(L(j), pts[j] + rng.normal(0, 0.2, 3))
     return graph, initial
+
+
+# ---- partial pose priors: PoseTranslationPrior / PoseRotationPrior <Pose3 | Pose2> -----------------------------------------------
+# The scenes the fixtures of tests/golden/make_golden_pose_partial.py are recorded on.  No graph has a full PriorFactor: the gauge is
+# fixed by position and attitude fixes alone.
+def _partial_noise(A, rng, k, dim, scale):
+    """The k-th partial prior's noise model: Unit, Isotropic, Diagonal, Gaussian in turn (`scale`: the size of a sigma)."""
+    nm = A.noiseModel
+    mode = k % 4
+    if mode == 0:
+        return nm.Unit.Create(dim)
+    if mode == 1:
+        return nm.Isotropic.Sigma(dim, scale, False)
+    if mode == 2:
+        return nm.Diagonal.Sigmas(scale * (1.0 + 0.5 * np.arange(dim)), False)
+    R = np.triu(rng.normal(0, 0.2 / scale, (dim, dim))) + np.diag(rng.uniform(0.8, 1.6, dim) / scale)   # an upper-triangular sqrt information
+    return nm.Gaussian.SqrtInformation(R, False)
+
+
+def pose_partial_graph3d(n_poses=97, n_closures=23, seed=0):
+    """A Pose3 pose graph anchored by partial priors alone: an odometry chain with drift (the initial values are the dead-reckoned
+    odometry), `n_closures` loop closures, and 131 partial priors -- 95 PoseTranslationPrior3D (every pose but each eighth; a second
+    one on every tenth pose) and 36 PoseRotationPrior3D (every third pose and poses 1, 50, 70) -- with Unit, Isotropic, Diagonal and
+    Gaussian models in turn; a Huber model on the translation prior of pose 12 and a Cauchy model on that of pose 33, whose measurement
+    is a gross outlier (30 m off).  Pose 0 carries two translation priors and a rotation prior.  The rotation prior of pose 1 measures
+    the initial rotation of that pose bit for bit (the Taylor branch of SO3::Logmap), that of pose 50 is pi - 5e-5 away from it with a
+    loose sigma (the near-pi branch); the others take the acos branch.
+    Graph order: between factors, translation priors, rotation priors.  Returns (graph, initial values, info) with info["rot_taylor"],
+    info["rot_near_pi"], info["outlier"], info["huber"] the indices of those factors among the partial priors."""
+    from . import api as A
+    rng = np.random.default_rng(seed)
+    nm = A.noiseModel
+    X = A.symbol_shorthand.X
+    # truth: a slowly turning, climbing path
+    step_w = np.stack([0.01 * rng.normal(size=n_poses), 0.01 * rng.normal(size=n_poses), 0.11 + 0.02 * rng.normal(size=n_poses)], 1)
+    step_t = np.stack([1.0 + 0.05 * rng.normal(size=n_poses), 0.05 * rng.normal(size=n_poses), 0.03 + 0.01 * rng.normal(size=n_poses)], 1)
+    dR = _rodrigues(step_w)
+    R, t = [np.eye(3)], [np.zeros(3)]
+    for i in range(1, n_poses):
+        R.append(R[-1] @ dR[i]); t.append(t[-1] + R[-2] @ step_t[i])
+    R, t = np.array(R), np.array(t)
+    edges = [(i, i + 1) for i in range(n_poses - 1)]
+    while len(edges) < n_poses - 1 + n_closures:
+        a, b = sorted(int(x) for x in rng.integers(0, n_poses, 2))
+        if b - a > 5 and (a, b) not in edges:
+            edges.append((a, b))
+    graph, initial = A.NonlinearFactorGraph(), A.Values()
+    n_odo = nm.Diagonal.Sigmas([0.01, 0.01, 0.015, 0.05, 0.05, 0.08], False)
+    n_loop = nm.Isotropic.Sigma(6, 0.1, False)
+    zs = []
+    for k, (a, b) in enumerate(edges):
+        zR = R[a].T @ R[b] @ _rodrigues(rng.normal(0, 0.01, (1, 3)))[0]
+        zt = R[a].T @ (t[b] - t[a]) + rng.normal(0, 0.05, 3)
+        zs.append((zR, zt))
+        graph.add(A.BetweenFactorPose3(X(a), X(b), A.Pose3(A.Rot3(zR), zt), n_odo if k < n_poses - 1 else n_loop))
+    # the initial values: the odometry composed from pose 0 (drift), pose 0 itself a little off the truth
+    Ri, ti = [R[0] @ _rodrigues(np.array([[0.02, -0.01, 0.03]]))[0]], [t[0] + np.array([0.3, -0.2, 0.1])]
+    for i in range(n_poses - 1):
+        zR, zt = zs[i]
+        ti.append(ti[-1] + Ri[-1] @ zt); Ri.append(Ri[-1] @ zR)
+    for i in range(n_poses):
+        initial.insert(X(i), A.Pose3(A.Rot3(Ri[i]), ti[i]))
+    info, k = {}, 0
+    trans = [i for i in range(n_poses) if i % 8 != 7] + list(range(0, n_poses, 10))
+    for i in trans:
+        z = t[i] + rng.normal(0, 0.3, 3)
+        model = _partial_noise(A, rng, k, 3, 0.5)
+        if k == 12:
+            model = nm.Robust.Create(nm.mEstimator.Huber.Create(1.345), nm.Isotropic.Sigma(3, 0.4, False)); info["huber"] = k
+        if k == 33:
+            model = nm.Robust.Create(nm.mEstimator.Cauchy.Create(1.0), nm.Diagonal.Sigmas([0.4, 0.5, 0.6], False))
+            z = z + np.array([30.0, -4.0, 2.0]); info["outlier"] = k
+        graph.add(A.PoseTranslationPrior3D(X(i), A.Point3(*z), model) if k % 2 else A.PoseTranslationPrior3D(X(i), A.Pose3(A.Rot3(), z), model))
+        k += 1
+    for i in sorted(list(range(0, n_poses, 3)) + [1, 50, 70]):
+        zR = R[i] @ _rodrigues(rng.normal(0, 0.02, (1, 3)))[0]
+        model = _partial_noise(A, rng, k, 3, 0.05)
+        if i == 1:
+            zR = Ri[i].copy(); info["rot_taylor"] = k
+        if i == 50:
+            axis = np.array([0.6, -0.48, 0.64])
+            zR = Ri[i] @ _rodrigues((np.pi - 5e-5) * axis[None])[0]
+            model = nm.Isotropic.Sigma(3, 10.0, False); info["rot_near_pi"] = k
+        graph.add(A.PoseRotationPrior3D(X(i), A.Rot3(zR), model) if k % 2 else A.PoseRotationPrior3D(X(i), A.Pose3(A.Rot3(zR), np.zeros(3)), model))
+        k += 1
+    return graph, initial, info
+
+
+def pose_partial_vo_graph(seed=0, n_poses=16):
+    """A smart-VO graph anchored by partial priors alone: smart_pose_graph's scene (SmartProjectionPose3Factor tracks, six explicit
+    Point3 landmarks with GenericProjectionFactors, a BetweenFactor chain, NO full prior) with a PoseTranslationPrior3D on every fifth
+    pose and one PoseRotationPrior3D on the first.  Graph order: smart, projection, between factors, then the partial priors.
+    Returns (graph, initial values, info of smart_pose_graph)."""
+    from . import api as A
+    prm = A.SmartProjectionParams()
+    prm.degeneracyMode = 1
+    graph, initial, info = smart_pose_graph(n_poses=n_poses, n_tracks=67, seed=seed, arc=0.5, radius=8.0, box=(2.0, 1.5, 2.0),
+                                            K=(520.0, 515.0, 0.3, 320.0, 240.0), sigma=1.5, pixel_noise=0.7, see=0.6, explicit_landmarks=6,
+                                            between_chain=True, priors=(), init_noise=(0.004, 0.02), params=prm)
+    rng = np.random.default_rng(seed + 1000)
+    nm = A.noiseModel
+    X = A.symbol_shorthand.X
+    # (the scene returns the perturbed initial poses: the fixes are taken around them, a few centimetres and a degree off)
+    for k, i in enumerate(range(0, n_poses, 5)):
+        T = initial.at(X(i))
+        graph.add(A.PoseTranslationPrior3D(X(i), A.Point3(*(T.translation() + rng.normal(0, 0.03, 3))), _partial_noise(A, rng, k + 1, 3, 0.05)))
+    T = initial.at(X(0))
+    graph.add(A.PoseRotationPrior3D(X(0), A.Rot3(T.rotation().matrix() @ _rodrigues(rng.normal(0, 0.01, (1, 3)))[0]), nm.Diagonal.Sigmas([0.02, 0.03, 0.02], False)))
+    return graph, initial, info
+
+
+def pose_partial_graph2d(n_poses=83, n_closures=9, seed=0):
+    """A Pose2 pose graph anchored by partial priors alone: a chain once round a loop with `n_closures` loop closures, 31
+    PoseTranslationPrior2D (every third pose and poses 1, 2, 4) and 15 PoseRotationPrior2D (every sixth pose and the wrap pose).  The
+    wrap pose (info["wrap_pose"]; its factor info["wrap"] among the partial priors) starts at theta = -3.1 and its rotation prior
+    measures 3.1: the residual is 2 pi - 6.2 = 0.083, not -6.2.  Returns (graph, initial values, info)."""
+    from . import api as A
+    rng = np.random.default_rng(seed)
+    nm = A.noiseModel
+    X = A.symbol_shorthand.X
+    th = 2.0 + 2 * np.pi * np.arange(n_poses) / n_poses + 0.02 * rng.normal(size=n_poses)
+    th = np.arctan2(np.sin(th), np.cos(th))
+    xy = np.cumsum(np.stack([np.cos(th), np.sin(th)], 1) * 0.8, 0)
+
+    def between(a, b):
+        c, s = np.cos(th[a]), np.sin(th[a])
+        d = xy[b] - xy[a]
+        dth = th[b] - th[a]
+        return np.array([c * d[0] + s * d[1], -s * d[0] + c * d[1], np.arctan2(np.sin(dth), np.cos(dth))])
+
+    edges = [(i, i + 1) for i in range(n_poses - 1)] + [(n_poses - 1, 0)]
+    while len(edges) < n_poses + n_closures:
+        a, b = sorted(int(x) for x in rng.integers(0, n_poses, 2))
+        if b - a > 4 and (a, b) not in edges:
+            edges.append((a, b))
+    graph, initial = A.NonlinearFactorGraph(), A.Values()
+    n_odo = nm.Diagonal.Sigmas([0.05, 0.05, 0.02], False)
+    for a, b in edges:
+        z = between(a, b) + rng.normal(0, [0.03, 0.03, 0.01])
+        graph.add(A.BetweenFactorPose2(X(a), X(b), A.Pose2(*z), n_odo))
+    wrap_pose = int(np.argmin(np.abs(np.abs(th) - np.pi)))
+    v0 = np.concatenate([xy + rng.normal(0, 0.15, xy.shape), (th + rng.normal(0, 0.05, n_poses))[:, None]], 1)
+    v0[:, 2] = np.arctan2(np.sin(v0[:, 2]), np.cos(v0[:, 2]))
+    v0[wrap_pose, 2] = -3.1
+    for i in range(n_poses):
+        initial.insert(X(i), A.Pose2(*v0[i]))
+    info, k = {"wrap_pose": wrap_pose}, 0
+    for i in sorted(set(range(0, n_poses, 3)) | {1, 2, 4}):
+        z = xy[i] + rng.normal(0, 0.1, 2)
+        model = _partial_noise(A, rng, k, 2, 0.2)
+        graph.add(A.PoseTranslationPrior2D(X(i), A.Point2(*z), model) if k % 2 else A.PoseTranslationPrior2D(X(i), A.Pose2(z[0], z[1], 0.3), model))
+        k += 1
+    for i in sorted(set(range(0, n_poses, 6)) | {wrap_pose}):
+        ang = th[i] + rng.normal(0, 0.02)
+        model = nm.Unit.Create(1) if k % 3 == 0 else nm.Isotropic.Sigma(1, 0.05, False)
+        if i == wrap_pose:
+            ang = 3.1; info["wrap"] = k
+        form = k % 3
+        pose_z = ang if form == 0 else A.Rot2.fromAngle(ang) if form == 1 else A.Pose2(0.0, 0.0, ang)
+        graph.add(A.PoseRotationPrior2D(X(i), pose_z, model))
+        k += 1
+    return graph, initial, info

@@ -24,6 +24,8 @@
 #include <gtsam/slam/StereoFactor.h>
 #include <gtsam/sam/BearingFactor.h>
 #include <gtsam/sam/BearingRangeFactor.h>
+#include <gtsam/slam/PoseRotationPrior.h>
+#include <gtsam/slam/PoseTranslationPrior.h>
 #include <gtsam/sam/RangeFactor.h>
 
 #include <gtsam/config.h>
@@ -79,6 +81,11 @@ typedef GenericStereoFactor<Pose3, Point3> StereoFactor;
 typedef BearingRangeFactor<Pose3, Point3> SamBearingRangeFactor;   // gtsam/sam: wrapped as BearingRangeFactor3D, RangeFactor3D, BearingFactor3D
 typedef RangeFactor<Pose3, Point3> SamRangeFactor;
 typedef BearingFactor<Pose3, Point3> SamBearingFactor;
+// partial pose priors (gtsam/slam): wrapped as PoseTranslationPrior3D / 2D and PoseRotationPrior3D / 2D
+typedef PoseTranslationPrior<Pose3> TranslationPrior3;
+typedef PoseRotationPrior<Pose3> RotationPrior3;
+typedef PoseTranslationPrior<Pose2> TranslationPrior2;
+typedef PoseRotationPrior<Pose2> RotationPrior2;
 typedef SmartProjectionFactor<SfmCamera> SmartFactor;   // the factor of timing/timeSFMBALsmart.cpp
 // The smart factor keeps its noise model and its parameters protected and has no accessor for them; a class derived from it may
 // name them, and the pointers to member it forms are ordinary pointers to members of the factor (a maintainer binding this into
@@ -181,7 +188,8 @@ void unpack(int32_t t, const double* p, Value& v) {
 }
 // ---- Jacobian records (gtg_get_jacobians): one whitened [A1 | A2 | b] per factor, row-major blocks at fixed offsets; the record's width follows
 // the factor type, the block sizes the factor's first variable (Pose2: 3x3 blocks inside the record of the Pose3 factor)
-const int64_t kRecordWidth[6] = {26, 20, 78, 90, 30, 30};   // by GTG_FAC_*
+constexpr int kFacTypes = 7;
+const int64_t kRecordWidth[kFacTypes] = {26, 20, 78, 90, 30, 30, 90};   // by GTG_FAC_*
 struct RecordLayout { int rows, nblk, boff[2], bcols[2], rhs; int64_t width; };
 template <class F> RecordLayout recordLayout(int32_t fac, F&& firstVarType) {   // firstVarType(): GTG_VAR_* of the factor's first variable, asked only where the layout depends on it
   const int64_t w = kRecordWidth[fac];
@@ -191,19 +199,19 @@ template <class F> RecordLayout recordLayout(int32_t fac, F&& firstVarType) {   
   if (fac == GTG_FAC_SAM) return {3, 2, {0, 18}, {tangentDim(GTG_VAR_POSE3), 3}, 27, w};   // (rows: the caller puts the kind's 3, 1 or 2 -- Impl::layoutOf)
   const int d = tangentDim(firstVarType());
   if (fac == GTG_FAC_BETWEEN_POSE3) return {d, 2, {0, 36}, {d, d}, 72, w};
-  return {d, 1, {0, 0}, {d, 0}, 81, w};
+  return {d, 1, {0, 0}, {d, 0}, 81, w};   // PRIOR, and POSE_PARTIAL (rows: the caller puts the factor's 3, 2 or 1 -- Impl::layoutOf)
 }
 typedef std::vector<std::pair<int32_t, int64_t>> FactorMap;   // factor of graph_ -> (GTG_FAC_*, index in that type's table); (-1, 0): null; (-2, i): smart factor i
 // The device's current records, one buffer per GTG_FAC_* (null and smart factors have none: a smart factor's linearisation is a Hessian factor the device never forms)
 struct Records {
-  std::vector<double> rec[6];
+  std::vector<double> rec[kFacTypes];
   const double* of(const std::pair<int32_t, int64_t>& tf) const { return rec[tf.first].data() + tf.second * kRecordWidth[tf.first]; }
 };
 Records fetchRecords(gtg_handle h, const FactorMap& fac_map) {
   Records out;
-  int64_t count[6] = {0, 0, 0, 0, 0, 0};
+  int64_t count[kFacTypes] = {0};
   for (const auto& tf : fac_map) if (tf.first >= 0) count[tf.first]++;
-  for (int t = 0; t < 6; t++) {
+  for (int t = 0; t < kFacTypes; t++) {
     if (!count[t]) continue;
     out.rec[t].resize((size_t)(count[t] * kRecordWidth[t]));
     check(gtg_get_jacobians(h, t, out.rec[t].data(), (int64_t)out.rec[t].size()), "gtg_get_jacobians");
@@ -272,9 +280,11 @@ struct GpuLevenbergMarquardtOptimizer::Impl {
   ~Impl() { if (h) gtg_destroy(h); }
   void takeScalars(const State& s) { error = s.error; lambda = s.lambda; factor = s.currentFactor; iterations = s.iterations; inner = s.totalNumberInnerIterations; }
   std::vector<int32_t> sam_kind;         // GTG_SAM_* by row of the sam table: a bearing / range record has its kind's 3, 1 or 2 rows
+  std::vector<int32_t> pp_kind;          // GTG_POSE_PARTIAL_* by row of the partial pose prior table: 3 rows on a Pose3, 2 or 1 on a Pose2
   RecordLayout layoutOf(const std::pair<int32_t, int64_t>& tf, Key first) const {
     RecordLayout lay = recordLayout(tf.first, [&] { return var_type[idOf(keys, first)]; });
     if (tf.first == GTG_FAC_SAM) lay.rows = sam_kind[(size_t)tf.second] == GTG_SAM_BEARING_RANGE ? 3 : sam_kind[(size_t)tf.second] == GTG_SAM_RANGE ? 1 : 2;
+    if (tf.first == GTG_FAC_POSE_PARTIAL) lay.rows = lay.bcols[0] == 6 ? 3 : pp_kind[(size_t)tf.second] == GTG_POSE_PARTIAL_TRANSLATION ? 2 : 1;
     return lay;
   }
 };
@@ -377,13 +387,13 @@ namespace {
 // calibrations as (run length, object) -- rows of the shared tables are handed out afterwards, sequentially, in first-occurrence
 // order, so that the tables are those of a single-threaded pass whatever the thread count.
 struct Extract {
-  std::vector<int32_t> sfm_cam, sfm_pt, pj_pose, pj_pt, pj_sen, st_pose, st_pt, st_sen, sam_kind, sam_pose, sam_pt, bt_1, bt_2, pr_var, sm_cam;
-  std::vector<double> sfm_z, pj_z, st_z, sam_z, sensor, bt_z, pr_data, sm_z, sm_prm;
+  std::vector<int32_t> sfm_cam, sfm_pt, pj_pose, pj_pt, pj_sen, st_pose, st_pt, st_sen, sam_kind, sam_pose, sam_pt, bt_1, bt_2, pr_var, sm_cam, pp_kind, pp_var;
+  std::vector<double> sfm_z, pj_z, st_z, sam_z, sensor, bt_z, pr_data, sm_z, sm_prm, pp_z;
   std::vector<int64_t> pr_off, sm_ptr;
   FactorMap fac_map;                                                        // (type, index in THIS chunk's table of that type)
   typedef std::vector<std::pair<int64_t, SharedNoiseModel>> Runs;
-  Runs sfm_nz, pj_nz, st_nz, sam_nz, bt_nz, pr_nz, sm_nz;
-  std::vector<int32_t> bt_dim, pr_dim, sam_dim;                             // expected noise dimension per between / prior / sam factor
+  Runs sfm_nz, pj_nz, st_nz, sam_nz, bt_nz, pr_nz, sm_nz, pp_nz;
+  std::vector<int32_t> bt_dim, pr_dim, sam_dim, pp_dim;                     // expected noise dimension per between / prior / sam / partial prior factor
   std::vector<std::pair<const void*, int>> pj_cal;                          // calibration object per projection factor, 1 = Cal3DS2
   std::vector<const Cal3_S2Stereo*> st_cal;                                 // calibration object per stereo factor
   std::vector<const Cal3_S2*> sm_cal;                                       // per smart factor: the shared K of a pose-type factor, null for a camera-type one
@@ -503,6 +513,14 @@ template <class T> void addPrior(Extract& x, const PriorFactor<T>& q, const std:
   packAs(q.prior(), Extract::grow(x.pr_data, storageSize(VarTypeOf<T>::value)));
   Extract::run(x.pr_nz, q.noiseModel()); x.pr_dim.push_back(tangentDim(VarTypeOf<T>::value));
 }
+// PoseTranslationPrior / PoseRotationPrior <Pose3 | Pose2>: one row of the partial pose prior table; z: the measurement's doubles (a
+// Point3, a Rot3's matrix row-major, a Point2, the (c, s) of a Rot2), rows: what the noise model's dimension must be
+void addPosePartial(Extract& x, int32_t kind, Key pose, const double* z, int nz, int rows, const SharedNoiseModel& nm, const std::vector<Key>& keys) {
+  x.fac_map.emplace_back(GTG_FAC_POSE_PARTIAL, (int64_t)x.pp_var.size());
+  x.pp_kind.push_back(kind); x.pp_var.push_back(idOf(keys, pose));
+  std::copy(z, z + nz, Extract::grow(x.pp_z, 9));
+  Extract::run(x.pp_nz, nm); x.pp_dim.push_back(rows);
+}
 void addFactor(Extract& x, const NonlinearFactor* f, const std::vector<Key>& keys) {
   if (auto s = dynamic_cast<const SfmFactor*>(f)) addSfm(x, *s, keys);
   else if (auto p = dynamic_cast<const ProjFactor*>(f)) addProjection(x, *p, keys);
@@ -516,13 +534,17 @@ void addFactor(Extract& x, const NonlinearFactor* f, const std::vector<Key>& key
   else if (auto sr = dynamic_cast<const SmartRigFactor*>(f)) addSmartRig(x, *sr, keys);
   else if (auto bb = dynamic_cast<const BetweenFactor<Pose3>*>(f)) addBetween(x, *bb, keys);
   else if (auto b2 = dynamic_cast<const BetweenFactor<Pose2>*>(f)) addBetween(x, *b2, keys);
+  else if (auto t3 = dynamic_cast<const TranslationPrior3*>(f)) { const Point3& t = t3->measured(); const double z[3] = {t.x(), t.y(), t.z()}; addPosePartial(x, GTG_POSE_PARTIAL_TRANSLATION, t3->key(), z, 3, 3, t3->noiseModel(), keys); }
+  else if (auto r3 = dynamic_cast<const RotationPrior3*>(f)) { double z[12]; packPose(Pose3(r3->measured(), Point3(0, 0, 0)), z); addPosePartial(x, GTG_POSE_PARTIAL_ROTATION, r3->key(), z, 9, 3, r3->noiseModel(), keys); }
+  else if (auto t2 = dynamic_cast<const TranslationPrior2*>(f)) { const double z[2] = {t2->measured().x(), t2->measured().y()}; addPosePartial(x, GTG_POSE_PARTIAL_TRANSLATION, t2->key(), z, 2, 2, t2->noiseModel(), keys); }
+  else if (auto r2 = dynamic_cast<const RotationPrior2*>(f)) { const double z[2] = {r2->measured().c(), r2->measured().s()}; addPosePartial(x, GTG_POSE_PARTIAL_ROTATION, r2->key(), z, 2, 1, r2->noiseModel(), keys); }
   else if (auto q2 = dynamic_cast<const PriorFactor<Pose2>*>(f)) addPrior(x, *q2, keys);
   else if (auto pp = dynamic_cast<const PriorFactor<Pose3>*>(f)) addPrior(x, *pp, keys);
   else if (auto pc = dynamic_cast<const PriorFactor<SfmCamera>*>(f)) addPrior(x, *pc, keys);
   else if (auto p3 = dynamic_cast<const PriorFactor<Point3>*>(f)) addPrior(x, *p3, keys);
   else throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: factor type outside the GPU hot path "   // (anything else is a hard error)
                                    "(supported: GeneralSFMFactor<SfmCamera,Point3>, GenericProjectionFactor<Pose3,Point3,Cal3_S2|Cal3DS2>, "
-                                   "GenericStereoFactor<Pose3,Point3>, BearingRangeFactor|RangeFactor|BearingFactor<Pose3,Point3>, SmartProjectionFactor<SfmCamera>, SmartProjectionPoseFactor<Cal3_S2>, SmartProjectionRigFactor<PinholePose<Cal3_S2>>, BetweenFactor<Pose3|Pose2>, PriorFactor<Pose3|Pose2|SfmCamera|Point3>)");
+                                   "GenericStereoFactor<Pose3,Point3>, BearingRangeFactor|RangeFactor|BearingFactor<Pose3,Point3>, SmartProjectionFactor<SfmCamera>, SmartProjectionPoseFactor<Cal3_S2>, SmartProjectionRigFactor<PinholePose<Cal3_S2>>, BetweenFactor<Pose3|Pose2>, PriorFactor<Pose3|Pose2|SfmCamera|Point3>, PoseTranslationPrior|PoseRotationPrior<Pose3|Pose2>)");
 }
 // The factors [b, e) of `graph` into x, each pointer also copied into `graphCopy`; the chunk stops at its first offending factor and keeps what that threw.
 void extractChunk(Extract& x, const NonlinearFactorGraph& graph, NonlinearFactorGraph& graphCopy, const std::vector<Key>& keys, size_t b, size_t e) {
@@ -551,13 +573,13 @@ template <class T> struct Raw {
   T* data() const { return p.get(); } size_t size() const { return n; }
 };
 typedef Raw<int32_t> RawI; typedef Raw<double> RawD;
-struct Place { int64_t o_sfm, o_pj, o_st, o_sam, o_bt, o_pr, o_sm; std::vector<std::pair<int64_t, int32_t>> sfm_rows; };   // per chunk: offsets of its tables, (count, noise row) of its GeneralSFM runs
+struct Place { int64_t o_sfm, o_pj, o_st, o_sam, o_bt, o_pr, o_sm, o_pp; std::vector<std::pair<int64_t, int32_t>> sfm_rows; };   // per chunk: offsets of its tables, (count, noise row) of its GeneralSFM runs
 struct HostProblem {
   NoiseTable nt;
   RawI sfm_cam, sfm_pt, sfm_nz;
   RawD sfm_z;
-  std::vector<int32_t> pj_pose, pj_pt, pj_nz, pj_cal, pj_sen, st_pose, st_pt, st_nz, st_cal, st_sen, sam_kind, sam_pose, sam_pt, sam_nz, bt_1, bt_2, bt_nz, pr_var, pr_nz, sm_cam, sm_nz, sm_cal, sm_sen, sm_mcal, sm_msen;
-  std::vector<double> pj_z, st_z, sam_z, calib, sensor, rig_sensor, bt_z, pr_data, sm_z, sm_prm;   // (rig_sensor: the rigs' extrinsics, appended to `sensor` behind every chunk's rows)
+  std::vector<int32_t> pj_pose, pj_pt, pj_nz, pj_cal, pj_sen, st_pose, st_pt, st_nz, st_cal, st_sen, sam_kind, sam_pose, sam_pt, sam_nz, bt_1, bt_2, bt_nz, pr_var, pr_nz, sm_cam, sm_nz, sm_cal, sm_sen, sm_mcal, sm_msen, pp_kind, pp_var, pp_nz;
+  std::vector<double> pj_z, st_z, sam_z, calib, sensor, rig_sensor, bt_z, pr_data, sm_z, sm_prm, pp_z;   // (rig_sensor: the rigs' extrinsics, appended to `sensor` behind every chunk's rows)
   std::vector<int64_t> pr_off, sm_ptr{0};    // (smart factors: one track each)
   bool any_smart_pose = false;               // a SmartProjectionPoseFactor: the smart_calib / smart_sensor tables go to the library
   bool any_smart_rig = false;                // a SmartProjectionRigFactor: sm_mcal / sm_msen (per smart measurement) go to the library too
@@ -618,6 +640,8 @@ struct HostProblem {
     pb.smart_calib = any_smart_pose ? sm_cal.data() : nullptr; pb.smart_sensor = any_smart_pose ? sm_sen.data() : nullptr;
     pb.smart_meas_calib = any_smart_rig ? sm_mcal.data() : nullptr; pb.smart_meas_sensor = any_smart_rig ? sm_msen.data() : nullptr;
     pb.n_prior = (int64_t)pr_var.size(); pb.prior_var = pr_var.data(); pb.prior_off = pr_off.data(); pb.prior_data = pr_data.data(); pb.prior_noise = pr_nz.data();
+    pb.n_pose_partial = (int64_t)pp_var.size();
+    if (pb.n_pose_partial) { pb.pose_partial_kind = pp_kind.data(); pb.pose_partial_var = pp_var.data(); pb.pose_partial_z = pp_z.data(); pb.pose_partial_noise = pp_nz.data(); }
     return pb;
   }
 };
@@ -727,7 +751,7 @@ HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap
     }
     for (const auto& kc : x.cal_order) { if (kc.second == 2) hp.stereoCalibRow(static_cast<const Cal3_S2Stereo*>(kc.first)); else hp.calibRow(kc.first, kc.second); }
     place[pi].o_sfm = o_sfm_next; place[pi].o_pj = (int64_t)hp.pj_pose.size(); place[pi].o_st = (int64_t)hp.st_pose.size(); place[pi].o_sam = (int64_t)hp.sam_pose.size(); place[pi].o_bt = (int64_t)hp.bt_1.size();
-    place[pi].o_pr = (int64_t)hp.pr_var.size(); place[pi].o_sm = (int64_t)hp.sm_nz.size();
+    place[pi].o_pr = (int64_t)hp.pr_var.size(); place[pi].o_sm = (int64_t)hp.sm_nz.size(); place[pi].o_pp = (int64_t)hp.pp_var.size();
     o_sfm_next += (int64_t)x.sfm_cam.size();
     for (const auto& r : x.sfm_nz) place[pi].sfm_rows.emplace_back(r.first, hp.nt.add(r.second, 2));
     cat(hp.pj_pose, x.pj_pose); cat(hp.pj_pt, x.pj_pt); cat(hp.pj_z, x.pj_z);
@@ -745,6 +769,8 @@ HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap
     cat(hp.pr_var, x.pr_var); cat(hp.pr_data, x.pr_data);
     for (int64_t o : x.pr_off) hp.pr_off.push_back(o + o_prd);
     rows(hp.pr_nz, x.pr_nz, &x.pr_dim);
+    cat(hp.pp_kind, x.pp_kind); cat(hp.pp_var, x.pp_var); cat(hp.pp_z, x.pp_z);
+    rows(hp.pp_nz, x.pp_nz, &x.pp_dim);
     cat(hp.sm_cam, x.sm_cam); cat(hp.sm_z, x.sm_z); cat(hp.sm_prm, x.sm_prm);
     for (size_t k = 1; k < x.sm_ptr.size(); k++) hp.sm_ptr.push_back(x.sm_ptr[k] + o_smc);
     rows(hp.sm_nz, x.sm_nz, nullptr);
@@ -777,7 +803,7 @@ HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap
     auto* fm_out = fac_map->data() + cut(nfac, part.size(), pi);     // (the chunk's factors: the range extractFactors gave it)
     for (const auto& fm : x.fac_map)
       *fm_out++ = {fm.first, fm.second + (fm.first == GTG_FAC_GENERAL_SFM ? pl.o_sfm : fm.first == GTG_FAC_PROJECTION ? pl.o_pj : fm.first == GTG_FAC_STEREO ? pl.o_st : fm.first == GTG_FAC_SAM ? pl.o_sam :
-                                           fm.first == GTG_FAC_BETWEEN_POSE3 ? pl.o_bt : fm.first == GTG_FAC_PRIOR ? pl.o_pr : fm.first == -2 ? pl.o_sm : 0)};
+                                           fm.first == GTG_FAC_BETWEEN_POSE3 ? pl.o_bt : fm.first == GTG_FAC_PRIOR ? pl.o_pr : fm.first == GTG_FAC_POSE_PARTIAL ? pl.o_pp : fm.first == -2 ? pl.o_sm : 0)};
   });
   return hp;
 }
@@ -832,7 +858,7 @@ void GpuLevenbergMarquardtOptimizer::init(const NonlinearFactorGraph& graph, con
   const HostProblem hp = mergeTables(part, graph.size(), &m.fac_map);
   lap("factors: merge, noise / calibration tables");
   const gtg_problem pb = hp.view(m.var_type);
-  m.sam_kind = hp.sam_kind;
+  m.sam_kind = hp.sam_kind; m.pp_kind = hp.pp_kind;
   if (shards.n_shards < 1 || shards.shard < 0 || shards.shard >= shards.n_shards) throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: bad ShardSpec");
   if (shards.n_shards > 1 && !shards.allreduce) throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: n_shards > 1 needs an all-reduce callback");
   for (auto& t : packers) t.join();

@@ -24,7 +24,7 @@ PHASES = ["linearize", "assemble", "point_eliminate", "schur", "cholesky", "solv
 SYMBOLS = ["gtg_create", "gtg_destroy", "gtg_prewarm", "gtg_last_error", "gtg_version", "gtg_upload_problem",
            "gtg_set_reduced_ordering", "gtg_values_size", "gtg_tangent_size", "gtg_set_values",
            "gtg_get_values", "gtg_get_trial_values", "gtg_error", "gtg_linearize", "gtg_try_lambda", "gtg_try_lambda_pcg",
-           "gtg_accept", "gtg_get_delta", "gtg_get_gradient", "gtg_get_hessian_diagonal",
+           "gtg_accept", "gtg_get_delta", "gtg_get_gradient", "gtg_get_graph_gradient", "gtg_get_hessian_diagonal",
            "gtg_get_jacobians", "gtg_reduced_dim", "gtg_get_reduced_matrix", "gtg_set_allreduce",
            "gtg_enable_timing", "gtg_get_phase_ms", "gtg_reset_timing", "gtg_phase_name",
            "gtg_cholesky_flops", "gtg_cholesky_flops_block_level", "gtg_cholesky_flops_executed", "gtg_linearize_bytes", "gtg_dense_cholesky_host", "gtg_structure_hash", "gtg_smart_repeated_keys", "gtg_smart_lost_workspace", "gtg_get_smart_triangulation",
@@ -78,7 +78,7 @@ def load():
     lib.gtg_upload_problem.argtypes = [C.c_void_p, C.POINTER(gtg_problem), C.c_int, C.c_int]
     lib.gtg_set_reduced_ordering.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     for name in ("gtg_set_values", "gtg_get_values", "gtg_get_trial_values", "gtg_get_delta",
-                 "gtg_get_gradient", "gtg_get_hessian_diagonal", "gtg_get_reduced_matrix"):
+                 "gtg_get_gradient", "gtg_get_graph_gradient", "gtg_get_hessian_diagonal", "gtg_get_reduced_matrix"):
         getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     lib.gtg_get_jacobians.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]
     lib.gtg_error.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -127,7 +127,7 @@ def _check(rc, what):
 class DeviceGraph:
     """One factor graph resident on one MI355X (one handle of the C ABI)."""
 
-    JAC_ROW = {0: 26, 1: 20, 2: 78, 3: 90, 4: 30, 5: 30}
+    JAC_ROW = {0: 26, 1: 20, 2: 78, 3: 90, 4: 30, 5: 30, 6: 90}
 
     def __init__(self, problem: Problem, device: int = 0, shard: int = 0, n_shards: int = 1,
                  reduced_ordering=None, allreduce=None):
@@ -185,6 +185,7 @@ class DeviceGraph:
     def trial_values(self): return self._get(self.lib.gtg_get_trial_values, self.val_size)
     def delta(self): return self._get(self.lib.gtg_get_delta, self.dim_size)
     def gradient(self): return self._get(self.lib.gtg_get_gradient, self.dim_size)
+    def graph_gradient(self): return self._get(self.lib.gtg_get_graph_gradient, self.dim_size)    # -gradientAtZero: smart factors as the Hessian factors they are
     def hessian_diagonal(self): return self._get(self.lib.gtg_get_hessian_diagonal, self.dim_size)
 
     def reduced_matrix(self):
@@ -194,7 +195,8 @@ class DeviceGraph:
         return out
 
     def jacobians(self, ftype):
-        n = {0: self.problem.n_sfm, 1: self.problem.n_proj, 2: self.problem.n_between, 3: self.problem.n_prior, 4: self.problem.n_stereo, 5: self.problem.n_sam}[ftype]
+        n = {0: self.problem.n_sfm, 1: self.problem.n_proj, 2: self.problem.n_between, 3: self.problem.n_prior, 4: self.problem.n_stereo, 5: self.problem.n_sam,
+             6: self.problem.n_pose_partial}[ftype]
         out = np.empty((n, self.JAC_ROW[ftype]), np.float64)
         _check(self.lib.gtg_get_jacobians(self.h, ftype, out.ctypes.data, out.size), "gtg_get_jacobians")
         return out

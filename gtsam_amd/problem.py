@@ -14,8 +14,9 @@ from dataclasses import dataclass, field
 import numpy as np
 
 VAR_POSE3, VAR_SFM_CAMERA, VAR_POINT3, VAR_POSE2 = 0, 1, 2, 3
-FAC_GENERAL_SFM, FAC_PROJECTION, FAC_BETWEEN_POSE3, FAC_PRIOR, FAC_STEREO, FAC_SAM = 0, 1, 2, 3, 4, 5
+FAC_GENERAL_SFM, FAC_PROJECTION, FAC_BETWEEN_POSE3, FAC_PRIOR, FAC_STEREO, FAC_SAM, FAC_POSE_PARTIAL = 0, 1, 2, 3, 4, 5, 6
 SAM_BEARING_RANGE, SAM_RANGE, SAM_BEARING = 0, 1, 2
+POSE_PARTIAL_TRANSLATION, POSE_PARTIAL_ROTATION = 0, 1
 NOISE_UNIT, NOISE_ISOTROPIC, NOISE_DIAGONAL, NOISE_GAUSSIAN = 0, 1, 2, 3
 SMART_RIG = -2     # smart_calib of a SmartProjectionRigFactor (GTG_SMART_RIG): calib / sensor per measurement
 ROBUST_NONE, ROBUST_FAIR, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY, ROBUST_WELSCH, ROBUST_GEMANMCCLURE, ROBUST_DCS, ROBUST_L2WITHDEADZONE = range(9)
@@ -47,6 +48,8 @@ class gtg_problem(C.Structure):
         ("smart_calib", _i32p), ("smart_sensor", _i32p),
         ("n_sam", C.c_int64), ("sam_kind", _i32p), ("sam_pose", _i32p), ("sam_point", _i32p), ("sam_z", _f64p), ("sam_noise", _i32p),
         ("smart_meas_calib", _i32p), ("smart_meas_sensor", _i32p),
+        ("n_pose_partial", C.c_int64), ("pose_partial_kind", _i32p), ("pose_partial_var", _i32p), ("pose_partial_z", _f64p),
+        ("pose_partial_noise", _i32p),
     ]
 
 
@@ -114,6 +117,12 @@ class Problem:
     prior_off: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int64))
     prior_data: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float64))
     prior_noise: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    # PoseTranslationPrior / PoseRotationPrior <Pose3 | Pose2>: pose_partial_kind POSE_PARTIAL_*, pose_partial_z 9 per factor = the
+    # measured Point3 | Rot3 row-major | Point2 | (c, s) of the measured Rot2 (the entries a form does not use are 0)
+    pose_partial_kind: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    pose_partial_var: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    pose_partial_z: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float64))
+    pose_partial_noise: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
 
     def __post_init__(self):
         for name, dt in (("var_type", np.int32), ("noise_kind", np.int32), ("noise_dim", np.int32),
@@ -132,7 +141,9 @@ class Problem:
                          ("calib_baseline", np.float64), ("smart_calib", np.int32), ("smart_sensor", np.int32),
                          ("smart_meas_calib", np.int32), ("smart_meas_sensor", np.int32),
                          ("sam_kind", np.int32), ("sam_pose", np.int32), ("sam_point", np.int32), ("sam_z", np.float64),
-                         ("sam_noise", np.int32)):
+                         ("sam_noise", np.int32),
+                         ("pose_partial_kind", np.int32), ("pose_partial_var", np.int32), ("pose_partial_z", np.float64),
+                         ("pose_partial_noise", np.int32)):
             setattr(self, name, _a(getattr(self, name), dt))
 
     # ---- sizes -------------------------------------------------------------------------------
@@ -152,6 +163,8 @@ class Problem:
     def n_prior(self): return int(self.prior_var.size)
     @property
     def n_smart(self): return int(self.smart_noise.size)
+    @property
+    def n_pose_partial(self): return int(self.pose_partial_var.size)
 
     def val_offsets(self):
         s = np.array([STORAGE[int(t)] for t in self.var_type], np.int64)
@@ -275,6 +288,14 @@ class Problem:
         p.sam_point = ptr(self.sam_point, C.c_int32)
         p.sam_z = ptr(self.sam_z, C.c_double)
         p.sam_noise = ptr(self.sam_noise, C.c_int32)
+        p.n_pose_partial = self.n_pose_partial
+        if self.pose_partial_z.size != 9 * self.n_pose_partial or \
+           any(a.size != self.n_pose_partial for a in (self.pose_partial_kind, self.pose_partial_noise)):
+            raise ValueError("inconsistent partial pose prior tables (pose_partial_z holds 9 doubles per factor)")
+        p.pose_partial_kind = ptr(self.pose_partial_kind, C.c_int32)
+        p.pose_partial_var = ptr(self.pose_partial_var, C.c_int32)
+        p.pose_partial_z = ptr(self.pose_partial_z, C.c_double)
+        p.pose_partial_noise = ptr(self.pose_partial_noise, C.c_int32)
         p._keep = keep
         return p
 
@@ -344,6 +365,27 @@ class Problem:
         self.sam_kind = np.append(self.sam_kind, np.int32(kind)); self.sam_pose = np.append(self.sam_pose, np.int32(pose))
         self.sam_point = np.append(self.sam_point, np.int32(point)); self.sam_noise = np.append(self.sam_noise, np.int32(noise_idx))
         self.sam_z = np.concatenate([self.sam_z, z])
+
+    # ---- partial pose priors -------------------------------------------------------------------
+    def add_pose_partial(self, kind: int, var: int, z, noise_idx: int):
+        """One PoseTranslationPrior (POSE_PARTIAL_TRANSLATION: z = the measured Point3 / Point2) or PoseRotationPrior
+        (POSE_PARTIAL_ROTATION: z = the measured Rot3's matrix, 9 doubles row-major, or the (c, s) the measured Rot2 holds) on the POSE3
+        or POSE2 variable `var`; the form follows from the kind and the variable's type."""
+        if kind not in (POSE_PARTIAL_TRANSLATION, POSE_PARTIAL_ROTATION):
+            raise ValueError("unknown partial pose prior kind")
+        if not 0 <= int(var) < self.n_vars or int(self.var_type[var]) not in (VAR_POSE3, VAR_POSE2):
+            raise ValueError("a partial pose prior needs a POSE3 or POSE2 variable")
+        z = _a(z, np.float64)
+        want = {(POSE_PARTIAL_TRANSLATION, VAR_POSE3): 3, (POSE_PARTIAL_ROTATION, VAR_POSE3): 9,
+                (POSE_PARTIAL_TRANSLATION, VAR_POSE2): 2, (POSE_PARTIAL_ROTATION, VAR_POSE2): 2}[(kind, int(self.var_type[var]))]
+        if z.size != want:
+            raise ValueError(f"partial pose prior: expected {want} measurement doubles, got {z.size}")
+        row = np.zeros(9)
+        row[:want] = z
+        self.pose_partial_kind = np.append(self.pose_partial_kind, np.int32(kind))
+        self.pose_partial_var = np.append(self.pose_partial_var, np.int32(var))
+        self.pose_partial_noise = np.append(self.pose_partial_noise, np.int32(noise_idx))
+        self.pose_partial_z = np.concatenate([self.pose_partial_z, row])
 
     # ---- priors ------------------------------------------------------------------------------
     def add_prior(self, var: int, value, noise_idx: int):

@@ -212,7 +212,34 @@ typedef struct gtg_problem {
    * (Appended after the bearing / range tables: a caller built against the older struct must be recompiled.) */
   const int32_t* smart_meas_calib;   /* [smart_ptr[n_smart]] index into the calib table, read for the measurements of rig-type factors */
   const int32_t* smart_meas_sensor;  /* [smart_ptr[n_smart]] index into the sensor table or -1, read for the same measurements */
+
+  /* GTG_FAC_POSE_PARTIAL: PoseTranslationPrior<POSE> and PoseRotationPrior<POSE> (slam/PoseTranslationPrior.h, slam/PoseRotationPrior.h;
+   * wrapped as PoseTranslationPrior3D / 2D and PoseRotationPrior3D / 2D), the absolute fix of PART of a pose: a position from GPS, UWB or a
+   * total station, an attitude from a compass or a gravity-aligned IMU.  Unary on a POSE3 or POSE2 variable; the kind and the variable's
+   * type decide the form (r the residual, H its Jacobian on the pose's tangent; b = -r, the whole system whitened, a Robust model
+   * re-weights by sqrt(weight(|whitened b|))):
+   *   TRANSLATION on POSE3  3 rows  r = t - z                      H = [0 | R]           z[0..2] the measured Point3
+   *   ROTATION    on POSE3  3 rows  r = Logmap(Z^T R)              H = [I | 0] exactly   z[0..8] the measured Rot3, row-major
+   *                                 (Rot3::localCoordinates, SO3::Logmap with its three branches; H is the identity block the
+   *                                 reference writes, not the derivative of Logmap)
+   *   TRANSLATION on POSE2  2 rows  r = t - z                      H = [c -s 0; s c 0]   z[0..1] the measured Point2
+   *   ROTATION    on POSE2  1 row   r = theta of Rot2(c_z, -s_z) * Rot2(c, s)  H = [0 0 1]  z[0..1] = c_z, s_z as the reference's
+   *                                 (Rot2::localCoordinates: wrapped into (-pi, pi])        Rot2 holds them
+   * pose_partial_z holds 9 doubles per factor, the entries a form does not use are 0.  PoseTranslationPrior<Pose3> is also the residual
+   * and Jacobian of navigation/GPSFactor.cpp:40-43 (p.translation(H) - nT_).  NULL / 0: no such factors.
+   * Refused by gtg_upload_problem, each with its own message: an unknown kind; a variable out of range or not POSE3 / POSE2; a noise
+   * dimension that is not the row count (3, 3, 2, 1); n_pose_partial > 0 with a table missing.
+   * (Appended after the rig-type smart tables: a caller built against the older struct must be recompiled.) */
+  int64_t n_pose_partial;
+  const int32_t* pose_partial_kind;   /* [n_pose_partial] GTG_POSE_PARTIAL_* */
+  const int32_t* pose_partial_var;    /* [n_pose_partial] variable id of the POSE3 or POSE2 */
+  const double* pose_partial_z;       /* [n_pose_partial*9] the measurement, see above */
+  const int32_t* pose_partial_noise;  /* [n_pose_partial] index into the noise table (dim 3, 3, 2 or 1 by kind and variable type) */
 } gtg_problem;
+/* pose_partial_kind */
+enum { GTG_POSE_PARTIAL_TRANSLATION = 0, GTG_POSE_PARTIAL_ROTATION = 1 };
+/* the factor type of the partial pose priors for gtg_get_jacobians (the enum of the factor types above, continued) */
+enum { GTG_FAC_POSE_PARTIAL = 6 };
 /* smart_calib[i] of a rig-type smart factor */
 enum { GTG_SMART_RIG = -2 };
 
@@ -303,12 +330,19 @@ int gtg_values_changed(gtg_handle h);
 int gtg_get_delta(gtg_handle h, double* delta, int64_t n);            /* VectorValues of last solve, variable id order */
 int gtg_get_gradient(gtg_handle h, double* g, int64_t n);             /* J^T b, variable id order */
 int gtg_get_hessian_diagonal(gtg_handle h, double* d, int64_t n);     /* GaussianFactorGraph::hessianDiagonal */
+/* -gradientAtZero() of the caller's linearised graph (GaussianFactorGraph::gradientAtZero, linear/GaussianFactorGraph.cpp), variable id
+ * order: gtg_get_gradient, except that every smart factor contributes as the Hessian factor it is in the reference -- its landmark
+ * eliminated without damping, so its cameras' blocks are F^T b - F^T E (E^T E)^-1 E^T b (SmartProjectionFactor.h:190-233).  Without
+ * smart factors the two getters return the same numbers.  A shard returns the share of its own factors, like gtg_get_gradient. */
+int gtg_get_graph_gradient(gtg_handle h, double* g, int64_t n);
 /* whitened Jacobian blocks + rhs of factor type `factor_type` after gtg_linearize():
  * row-major per factor: SFM [A1 2x9 | A2 2x3 | b 2], PROJECTION [2x6 | 2x3 | 2],
  * (the caller's own factors: never the measurements of smart factors), BETWEEN [6x6 | 6x6 | 6], PRIOR [d x d | d] padded to d=9 (81+9), STEREO [A1 3x6 | A2 3x3 | b 3] (30 doubles, the caller's stereo
  * factors in the caller's order; PROJECTION keeps returning the 20-double records of the monocular factors alone), SAM the same
  * 30-double record (the caller's bearing / range factors in the caller's order: bearing rows 0-1 and range row 2 of a bearing-range
- * factor, a range-only factor in row 0, a bearing-only factor in rows 0-1; the rows a kind does not use are exactly 0).
+ * factor, a range-only factor in row 0, a bearing-only factor in rows 0-1; the rows a kind does not use are exactly 0), POSE_PARTIAL the 90-double PRIOR
+ * record of the pose's tangent dimension d (the caller's partial pose priors in the caller's order: the factor's 3, 2 or 1 rows first,
+ * the rows it does not have exactly 0; PRIOR keeps returning the caller's PriorFactor records alone).
  * n = doubles available in out. */
 int gtg_get_jacobians(gtg_handle h, int factor_type, double* out, int64_t n);
 int64_t gtg_reduced_dim(gtg_handle h);
