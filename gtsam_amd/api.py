@@ -19,7 +19,7 @@ import numpy as np
 from .optimizer import DeviceLevenbergMarquardt
 from .params import LevenbergMarquardtParams
 from .problem import (NOISE_DIAGONAL, NOISE_GAUSSIAN, NOISE_ISOTROPIC, NOISE_UNIT, POSE_PARTIAL_ROTATION, POSE_PARTIAL_TRANSLATION, SAM_BEARING,
-                      SAM_BEARING_RANGE, SAM_RANGE, STORAGE, TANGENT, VAR_POINT3, VAR_POSE2, VAR_POSE3, VAR_SFM_CAMERA, Problem)
+                      SAM_BEARING_RANGE, SAM_RANGE, STORAGE, TANGENT, VAR_POINT2, VAR_POINT3, VAR_POSE2, VAR_POSE3, VAR_SFM_CAMERA, Problem)
 
 
 # ---- keys ---------------------------------------------------------------------------------------------------
@@ -69,6 +69,16 @@ class BearingRange3D:
     """gtsam.BearingRange3D = BearingRange<Pose3, Point3> (geometry/BearingRange.h): a Unit3 and a range."""
 
     def __init__(self, b: Unit3, r: float):
+        self.b, self.r = b, float(r)
+
+    def bearing(self): return self.b
+    def range(self): return self.r
+
+
+class BearingRange2D:
+    """gtsam.BearingRange2D = BearingRange<Pose2, Point2> (geometry/BearingRange.h): a Rot2 and a range."""
+
+    def __init__(self, b: "Rot2", r: float):
         self.b, self.r = b, float(r)
 
     def bearing(self): return self.b
@@ -355,6 +365,36 @@ class BearingFactor3D:
     def measured(self): return self.bearing
 
 
+class BearingRangeFactor2D:
+    """BearingRangeFactor<Pose2, Point2> under the name of GTSAM's Python wrapper (sam/sam.i): measuredBearing a Rot2."""
+    kind = SAM_BEARING_RANGE
+
+    def __init__(self, poseKey, pointKey, measuredBearing: Rot2, measuredRange: float, noiseModel):
+        self.keys_, self.bearing, self.range, self.model = (poseKey, pointKey), measuredBearing, float(measuredRange), noiseModel
+
+    def measured(self): return BearingRange2D(self.bearing, self.range)
+
+
+class RangeFactor2D:
+    """RangeFactor<Pose2, Point2> (sam/sam.i)."""
+    kind = SAM_RANGE
+
+    def __init__(self, key1, key2, measured: float, noiseModel):
+        self.keys_, self.bearing, self.range, self.model = (key1, key2), None, float(measured), noiseModel
+
+    def measured(self): return self.range
+
+
+class BearingFactor2D:
+    """BearingFactor<Pose2, Point2, Rot2> (sam/sam.i)."""
+    kind = SAM_BEARING
+
+    def __init__(self, key1, key2, measured: Rot2, noiseModel):
+        self.keys_, self.bearing, self.range, self.model = (key1, key2), measured, None, noiseModel
+
+    def measured(self): return self.bearing
+
+
 class SmartProjectionParams:
     """slam/SmartFactorParams.h:42-66 + geometry/triangulation.h:558-600 (IMPLICIT_SCHUR is refused at upload)."""
     IGNORE_DEGENERACY, ZERO_ON_DEGENERACY, HANDLE_INFINITY = 0, 1, 2
@@ -546,7 +586,7 @@ class Values:
             raise KeyError(f"ValuesKeyDoesNotExist: {key}")
         return self._d[key]
 
-    atPose3 = atPoint3 = atPinholeCameraCal3Bundler = at
+    atPose3 = atPoint3 = atPose2 = atPoint2 = atPinholeCameraCal3Bundler = at
 
 
 class NonlinearFactorGraph:
@@ -582,6 +622,8 @@ def extract(graph: NonlinearFactorGraph, values: Values):
         elif isinstance(v, Pose2): vt.append(VAR_POSE2); packed.append(v.packed())
         elif isinstance(v, PinholeCameraCal3Bundler): vt.append(VAR_SFM_CAMERA); packed.append(v.packed())
         elif isinstance(v, np.ndarray) and v.size == 3: vt.append(VAR_POINT3); packed.append(v.astype(np.float64))
+        elif isinstance(v, np.ndarray) and v.size == 2:     # a Point2, padded to the landmark slot (x, y, 0): the padding never leaves the C ABI
+            vt.append(VAR_POINT2); packed.append(np.array([v[0], v[1], 0.0], np.float64))
         else:
             raise ValueError(f"unsupported value type for key {k}")
     p = Problem(var_type=np.array(vt, np.int32))
@@ -628,6 +670,9 @@ def extract(graph: NonlinearFactorGraph, values: Values):
         elif isinstance(f, (BearingRangeFactor3D, RangeFactor3D, BearingFactor3D)):   # no calib or sensor entry
             p.add_sam(f.kind, vid(f.keys_[0]), vid(f.keys_[1]), nid(f.model, {SAM_BEARING_RANGE: 3, SAM_RANGE: 1, SAM_BEARING: 2}[f.kind]),
                       None if f.bearing is None else f.bearing.p, f.range)
+        elif isinstance(f, (BearingRangeFactor2D, RangeFactor2D, BearingFactor2D)):
+            p.add_sam2(f.kind, vid(f.keys_[0]), vid(f.keys_[1]), nid(f.model, 2 if f.kind == SAM_BEARING_RANGE else 1),
+                       None if f.bearing is None else (f.bearing.c(), f.bearing.s()), f.range)
         elif isinstance(f, SmartProjectionFactorPinholeCameraCal3Bundler):
             sp = f.params
             p.add_smart([vid(k) for k in f.keys_], np.concatenate(f.zs), nid(f.model, 2), sp.rankTolerance, sp.landmarkDistanceThreshold,
@@ -680,6 +725,8 @@ def extract(graph: NonlinearFactorGraph, values: Values):
         elif isinstance(f, _Prior):
             v = vid(f.keys_[0]); t = vt[v]
             data = f.prior.packed() if hasattr(f.prior, "packed") else np.asarray(f.prior, np.float64)
+            if t == VAR_POINT2:
+                raise ValueError("PriorFactor on a Point2 is outside the GPU hot path")
             if data.size != STORAGE[t]:
                 raise ValueError("prior type does not match the variable")
             p.add_prior(v, data, nid(f.model, TANGENT[t]))
@@ -727,8 +774,9 @@ class LevenbergMarquardtOptimizer:
         ordering = getattr(params, "ordering", None) if params is not None else None
         if ordering is not None:
             ids = {k: i for i, k in enumerate(self._keys)}
-            reduced = [ids[k] for k in ordering if k in ids and self._problem.var_type[ids[k]] != 2]
-            if len(reduced) != int((self._problem.var_type != 2).sum()):
+            landmark = np.isin(self._problem.var_type, (VAR_POINT3, VAR_POINT2))
+            reduced = [ids[k] for k in ordering if k in ids and not landmark[ids[k]]]
+            if len(reduced) != int((~landmark).sum()):
                 raise ValueError("LevenbergMarquardtParams.ordering must contain every non-landmark key exactly once")
         self._opt = DeviceLevenbergMarquardt(self._problem, v0, params, device=device, reduced_ordering=reduced)
 
@@ -750,5 +798,6 @@ class LevenbergMarquardtOptimizer:
             seg = packed[off[i]:off[i + 1]]
             proto = self._types[i]
             out.insert(k, Pose3.from_packed(seg) if isinstance(proto, Pose3) else Pose2.from_packed(seg) if isinstance(proto, Pose2)
-                       else PinholeCameraCal3Bundler.from_packed(seg) if isinstance(proto, PinholeCameraCal3Bundler) else seg.copy())
+                       else PinholeCameraCal3Bundler.from_packed(seg) if isinstance(proto, PinholeCameraCal3Bundler)
+                       else seg[:proto.size].copy())      # (a Point2 is the first two of its padded slot)
         return out

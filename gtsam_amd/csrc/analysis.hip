@@ -97,11 +97,11 @@ void analyze(gtg_context& c) {
   const int64_t n_sfm = c.f.n_sfm, n_proj = c.f.n_proj, n_btw = c.f.n_between, n_pri = c.f.n_prior;
   hipStream_t s = c.stream;
 
-  // landmarks = POINT3 variables (eliminated first, timing/timeSFMBAL.h:74-83); the rest is reduced
+  // landmarks = POINT3 variables -- POINT2 in a planar graph -- (eliminated first, timing/timeSFMBAL.h:74-83); the rest is reduced
   c.h_lm_index.assign(nv, -1); c.h_red_index.assign(nv, -1);
   c.h_lm_var.clear(); c.h_red_var.clear();
   for (int v = 0; v < nv; v++) {
-    if (c.h_var_type[v] == GTG_VAR_POINT3) { c.h_lm_index[v] = (int)c.h_lm_var.size(); c.h_lm_var.push_back(v); }
+    if (c.h_var_type[v] == GTG_VAR_POINT3 || c.h_var_type[v] == GTG_VAR_POINT2) { c.h_lm_index[v] = (int)c.h_lm_var.size(); c.h_lm_var.push_back(v); }
     else { c.h_red_index[v] = (int)c.h_red_var.size(); c.h_red_var.push_back(v); }
   }
   c.n_lm = (int)c.h_lm_var.size(); c.n_red_vars = (int)c.h_red_var.size();
@@ -112,14 +112,16 @@ void analyze(gtg_context& c) {
   // runtime of the CPU tests reports none -- cannot run the device pass)
   bool kernels_can_run = false;
   { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, c.device) == hipSuccess) kernels_can_run = std::strncmp(prop.gcnArchName, "gfx", 3) == 0; }
-  const bool device_terms = c.n_shards == 1 && c.n_lm > 0 && !std::getenv("GTG_HOST_ANALYSIS") && kernels_can_run;
+  // (a planar graph takes the host threads as well: the device pass checks the key roles of a camera graph)
+  const bool planar = c.f.form == ProjForm::Planar;
+  const bool device_terms = c.n_shards == 1 && c.n_lm > 0 && !std::getenv("GTG_HOST_ANALYSIS") && kernels_can_run && !planar;
   c.device_terms = device_terms;
   // validate factor roles (the observation factors' in the device pass when it runs: device_incidence_lists)
   if (!device_terms) {
     for (int64_t i = 0; i < n_sfm; i++)
       if (c.h_var_type[hi.sfm_cam[i]] != GTG_VAR_SFM_CAMERA || c.h_var_type[hi.sfm_point[i]] != GTG_VAR_POINT3)
         throw std::invalid_argument("GeneralSFMFactor keys must be (SFM_CAMERA, POINT3)");
-    for (int64_t i = 0; i < n_proj; i++)
+    for (int64_t i = 0; i < n_proj && !planar; i++)   // (planar: upload.hip has checked (POSE2, POINT2))
       if (c.h_var_type[hi.proj_pose[i]] != GTG_VAR_POSE3 || c.h_var_type[hi.proj_point[i]] != GTG_VAR_POINT3)
         throw std::invalid_argument("GenericProjectionFactor keys must be (POSE3, POINT3)");
   }

@@ -447,6 +447,7 @@ int gtg_try_lambda_pcg(gtg_handle c, double lambda, int diag, double dmin, doubl
   GTG_TRY
   if (!c || !c->uploaded || !c->linearized) throw std::invalid_argument("gtg_try_lambda_pcg: call gtg_linearize first");
   if (!(lambda > 0.0) || !cg) throw std::invalid_argument("gtg_try_lambda_pcg: lambda must be > 0, cg = {max, min, eps_rel, eps_abs}");
+  if (c->f.form == ProjForm::Planar) throw std::invalid_argument("gtg_try_lambda_pcg: a planar graph (POINT2 landmarks) is not supported, use gtg_try_lambda");
   DeviceGuard on_device(c->device);
   check_hip(hipMemsetAsync(c->scalars.p + SC_FAIL, 0, 3 * sizeof(double), c->stream), "memset");
   { PhaseTimer t(*c, GTG_PH_POINT_ELIM); launch_point_eliminate(*c, lambda, diag, dmin, dmax); }
@@ -597,7 +598,8 @@ int gtg_get_jacobians(gtg_handle c, int type, double* out, int64_t n) {
     case GTG_FAC_PRIOR: src = c->f.prior_J.p; cnt = c->f.n_user_prior * kPriorRec; break;   // (not the partial pose priors behind them)
     case GTG_FAC_POSE_PARTIAL: src = c->f.prior_J.p + (int64_t)kPriorRec * c->f.n_user_prior; cnt = (c->f.n_prior - c->f.n_user_prior) * kPriorRec; break;
     case GTG_FAC_STEREO: src = c->f.proj_J.p + (int64_t)kStereoRec * c->f.n_mono; cnt = (c->f.n_cam - c->f.n_mono) * kStereoRec; break;
-    case GTG_FAC_SAM: src = c->f.proj_J.p + (int64_t)kStereoRec * c->f.n_cam; cnt = (c->f.n_proj - c->f.n_cam) * kStereoRec; break;
+    case GTG_FAC_SAM: src = c->f.proj_J.p + (int64_t)kStereoRec * c->f.n_cam; cnt = has_sam(c->f.form) ? (c->f.n_proj - c->f.n_cam) * kStereoRec : 0; break;
+    case GTG_FAC_SAM2: src = c->f.proj_J.p; cnt = c->f.form == ProjForm::Planar ? c->f.n_proj * kPlanarRec : 0; break;   // (a planar range holds nothing else)
     default: throw std::invalid_argument("unknown factor type");
   }
   if (n != cnt) throw std::invalid_argument("gtg_get_jacobians: wrong output size");

@@ -29,24 +29,26 @@ struct JTabs {
 };
 
 // (A, rows, row stride, b) of one contribution to a reduced variable.  PR: rows of a projection record -- 2, or 3 in a graph with
-// stereo factors, where every observation of the projection range has the record [A1 PR x 6 | A2 PR x 3 | b PR] (factors.h kStereoRec)
-static_assert(proj_rec(ProjForm::Rows2) == kProjRec && proj_rec(ProjForm::Rows3) == kStereoRec, "a projection record is addressed by its row count");
-template <int PR>
+// stereo factors, where every observation of the projection range has the record [A1 PR x 6 | A2 PR x 3 | b PR] (factors.h kStereoRec).
+// DC: columns of its A1 -- 6, or 3 in a planar graph ([A1 3x3 | A2 3x3 | b 3], kPlanarRec: the POSE2 of a bearing / range factor)
+static_assert(proj_rec(ProjForm::Rows2) == kProjRec && proj_rec(ProjForm::Rows3) == kStereoRec && proj_rec(ProjForm::Planar) == kPlanarRec,
+              "a projection record is addressed by its row and column counts");
+template <int PR, int DC = 6>
 __device__ __forceinline__ void contribution(const JTabs& t, int kind, int idx, int d, const double*& A,
                                              int& rows, const double*& b) {
   if (kind == INC_SFM) { const double* J = t.sfm_J + (int64_t)kSfmRec * idx; A = J; rows = 2; b = J + 24; }
-  else if (kind == INC_PROJ) { const double* J = t.proj_J + (int64_t)(10 * PR) * idx; A = J; rows = PR; b = J + 9 * PR; }
+  else if (kind == INC_PROJ) { const double* J = t.proj_J + (int64_t)((DC + 4) * PR) * idx; A = J; rows = PR; b = J + (DC + 3) * PR; }
   else if (kind == INC_BTW_A) { const double* J = t.bt_J + (int64_t)kBetweenRec * idx; A = J; rows = d; b = J + 72; }   // d = 6 Pose3, 3 Pose2
   else if (kind == INC_BTW_B) { const double* J = t.bt_J + (int64_t)kBetweenRec * idx; A = J + 36; rows = d; b = J + 72; }
   else { const double* J = t.pr_J + (int64_t)kPriorRec * idx; A = J; rows = d; b = J + 81; }
 }
 
 // observation o -> (Jc rows x dc, Jp rows x 3, b rows); rows = 2, or PR for a projection observation
-template <int PR>
+template <int PR, int DC = 6>
 __device__ __forceinline__ void obs_rec(const JTabs& t, int64_t o, const double*& Jc, const double*& Jp,
                                         const double*& b, int& dc, int& rows) {
   if (o < t.n_sfm) { const double* J = t.sfm_J + (int64_t)kSfmRec * o; Jc = J; Jp = J + 18; b = J + 24; dc = 9; rows = 2; }
-  else { const double* J = t.proj_J + (int64_t)(10 * PR) * (o - t.n_sfm); Jc = J; Jp = J + 6 * PR; b = J + 9 * PR; dc = 6; rows = PR; }
+  else { const double* J = t.proj_J + (int64_t)((DC + 4) * PR) * (o - t.n_sfm); Jc = J; Jp = J + DC * PR; b = J + (DC + 3) * PR; dc = DC; rows = PR; }
 }
 
 // ---- lambda-invariant assembly --------------------------------------------------------------------
@@ -57,7 +59,7 @@ __device__ __forceinline__ void obs_rec(const JTabs& t, int64_t o, const double*
 // contribution list and are combined through LDS in wave order (deterministic).
 typedef double v4f64a __attribute__((ext_vector_type(4)));
 constexpr int kRedWaves = 16;   // waves per reduced variable: a 16-camera problem still has 256 wavefronts of work
-template <int PR>
+template <int PR, int DC = 6>
 __global__ __launch_bounds__(64 * kRedWaves) void k_red_diag(int32_t n_red_vars, const int64_t* __restrict__ inc_ptr,
     const int32_t* __restrict__ inc_kind, const int32_t* __restrict__ inc_idx, const int32_t* __restrict__ red_dim,
     const int64_t* __restrict__ red_off, JTabs t, double* __restrict__ Hd, double* __restrict__ g,
@@ -75,7 +77,7 @@ __global__ __launch_bounds__(64 * kRedWaves) void k_red_diag(int32_t n_red_vars,
   for (int64_t k = beg + wave; k < end; k += kRedWaves) {
     const double* A; const double* b; int rows;
     if (after_fused && inc_kind[k] == INC_SFM) continue;   // (wave-uniform)
-    contribution<PR>(t, inc_kind[k], inc_idx[k], d, A, rows, b);
+    contribution<PR, DC>(t, inc_kind[k], inc_idx[k], d, A, rows, b);
     const int boff = (int)(b - A);
     for (int q0 = 0; q0 < rows; q0 += 4) {
       const int q = q0 + lk;
@@ -246,8 +248,8 @@ __global__ __launch_bounds__(kBlock) void k_lm_fused(int32_t n_lm, const int64_t
 }
 
 // One lane per landmark: V = sum Jp^T Jp (+ priors), gp = sum Jp^T b.  PR = 3 (a graph with stereo factors): the projection
-// observations add their third row.
-template <int PR>
+// observations add their third row.  DC = 3: the records of a planar graph.
+template <int PR, int DC = 6>
 __global__ __launch_bounds__(kBlock) void k_lm_diag(int32_t n_lm, const int64_t* __restrict__ obs_ptr,
     const int32_t* __restrict__ obs, const int64_t* __restrict__ pri_ptr, const int32_t* __restrict__ pri,
     JTabs t, double* __restrict__ V, double* __restrict__ gp) {
@@ -255,7 +257,7 @@ __global__ __launch_bounds__(kBlock) void k_lm_diag(int32_t n_lm, const int64_t*
     double v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
     for (int64_t k = obs_ptr[l]; k < obs_ptr[l + 1]; k++) {
       const double *Jc, *Jp, *b; int dc, rows;
-      obs_rec<PR>(t, obs[k], Jc, Jp, b, dc, rows);
+      obs_rec<PR, DC>(t, obs[k], Jc, Jp, b, dc, rows);
       for (int i = 0; i < 3; i++) {
         for (int j = 0; j < 3; j++) v[3 * i + j] += Jp[i] * Jp[j] + Jp[3 + i] * Jp[3 + j];
         g[i] += Jp[i] * b[0] + Jp[3 + i] * b[1];
@@ -317,6 +319,11 @@ __device__ __forceinline__ double damp_term(double hjj, double invsigma, int dia
 
 // One lane per landmark: damped 3x3 Cholesky (Eigen LLT semantics + the exponent test of
 // base/cholesky.cpp:144-157), L^-1 and y = L^-1 gp.
+// PLANAR (ProjForm::Planar): every landmark is a POINT2 in the 3-wide slot.  Its E blocks have a zero third column, so row / column 3
+// of V is exactly zero, as for a point at infinity below: the third diagonal entry gets 1 and NO damping term for every lambda, under
+// diagonalDamping as well -- the damped 2 x 2 block's factor and an uncoupled y_3 = 0 -- and the exponent test compares the two pivots
+// of the clique's two frontal columns.
+template <bool PLANAR>
 __global__ __launch_bounds__(kBlock) void k_point_factor(int32_t n_lm, const int32_t* __restrict__ owned,
     const double* __restrict__ V, const double* __restrict__ gp, double invsigma, int diag, double dmin,
     double dmax, double* __restrict__ Linv, double* __restrict__ y, double* __restrict__ fail,
@@ -338,7 +345,9 @@ __global__ __launch_bounds__(kBlock) void k_point_factor(int32_t n_lm, const int
     }
     const double a00 = v[0] + (sm >= 0 ? 0.0 : damp_term(v[0], invsigma, diag, dmin, dmax));
     const double a11 = v[4] + (sm >= 0 ? 0.0 : damp_term(v[4], invsigma, diag, dmin, dmax));
-    const double a22 = (st & kTriAtInfinity) ? 1.0 : v[8] + (sm >= 0 ? 0.0 : damp_term(v[8], invsigma, diag, dmin, dmax));
+    double a22;
+    if constexpr (PLANAR) a22 = 1.0;
+    else a22 = (st & kTriAtInfinity) ? 1.0 : v[8] + (sm >= 0 ? 0.0 : damp_term(v[8], invsigma, diag, dmin, dmax));
     const double a10 = v[3], a20 = v[6], a21 = v[7];
     bool bad = !(a00 > 0.0);
     const double l00 = sqrt(a00);
@@ -351,8 +360,8 @@ __global__ __launch_bounds__(kBlock) void k_point_factor(int32_t n_lm, const int
     bad = bad || !(x22 > 0.0);
     const double l22 = sqrt(x22);
     int ex2, ex1;
-    (void)frexp(l11, &ex2);
-    (void)frexp(l22, &ex1);
+    if constexpr (PLANAR) { (void)frexp(l00, &ex2); (void)frexp(l11, &ex1); }
+    else { (void)frexp(l11, &ex2); (void)frexp(l22, &ex1); }
     bad = bad || (sm < 0 && !(ex2 - ex1 < 12));   // (choleskyPartial's rank test belongs to the eliminated cliques, not to a smart factor's inverse)
     if (bad) *fail = 1.0;
     // inverse of the lower-triangular factor
@@ -735,7 +744,7 @@ void launch_obs_wpos(gtg_context& c, int64_t n_inc) {
 
 void launch_assemble(gtg_context& c) {
   JTabs t = jtabs(c);
-  const bool three = proj_rows(c.f.form) == 3;
+  const bool three = proj_rows(c.f.form) == 3, planar = c.f.form == ProjForm::Planar;   // (planar: three rows as well, A1 three columns wide)
   if (c.n_red_vars && c.fused_sfm) {
     // several workgroups per camera where there are few cameras (a 16-camera graph has thousands of observations per camera)
     const int splits = c.n_red_vars >= 512 ? 1 : std::min(16, (1024 + c.n_red_vars - 1) / c.n_red_vars);
@@ -749,13 +758,13 @@ void launch_assemble(gtg_context& c) {
       hipLaunchKernelGGL(k_red_diag<2>, dim3(c.n_red_vars), dim3(64 * kRedWaves), 0, c.stream, c.n_red_vars, c.red_inc_ptr.p,
                          c.red_inc_kind.p, c.red_inc_idx.p, c.red_dim.p, c.red_off.p, t, c.Hd.p, c.gred0.p, c.hdiag_red.p, 1);
   } else if (c.n_red_vars)     // (a three-row graph is never fused: upload.hip)
-    hipLaunchKernelGGL(three ? k_red_diag<3> : k_red_diag<2>, dim3(c.n_red_vars), dim3(64 * kRedWaves), 0, c.stream, c.n_red_vars, c.red_inc_ptr.p,
+    hipLaunchKernelGGL((planar ? k_red_diag<3, 3> : three ? k_red_diag<3> : k_red_diag<2>), dim3(c.n_red_vars), dim3(64 * kRedWaves), 0, c.stream, c.n_red_vars, c.red_inc_ptr.p,
                        c.red_inc_kind.p, c.red_inc_idx.p, c.red_dim.p, c.red_off.p, t, c.Hd.p, c.gred0.p, c.hdiag_red.p, 0);
   if (c.n_lm && c.fused_sfm)
     hipLaunchKernelGGL(k_lm_fused, dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_obs_ptr.p, c.lm_obs.p,
                        c.lm_pri_ptr.p, c.lm_pri.p, t, sfm_tabs(c), c.V.p, c.gp.p);
   else if (c.n_lm)
-    hipLaunchKernelGGL(three ? k_lm_diag<3> : k_lm_diag<2>, dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_obs_ptr.p, c.lm_obs.p,
+    hipLaunchKernelGGL((planar ? k_lm_diag<3, 3> : three ? k_lm_diag<3> : k_lm_diag<2>), dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_obs_ptr.p, c.lm_obs.p,
                        c.lm_pri_ptr.p, c.lm_pri.p, t, c.V.p, c.gp.p);
   if (c.n_hoff)
     hipLaunchKernelGGL(k_hoff, dim3((unsigned)c.n_hoff), dim3(64), 0, c.stream, c.n_hoff, c.hoff_ptr.p, c.hoff_fac.p,
@@ -861,7 +870,8 @@ void launch_smart_lin1(gtg_context& c) {
 void launch_point_eliminate(gtg_context& c, double lambda, int diag, double dmin, double dmax) {
   if (!c.n_lm) return;
   const double is = inv_sigma(lambda);
-  hipLaunchKernelGGL(k_point_factor, dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_owned.p, c.V.p,
+  const bool planar = c.f.form == ProjForm::Planar;
+  hipLaunchKernelGGL(planar ? k_point_factor<true> : k_point_factor<false>, dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_owned.p, c.V.p,
                      c.gp.p, is, diag, dmin, dmax, c.Linv.p, c.ylm.p, c.scalars.p + SC_FAIL, c.n_smart ? c.lm_smart.p : nullptr, c.smart_lin_status.p);
   const SfmTabs st = sfm_tabs(c);
   if (c.f.n_sfm && c.fused_sfm)
@@ -871,7 +881,7 @@ void launch_point_eliminate(gtg_context& c, double lambda, int diag, double dmin
     hipLaunchKernelGGL((k_obs_E<kSfmRec, 9, 2, false>), dim3(grid1(c.f.n_sfm / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_sfm, c.f.sfm_J.p, st,
                        c.obs_lm.p, c.Linv.p, c.ylm.p, c.E.p, c.wobs.p, c.obs_wpos.p);
   if (c.f.n_proj)
-    hipLaunchKernelGGL((proj_rows(c.f.form) == 3 ? k_obs_E<kStereoRec, 6, 3, false> : k_obs_E<kProjRec, 6, 2, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
+    hipLaunchKernelGGL((planar ? k_obs_E<kPlanarRec, 3, 3, false> : proj_rows(c.f.form) == 3 ? k_obs_E<kStereoRec, 6, 3, false> : k_obs_E<kProjRec, 6, 2, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
                        c.f.proj_J.p, st, c.obs_lm.p + c.f.n_sfm, c.Linv.p, c.ylm.p, c.E.p + (int64_t)kEStride * c.f.n_sfm, c.wobs.p, c.obs_wpos.p + c.f.n_sfm);
   check_hip(hipGetLastError(), "point_eliminate");
 }
@@ -908,7 +918,7 @@ void launch_back_substitute(gtg_context& c) {
     hipLaunchKernelGGL((k_obs_v<kSfmRec, 9, 2, false>), dim3(grid1(c.f.n_sfm / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_sfm, c.f.sfm_J.p, st,
                        c.obs_red.p, c.red_off.p, c.xred.p, c.vobs.p);
   if (c.f.n_proj && c.n_lm)
-    hipLaunchKernelGGL((proj_rows(c.f.form) == 3 ? k_obs_v<kStereoRec, 6, 3, false> : k_obs_v<kProjRec, 6, 2, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
+    hipLaunchKernelGGL((c.f.form == ProjForm::Planar ? k_obs_v<kPlanarRec, 3, 3, false> : proj_rows(c.f.form) == 3 ? k_obs_v<kStereoRec, 6, 3, false> : k_obs_v<kProjRec, 6, 2, false>), dim3(grid1(c.f.n_proj / 4 + 1)), dim3(kBlock), 0, c.stream, c.f.n_proj,
                        c.f.proj_J.p, st, c.obs_red.p + c.f.n_sfm, c.red_off.p, c.xred.p, c.vobs.p + 3 * c.f.n_sfm);
   if (c.n_lm)
     hipLaunchKernelGGL(k_backsub_lm, dim3(grid1(c.n_lm)), dim3(kBlock), 0, c.stream, c.n_lm, c.lm_owned.p,
@@ -924,8 +934,9 @@ void launch_scatter_delta(gtg_context& c) {
 
 // gtg_prewarm: this unit's kernels (kernels.h)
 static void prewarm_assemble(int) {
-  prewarm_kernels({(const void*)k_red_diag<2>, (const void*)k_red_diag<3>, (const void*)k_cam_fused, (const void*)k_cam_combine, (const void*)k_lm_fused, (const void*)k_lm_diag<2>, (const void*)k_lm_diag<3>, (const void*)k_hoff,
-                   (const void*)k_point_factor, (const void*)k_obs_E<kSfmRec, 9, 2, true>, (const void*)k_obs_E<kSfmRec, 9, 2, false>, (const void*)k_obs_E<kProjRec, 6, 2, false>, (const void*)k_obs_E<kStereoRec, 6, 3, false>, (const void*)k_obs_v<kStereoRec, 6, 3, false>,
+  prewarm_kernels({(const void*)k_red_diag<2>, (const void*)k_red_diag<3>, (const void*)k_red_diag<3, 3>, (const void*)k_lm_diag<3, 3>, (const void*)k_point_factor<true>,
+                   (const void*)k_obs_E<kPlanarRec, 3, 3, false>, (const void*)k_obs_v<kPlanarRec, 3, 3, false>, (const void*)k_cam_fused, (const void*)k_cam_combine, (const void*)k_lm_fused, (const void*)k_lm_diag<2>, (const void*)k_lm_diag<3>, (const void*)k_hoff,
+                   (const void*)k_point_factor<false>, (const void*)k_obs_E<kSfmRec, 9, 2, true>, (const void*)k_obs_E<kSfmRec, 9, 2, false>, (const void*)k_obs_E<kProjRec, 6, 2, false>, (const void*)k_obs_E<kStereoRec, 6, 3, false>, (const void*)k_obs_v<kStereoRec, 6, 3, false>,
                    (const void*)k_obs_v<kSfmRec, 9, 2, true>, (const void*)k_obs_v<kSfmRec, 9, 2, false>, (const void*)k_obs_v<kProjRec, 6, 2, false>, (const void*)k_build_diag,
                    (const void*)k_scatter_hoff, (const void*)k_schur_pairs, (const void*)k_schur_pairs_heavy, (const void*)k_pad_diag, (const void*)k_backsub_lm,
                    (const void*)k_scatter_delta, (const void*)k_obs_wpos, (const void*)k_cam_pack, (const void*)k_smart_hdiag, (const void*)k_smart_lin1,

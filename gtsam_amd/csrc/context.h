@@ -107,16 +107,19 @@ struct DfPlan : DfLists {                       // + the device copies (tile_pla
 
 // The form of the projection range: what its records look like and which kernels linearise and evaluate it.  Decided once per
 // upload (upload.hip::upload_projection) from facts of the WHOLE graph -- a shard may own none of the factors that define the form.
-// These four are the only states: pose-type smart factors beside stereo or bearing / range factors are refused by SmartView
-// (upload.hip), and bearing / range factors alone already make a three-row graph.
+// These five are the only states: pose-type smart factors beside stereo or bearing / range factors are refused by SmartView
+// (upload.hip), bearing / range factors alone already make a three-row graph, and a planar graph has no other observation.
 enum class ProjForm {
   Rows2,        // GenericProjectionFactors only: records [A1 2x6 | A2 2x3 | b 2], two measurement entries
   Rows2Smart,   // ... and the measurements of pose-type smart factors behind them (gtg_context::smart_pose, which this state is derived from)
   Rows3,        // the graph has a GenericStereoFactor: three-row records and three measurement entries for every observation of the range
   Rows3Sam,     // the graph has bearing / range factors (with or without stereo factors): the same records, the sam factors in [n_cam, n_proj)
+  Planar,       // a POSE2 / POINT2 graph: the range is its bearing / range factors alone, the POSE2 as the "camera" (reduced dimension 3):
+                // records [A1 3x3 | A2 3x3 | b 3] with a zero third landmark column (the POINT2 padded to the landmark slot)
 };
-constexpr int proj_rows(ProjForm f) { return f == ProjForm::Rows3 || f == ProjForm::Rows3Sam ? 3 : 2; }
-constexpr int proj_rec(ProjForm f) { return 10 * proj_rows(f); }   // doubles per record [A1 R x 6 | A2 R x 3 | b R]: kProjRec / kStereoRec (factors.h)
+constexpr int proj_rows(ProjForm f) { return f == ProjForm::Rows2 || f == ProjForm::Rows2Smart ? 2 : 3; }
+constexpr int proj_dc(ProjForm f) { return f == ProjForm::Planar ? 3 : 6; }   // tangent dimension of the range's "camera"
+constexpr int proj_rec(ProjForm f) { return proj_rows(f) * (proj_dc(f) + 4); }   // doubles per record [A1 R x DC | A2 R x 3 | b R]: kProjRec / kStereoRec / kPlanarRec (factors.h)
 constexpr bool has_sam(ProjForm f) { return f == ProjForm::Rows3Sam; }
 
 struct FactorTables {
@@ -139,6 +142,8 @@ struct FactorTables {
   // range, behind the stereo factors [n_mono, n_cam).  They read no calib or sensor entry (proj_calib / proj_sensor hold -1 for them) and
   // keep their measurements in an array of their own: sam_z[4 (i - n_cam)] = the measured Unit3, then the range; sam_kind GTG_SAM_*.
   // Without sam factors n_cam == n_proj and both buffers are empty.
+  // ProjForm::Planar: the range is the planar bearing / range factors alone (n_mono == n_cam == 0); the two buffers hold their kinds
+  // and measurements, sam_z[3 i] = (c, s) of the measured Rot2, then the range.
   int64_t n_cam = 0;
   DevBuf<int32_t> sam_kind;
   DevBuf<double> sam_z;

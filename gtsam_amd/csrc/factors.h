@@ -5,6 +5,7 @@
 //   GenericProjectionFactor::evaluateError           slam/ProjectionFactor.h:138-166
 //   GenericStereoFactor<Pose3,Point3>::evaluateError  slam/StereoFactor.h:126-154
 //   BearingRange / Range / BearingFactor<Pose3,Point3>  sam/*.h through nonlinear/ExpressionFactor.h:104-153
+//   BearingRange / Range / BearingFactor<Pose2,Point2>  the same, planar
 //   BetweenFactor<Pose3>::evaluateError              slam/BetweenFactor.h:111-124
 //   PriorFactor<T>::evaluateError                    nonlinear/PriorFactor.h:98-102
 // followed by NoiseModelFactor::linearize's  b = -r, WhitenSystem(A, b)
@@ -384,6 +385,106 @@ GT_HD double sam_residual(int kind, const double* pose, const double* pt, const 
 GT_HD double sam_error(int kind, const double* pose, const double* pt, const double* z, const NoiseRef& n) {
   double r[3];
   return factor_loss(n, sam_residual(kind, pose, pt, z, n, r));
+}
+
+// ---- BearingRangeFactor / RangeFactor / BearingFactor <Pose2,Point2> (gtsam/sam, planar) -------
+// The same ExpressionFactorN as above with h = Pose2::bearing / Pose2::range of the landmark:
+//   transformTo (geometry/Pose2.cpp:207-214, Rot2::unrotate Rot2.cpp:110-116): q = R^T (p - t), Hpose = [-1 0 q.y; 0 -1 -q.x], Hpoint = R^T
+//   bearing (Pose2.cpp:245-256) = Rot2::relativeBearing(q) (Rot2.cpp:119-130): H = [-y/d2, x/d2] and fromCosSin(x/n, y/n) when n > 1e-5,
+//     otherwise the identity rotation with a ZERO Jacobian
+//   range (Pose2.cpp:270-284) = norm2(p - t) (Point2.cpp:27-36), Jacobian (1, 1) at r <= 1e-10, Hpose = D [-c s 0; -s -c 0], Hpoint = D
+//   b = Local(h, z) = [theta(h^-1 z) ; z_range - h_range] (BearingRange.h:138-144); the product goes through Rot2::operator* /
+//     fromCosSin (re-normalised beyond 1e-10 only, Rot2.cpp:56-64), the angle is atan2's
+// The Jacobians are those of h alone; the whole system is whitened, a Robust model re-weights by sqrt(weight(|whitened b|)).
+// pose: (x, y, theta) as stored; pt: (x, y, 0), the POINT2 padded to the landmark slot; z: (c, s) of the measured Rot2 as the reference
+// holds it, then the range.  Record [A1 3x3 | A2 3x3 | b 3] (kPlanarRec): bearing in row 0 and range in row 1 of a bearing-range factor,
+// a bearing-only or range-only factor in row 0; A2's third column and every unused row are exactly 0.
+// Contraction is off where p - t, the products of unrotate and h^-1 z are formed: one record, the same doubles in every kernel and in
+// the host compile of the CPU parity test.
+constexpr int kPlanarRec = 3 * 3 + 3 * 3 + 3;
+GT_HD int sam2_rows(int kind) { return kind == kSamBearingRange ? 2 : 1; }
+// the unwhitened compact system [A1 ROWS x 3 | A2 ROWS x 2 | b ROWS] (A1 = nullptr: b alone)
+template <int KIND>
+GT_HD void sam2_system(const double* pose, const double* pt, const double* z, double* A1, double* A2, double* b) {
+  _Pragma("clang fp contract(off)")
+  const double c = cos(pose[2]), s = sin(pose[2]);
+  const double dx = pt[0] - pose[0], dy = pt[1] - pose[1];
+  constexpr int r0 = KIND == kSamBearingRange ? 1 : 0;   // the range's row
+  if (KIND != kSamRange) {
+    const double qx = c * dx + s * dy, qy = -s * dx + c * dy;
+    const double d2 = qx * qx + qy * qy, n = sqrt(d2);
+    double hc = 1.0, hs = 0.0, H0 = 0.0, H1 = 0.0;
+    if (fabs(n) > 1e-5) {
+      H0 = -qy / d2; H1 = qx / d2;
+      hc = qx / n; hs = qy / n;
+      rot2_normalize(hc, hs);
+    }
+    if (A1) {
+      A1[0] = H0 * -1.0 + H1 * 0.0; A1[1] = H0 * 0.0 + H1 * -1.0; A1[2] = H0 * qy + H1 * -qx;
+      A2[0] = H0 * c + H1 * -s; A2[1] = H0 * s + H1 * c;
+    }
+    // h^-1 z: Rot2(hc, -hs) * Rot2(z0, z1)
+    double bc = hc * z[0] - (-hs) * z[1], bs = (-hs) * z[0] + hc * z[1];
+    rot2_normalize(bc, bs);
+    b[0] = atan2(bs, bc);
+  }
+  if (KIND != kSamBearing) {
+    const double r = sqrt(dx * dx + dy * dy);
+    double D0 = 1.0, D1 = 1.0;
+    if (fabs(r) > 1e-10) { D0 = dx / r; D1 = dy / r; }
+    if (A1) {
+      A1[3 * r0] = D0 * -c + D1 * -s; A1[3 * r0 + 1] = D0 * s + D1 * -c; A1[3 * r0 + 2] = D0 * 0.0 + D1 * 0.0;
+      A2[2 * r0] = D0; A2[2 * r0 + 1] = D1;
+    }
+    b[r0] = z[2] - r;
+  }
+}
+template <int KIND>
+GT_HD void sam2_linearize_kind(const double* pose, const double* pt, const double* z, const NoiseRef& n, double* J) {
+  _Pragma("clang fp contract(off)")
+  constexpr int R = KIND == kSamBearingRange ? 2 : 1;
+  double A1[3 * R], A2[2 * R], b[R];
+  sam2_system<KIND>(pose, pt, z, A1, A2, b);
+  whiten_cols<R>(n.kind, n.data, A1, 3);
+  whiten_cols<R>(n.kind, n.data, A2, 2);
+  whiten_cols<R>(n.kind, n.data, b, 1);
+  if (n.rkind) {
+    const double w = reweight_factor(n, b, R);
+    for (int i = 0; i < 3 * R; i++) A1[i] *= w;
+    for (int i = 0; i < 2 * R; i++) A2[i] *= w;
+    for (int i = 0; i < R; i++) b[i] *= w;
+  }
+  for (int i = 0; i < kPlanarRec; i++) J[i] = 0.0;
+  for (int r = 0; r < R; r++) {
+    for (int k = 0; k < 3; k++) J[3 * r + k] = A1[3 * r + k];
+    for (int k = 0; k < 2; k++) J[9 + 3 * r + k] = A2[2 * r + k];
+    J[18 + r] = b[r];
+  }
+}
+GT_HD void sam2_linearize(int kind, const double* pose, const double* pt, const double* z, const NoiseRef& n, double* J) {
+  if (kind == kSamBearingRange) sam2_linearize_kind<kSamBearingRange>(pose, pt, z, n, J);
+  else if (kind == kSamRange) sam2_linearize_kind<kSamRange>(pose, pt, z, n, J);
+  else sam2_linearize_kind<kSamBearing>(pose, pt, z, n, J);
+}
+// the whitened residual -Local(h, z) of the factor in its first sam2_rows(kind) places (what its error is the loss of)
+template <int KIND>
+GT_HD double sam2_residual_kind(const double* pose, const double* pt, const double* z, const NoiseRef& n, double* r) {
+  constexpr int R = KIND == kSamBearingRange ? 2 : 1;
+  sam2_system<KIND>(pose, pt, z, nullptr, nullptr, r);
+  for (int i = 0; i < R; i++) r[i] = -r[i];
+  whiten_cols<R>(n.kind, n.data, r, 1);
+  double sq = 0.0;
+  for (int i = 0; i < R; i++) sq += r[i] * r[i];
+  return sq;
+}
+GT_HD double sam2_residual(int kind, const double* pose, const double* pt, const double* z, const NoiseRef& n, double* r) {
+  if (kind == kSamBearingRange) return sam2_residual_kind<kSamBearingRange>(pose, pt, z, n, r);
+  if (kind == kSamRange) return sam2_residual_kind<kSamRange>(pose, pt, z, n, r);
+  return sam2_residual_kind<kSamBearing>(pose, pt, z, n, r);
+}
+GT_HD double sam2_error(int kind, const double* pose, const double* pt, const double* z, const NoiseRef& n) {
+  double r[2];
+  return factor_loss(n, sam2_residual(kind, pose, pt, z, n, r));
 }
 
 // ---- BetweenFactor<Pose3> ---------------------------------------------------------------------

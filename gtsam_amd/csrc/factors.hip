@@ -169,6 +169,31 @@ __global__ __launch_bounds__(kBlock) void k_lin_rows3(int64_t n, int64_t n_mono,
   }
 }
 
+// The projection range of a planar graph (ProjForm::Planar): every observation is a bearing / range factor <Pose2, Point2> of kind[i]
+// with the measurement z[3 i]; the pose holds three doubles, the landmark (x, y, 0).  One factor per lane, the record (kPlanarRec) in
+// place in the LDS image and stored as above.
+__global__ __launch_bounds__(kBlock) void k_lin_planar(int64_t n, const int32_t* __restrict__ pose, const int32_t* __restrict__ pt,
+    const int32_t* __restrict__ nz, const int32_t* __restrict__ kind, const double* __restrict__ z,
+    const double* __restrict__ values, const int64_t* __restrict__ val_off, NoiseTab nt, double* __restrict__ J) {
+  typedef RecIO<kPlanarRec> IO;
+  __shared__ double img[kBlock / 64][IO::LDS_DOUBLES];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double* my = img[wave];
+  const int64_t nchunks = (n + 63) / 64, stride = (int64_t)gridDim.x * (kBlock / 64);
+  for (int64_t ch = blockIdx.x * (int64_t)(kBlock / 64) + wave; ch < nchunks; ch += stride) {
+    const int64_t i = ch * 64 + lane;
+    if (i < n) {
+      double x[3], p[3], zz[3];
+      const double* xp = values + val_off[pose[i]];
+      const double* pp = values + val_off[pt[i]];
+      for (int k = 0; k < 3; k++) { x[k] = xp[k]; p[k] = pp[k]; zz[k] = z[3 * i + k]; }
+      sam2_linearize(kind[i], x, p, zz, nt.ref(nz[i]), my + lane * IO::PITCH);
+    }
+    const int64_t left = n - ch * 64;
+    IO::store(my, J + (int64_t)kPlanarRec * ch * 64, left < 64 ? (int)left : 64, lane);
+  }
+}
+
 // BetweenFactor<Pose3> or BetweenFactor<Pose2>: decided by the type of the factor's variables (both of one type)
 __global__ __launch_bounds__(kBlock) void k_lin_between(int64_t n, const int32_t* __restrict__ v1,
     const int32_t* __restrict__ v2, const double* __restrict__ z, const int32_t* __restrict__ nz,
@@ -332,6 +357,23 @@ __global__ __launch_bounds__(kBlock) void k_error_rows3(int64_t n, int64_t n_mon
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
+// The projection range of a planar graph (the range of k_lin_planar), in the place of k_error_rows3.  Fixed slices per block as above.
+__global__ __launch_bounds__(kBlock) void k_error_planar(int64_t n, const int32_t* __restrict__ pose, const int32_t* __restrict__ pt,
+    const int32_t* __restrict__ nz, const int32_t* __restrict__ kind, const double* __restrict__ z,
+    const double* __restrict__ values, const int64_t* __restrict__ val_off, NoiseTab nt, double* __restrict__ partials) {
+  double acc = 0.0;
+  const int64_t tid = blockIdx.x * (int64_t)kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = tid; i < n; i += stride) {
+    double x[3], p[3], zz[3];
+    const double* xp = values + val_off[pose[i]];
+    const double* pp = values + val_off[pt[i]];
+    for (int k = 0; k < 3; k++) { x[k] = xp[k]; p[k] = pp[k]; zz[k] = z[3 * i + k]; }
+    acc += sam2_error(kind[i], x, p, zz, nt.ref(nz[i]));
+  }
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
 // The partial pose priors (the range of k_lin_pose_partial): k_error<kErrRest> is launched with the caller's PriorFactors alone.
 // Fixed slices per block as above; the block partials go behind those of the other error kernels, where k_final_sum picks them up.
 __global__ __launch_bounds__(kBlock) void k_error_pose_partial(int64_t n, int64_t first, const int32_t* __restrict__ var,
@@ -375,8 +417,8 @@ struct LinErrArgs {
 
 // FUSED: the records of the GeneralSFM factors are recomputed (fused.h) instead of read: chunk c of 64 consecutive factors belongs to
 // wavefront c of the grid, as in k_lin_sfm.  PR: rows of a projection record -- 2, or 3 in a graph with stereo factors ([A1 PR x 6 |
-// A2 PR x 3 | b PR], factors.h).
-template <bool FUSED, int PR>
+// A2 PR x 3 | b PR], factors.h).  DC: columns of its A1 -- 6, or 3 in a planar graph (the POSE2 of a bearing / range factor).
+template <bool FUSED, int PR, int DC = 6>
 __global__ __launch_bounds__(kBlock) void k_linear_error(LinErrArgs a, SfmTabs t, const double* __restrict__ delta,
                                                          double* __restrict__ partials) {
   typedef RecIO<kSfmRec> IO;
@@ -416,14 +458,14 @@ __global__ __launch_bounds__(kBlock) void k_linear_error(LinErrArgs a, SfmTabs t
   }
   }
   for (int64_t i = tid; i < a.n_proj; i += stride) {
-    const double* J = a.proj_J + (int64_t)(10 * PR) * i;
+    const double* J = a.proj_J + (int64_t)((DC + 4) * PR) * i;
     const double* dc = delta + a.dim_off[a.proj_pose[i]];
     const double* dp = delta + a.dim_off[a.proj_pt[i]];
     for (int r = 0; r < PR; r++) {
-      const double b = J[9 * PR + r];
+      const double b = J[(DC + 3) * PR + r];
       double v = -b;
-      for (int k = 0; k < 6; k++) v += J[6 * r + k] * dc[k];
-      for (int k = 0; k < 3; k++) v += J[6 * PR + 3 * r + k] * dp[k];
+      for (int k = 0; k < DC; k++) v += J[DC * r + k] * dc[k];
+      for (int k = 0; k < 3; k++) v += J[DC * PR + 3 * r + k] * dp[k];
       e0 += b * b; e1 += v * v;
     }
   }
@@ -720,6 +762,10 @@ void launch_linearize(gtg_context& c) {
       break;
     case ProjForm::Rows3: three_row(k_lin_rows3<false>); break;
     case ProjForm::Rows3Sam: three_row(k_lin_rows3<true>); break;
+    case ProjForm::Planar:
+      hipLaunchKernelGGL(k_lin_planar, dim3(grid_for(f.n_proj)), dim3(kBlock), 0, c.stream, f.n_proj, f.proj_pose.p, f.proj_point.p,
+                         f.proj_noise.p, f.sam_kind.p, f.sam_z.p, c.values.p, c.val_off.p, nt, f.proj_J.p);
+      break;
   }
   if (f.n_between)
     hipLaunchKernelGGL(k_lin_between, dim3(grid_for(f.n_between)), dim3(kBlock), 0, c.stream, f.n_between,
@@ -764,7 +810,7 @@ void launch_sfm_records(gtg_context& c, double* dst) {
 
 void launch_error(gtg_context& c, const double* values, int slot, const double* gate) {
   auto& f = c.f;
-  const bool three = proj_rows(f.form) == 3;   // (its projection range goes to k_error_rows3, the third group of block partials)
+  const bool three = proj_rows(f.form) == 3;   // (its projection range goes to k_error_rows3 -- k_error_planar --, the third group of block partials)
   const int64_t n_partial = f.n_prior - f.n_user_prior;   // (the partial pose priors go to k_error_pose_partial, the last group of block partials)
   ErrArgs a{f.n_sfm, three ? 0 : f.n_proj, f.n_between, f.n_user_prior,
             f.sfm_cam.p, f.sfm_point.p, f.sfm_noise.p, f.sfm_z.p,
@@ -783,7 +829,10 @@ void launch_error(gtg_context& c, const double* values, int slot, const double* 
   const auto k_three = has_sam(f.form) ? k_error_rows3<true> : k_error_rows3<false>;
   if (g1) hipLaunchKernelGGL(k_error<kErrSfm>, dim3(g1), dim3(kBlock), 0, c.stream, a_sfm, values, noise_tab(c), c.partials.p);
   if (g2) hipLaunchKernelGGL(k_rest, dim3(g2), dim3(kBlock), 0, c.stream, a, values, noise_tab(c), c.partials.p + g1);
-  if (g3) hipLaunchKernelGGL(k_three, dim3(g3), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.n_cam, f.proj_pose.p, f.proj_point.p,
+  if (g3 && f.form == ProjForm::Planar)
+    hipLaunchKernelGGL(k_error_planar, dim3(g3), dim3(kBlock), 0, c.stream, f.n_proj, f.proj_pose.p, f.proj_point.p, f.proj_noise.p,
+                       f.sam_kind.p, f.sam_z.p, values, c.val_off.p, noise_tab(c), c.partials.p + g1 + g2);
+  else if (g3) hipLaunchKernelGGL(k_three, dim3(g3), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.n_cam, f.proj_pose.p, f.proj_point.p,
                              f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_baseline.p, f.sensor.p,
                              f.sam_kind.p, f.sam_z.p, values, c.val_off.p, noise_tab(c), c.partials.p + g1 + g2);
   const int g4 = n_partial ? std::min(grid_for(n_partial), gmax) : 0;
@@ -807,8 +856,9 @@ void launch_linear_error(gtg_context& c) {
                f.sfm_J.p, f.proj_J.p, f.between_J.p, f.prior_J.p, c.var_type.p, c.dim_off.p};
   const int64_t nmax = std::max(std::max(f.n_sfm, f.n_proj), std::max(f.n_between, f.n_prior));
   const int g = grid_for(nmax);
-  static_assert(proj_rec(ProjForm::Rows2) == kProjRec && proj_rec(ProjForm::Rows3) == kStereoRec, "k_linear_error addresses a projection record by its row count");
-  const auto kernel = proj_rows(f.form) == 3 ? k_linear_error<false, 3> : c.fused_sfm ? k_linear_error<true, 2> : k_linear_error<false, 2>;   // (three-row: never fused, upload.hip)
+  static_assert(proj_rec(ProjForm::Rows2) == kProjRec && proj_rec(ProjForm::Rows3) == kStereoRec && proj_rec(ProjForm::Planar) == kPlanarRec,
+                "k_linear_error addresses a projection record by its row and column counts");
+  const auto kernel = f.form == ProjForm::Planar ? k_linear_error<false, 3, 3> : proj_rows(f.form) == 3 ? k_linear_error<false, 3> : c.fused_sfm ? k_linear_error<true, 2> : k_linear_error<false, 2>;   // (three-row, planar: never fused, upload.hip)
   hipLaunchKernelGGL(kernel, dim3(g), dim3(kBlock), 0, c.stream, a, sfm_tabs(c), c.delta.p, c.partials.p);
   hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(kBlock), 0, c.stream, c.partials.p, g, 2, c.scalars.p, (int)SC_LIN0);
   check_hip(hipGetLastError(), "linear_error");
@@ -832,7 +882,8 @@ void prewarm_factors(int) {
   prewarm_kernels({(const void*)k_lin_sfm, (const void*)k_lin_proj<false>, (const void*)k_lin_proj<true>, (const void*)k_lin_rows3<false>, (const void*)k_lin_rows3<true>,
                    (const void*)k_lin_between, (const void*)k_lin_prior, (const void*)k_lin_pose_partial, (const void*)k_error_pose_partial, (const void*)k_error<kErrSfm>, (const void*)k_error<kErrRest>,
                    (const void*)k_error<kErrRest | kErrSmartProj>, (const void*)k_error_rows3<false>, (const void*)k_error_rows3<true>, (const void*)k_final_sum,
-                   (const void*)k_linear_error<true, 2>, (const void*)k_linear_error<false, 2>, (const void*)k_linear_error<false, 3>, (const void*)k_retract,
+                   (const void*)k_linear_error<true, 2>, (const void*)k_linear_error<false, 2>, (const void*)k_linear_error<false, 3>, (const void*)k_linear_error<false, 3, 3>,
+                   (const void*)k_lin_planar, (const void*)k_error_planar, (const void*)k_retract,
                    (const void*)k_sumsq, (const void*)k_smart_triangulate<false, false>, (const void*)k_smart_triangulate<true, false>,
                    (const void*)k_smart_triangulate<false, true>, (const void*)k_smart_triangulate<true, true>, (const void*)k_lin_smart_at_infinity,
                    (const void*)k_error_smart_at_infinity, (const void*)k_sfm_value_offsets, (const void*)k_lin_smart_pose_at_infinity,

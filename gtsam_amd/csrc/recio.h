@@ -14,8 +14,10 @@ namespace gt {
 
 template <int REC>
 struct RecIO {
-  static_assert(REC % 2 == 0, "records are copied in 16-byte pieces");
-  static constexpr int PITCH = REC + 1;
+  // even records are copied in 16-byte pieces; an odd one (the planar record of 21 doubles) double by double, 512 B contiguous per
+  // instruction: a piece of two would straddle two records -- and, behind the last record of the range, the end of the buffer
+  static constexpr bool PAIRS = REC % 2 == 0;
+  static constexpr int PITCH = PAIRS ? REC + 1 : REC;   // odd either way
   static constexpr int LDS_DOUBLES = 64 * PITCH;   // per wavefront
 
   static __device__ __forceinline__ void wave_sync() {
@@ -26,6 +28,7 @@ struct RecIO {
   // LDS image -> global: g points at the wavefront's first record (16-byte aligned), nrec <= 64 records are valid
   static __device__ __forceinline__ void store(const double* lds, double* __restrict__ g, int nrec, int lane) {
     wave_sync();
+    if constexpr (PAIRS) {
 #pragma unroll
     for (int u = 0; u < REC / 2; u++) {
       const int e = 2 * (u * 64 + lane), r = e / REC, o = e - r * REC;
@@ -35,10 +38,18 @@ struct RecIO {
         *reinterpret_cast<double2*>(g + e) = v;
       }
     }
+    } else {
+#pragma unroll
+    for (int u = 0; u < REC; u++) {
+      const int e = u * 64 + lane, r = e / REC, o = e - r * REC;
+      if (r < nrec) g[e] = lds[r * PITCH + o];
+    }
+    }
     wave_sync();   // the image may be overwritten afterwards
   }
   // global -> LDS image
   static __device__ __forceinline__ void load(double* lds, const double* __restrict__ g, int nrec, int lane) {
+    if constexpr (PAIRS) {
     double2 v[REC / 2];
 #pragma unroll
     for (int u = 0; u < REC / 2; u++) {
@@ -50,6 +61,20 @@ struct RecIO {
     for (int u = 0; u < REC / 2; u++) {
       const int e = 2 * (u * 64 + lane), r = e / REC, o = e - r * REC;
       lds[r * PITCH + o] = v[u].x; lds[r * PITCH + o + 1] = v[u].y;
+    }
+    } else {
+    double v[REC];
+#pragma unroll
+    for (int u = 0; u < REC; u++) {
+      const int e = u * 64 + lane, r = e / REC;
+      v[u] = (r < nrec) ? g[e] : 0.0;
+    }
+    wave_sync();   // earlier readers of the image are done
+#pragma unroll
+    for (int u = 0; u < REC; u++) {
+      const int e = u * 64 + lane, r = e / REC, o = e - r * REC;
+      lds[r * PITCH + o] = v[u];
+    }
     }
     wave_sync();
   }

@@ -18,6 +18,7 @@
 #endif
 namespace gt {
 namespace {
+static_assert(proj_rec(ProjForm::Planar) == kPlanarRec, "context.h states the record lengths of factors.h");
 static_assert(kSamBearingRange == GTG_SAM_BEARING_RANGE && kSamRange == GTG_SAM_RANGE && kSamBearing == GTG_SAM_BEARING, "factors.h names the sam kinds of the C ABI");
 static_assert(kPartialTranslation == GTG_POSE_PARTIAL_TRANSLATION && kPartialRotation == GTG_POSE_PARTIAL_ROTATION, "factors.h names the partial pose prior kinds of the C ABI");
 
@@ -204,16 +205,35 @@ void layout_variables(gtg_context& c, const gtg_problem& p) {
   c.h_val_off.assign(p.n_vars + 1, 0); c.h_dim_off.assign(p.n_vars + 1, 0);
   for (int v = 0; v < p.n_vars; v++) {
     const int t = p.var_type[v];
-    if (t < 0 || t > GTG_VAR_POSE2) throw std::invalid_argument("unknown variable type");
+    if (t < 0 || t > GTG_VAR_POINT2) throw std::invalid_argument("unknown variable type");
     c.h_val_off[v + 1] = c.h_val_off[v] + storage_size(t);
     c.h_dim_off[v + 1] = c.h_dim_off[v] + tangent_dim(t);
   }
   c.val_size = c.h_val_off[p.n_vars]; c.dim_size = c.h_dim_off[p.n_vars];
   c.user_val_size = c.h_val_off[c.n_user_vars]; c.user_dim_size = c.h_dim_off[c.n_user_vars];
-  up(c.var_type, c.h_var_type, c.stream); up(c.val_off, c.h_val_off, c.stream); up(c.dim_off, c.h_dim_off, c.stream);
+  // on the device a POINT2 is the POINT3 whose slot it is padded to (x, y, 0 / dx, dy, 0): retraction and everything else that reads
+  // var_type there stay as they are; the host keeps the caller's types
+  std::vector<int32_t> dev_type(c.h_var_type);
+  for (int32_t& t : dev_type) if (t == GTG_VAR_POINT2) t = GTG_VAR_POINT3;
+  up(c.var_type, dev_type, c.stream); up(c.val_off, c.h_val_off, c.stream); up(c.dim_off, c.h_dim_off, c.stream);
   c.values.alloc(std::max<int64_t>(c.val_size, 1)); c.trial.alloc(std::max<int64_t>(c.val_size, 1));
   c.delta.alloc(std::max<int64_t>(c.dim_size, 1));
   check_hip(hipMemsetAsync(c.delta.p, 0, sizeof(double) * c.delta.n, c.stream), "memset");
+}
+
+// A planar graph (a POINT2 variable or a planar bearing / range factor) is a graph of POSE2 and POINT2 variables with no other
+// observation: its projection range is ProjForm::Planar (context.h).  Sharding is a follow-up.
+bool check_planar(const gtg_problem& p, int n_shards) {
+  bool planar = p.planar.n_sam2 > 0;
+  for (int v = 0; v < p.n_vars && !planar; v++) planar = p.var_type[v] == GTG_VAR_POINT2;
+  if (!planar) return false;
+  bool other = p.n_sfm > 0 || p.n_proj > 0 || p.n_stereo > 0 || p.n_sam > 0 || p.n_smart > 0;
+  for (int v = 0; v < p.n_vars && !other; v++) other = p.var_type[v] == GTG_VAR_POSE3 || p.var_type[v] == GTG_VAR_SFM_CAMERA || p.var_type[v] == GTG_VAR_POINT3;
+  if (other)
+    throw std::invalid_argument("planar graph: POINT2 variables and planar bearing / range factors cannot share a graph with POSE3, SFM_CAMERA or POINT3 "
+                                "variables or with camera, stereo, 3-D bearing / range or smart factors");
+  if (n_shards > 1) throw std::invalid_argument("planar graph: n_shards > 1 is not supported");
+  return true;
 }
 
 // noise table: derive the inverse sigmas like the reference constructors (NoiseModel.cpp:275-281, Isotropic ctor)
@@ -391,10 +411,43 @@ void upload_sfm(gtg_context& c, HostIndex& hi, const gtg_problem& p, const std::
   hi.sfm_cam = std::move(cam); hi.sfm_point = std::move(pt);
 }
 
-void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, const std::vector<int32_t>& of_obs, const std::vector<uint8_t>& is_rig, const ShardFilter& own) {
+// The projection range of a planar graph: its bearing / range factors <Pose2, Point2> alone, the POSE2 as the "camera".  The factors
+// read no calib or sensor entry; their kinds and measurements (c, s of a Rot2 and a range) go into the buffers of the 3-D sam factors.
+void upload_planar(gtg_context& c, HostIndex& hi, const gtg_problem& p) {
+  auto& f = c.f;
+  f.form = ProjForm::Planar;
+  const int64_t n = p.planar.n_sam2 > 0 ? p.planar.n_sam2 : 0;
+  if (n && (!p.planar.sam2_kind || !p.planar.sam2_pose || !p.planar.sam2_point || !p.planar.sam2_z || !p.planar.sam2_noise)) throw std::invalid_argument("planar bearing / range factor tables missing");
+  std::vector<int32_t> pose, pt, nz, none, kind; std::vector<double> z;
+  for (int64_t i = 0; i < n; i++) {
+    const int k = p.planar.sam2_kind[i];
+    if (k != GTG_SAM_BEARING_RANGE && k != GTG_SAM_RANGE && k != GTG_SAM_BEARING)
+      throw std::invalid_argument("planar bearing / range factor: unknown sam2_kind (GTG_SAM_BEARING_RANGE, GTG_SAM_RANGE or GTG_SAM_BEARING)");
+    const char* what = k == GTG_SAM_BEARING_RANGE ? "BearingRangeFactor2D" : k == GTG_SAM_RANGE ? "RangeFactor2D" : "BearingFactor2D";
+    check_var(p, p.planar.sam2_pose[i]); check_var(p, p.planar.sam2_point[i]);
+    if (p.var_type[p.planar.sam2_pose[i]] != GTG_VAR_POSE2 || p.var_type[p.planar.sam2_point[i]] != GTG_VAR_POINT2)
+      throw std::invalid_argument(std::string(what) + " keys must be (POSE2, POINT2)");
+    check_noise(p, p.planar.sam2_noise[i], sam2_rows(k), what);
+    pose.push_back(p.planar.sam2_pose[i]); pt.push_back(p.planar.sam2_point[i]); nz.push_back(p.planar.sam2_noise[i]); none.push_back(-1);
+    kind.push_back(k);
+    for (int e = 0; e < 3; e++) z.push_back(p.planar.sam2_z[3 * i + e]);
+  }
+  f.n_mono = 0; f.n_cam = 0; f.n_proj = n;
+  c.n_rep_vars = 0; c.rep_var.free(); c.rep_grp_ptr.free(); c.rep_obs_ptr.free(); c.rep_smart.free(); c.rep_obs.free();
+  up(f.sam_kind, kind, c.stream); up(f.sam_z, z, c.stream);
+  up(f.proj_pose, pose, c.stream); up(f.proj_point, pt, c.stream); up(f.proj_noise, nz, c.stream); up(f.proj_calib, none, c.stream);
+  up(f.proj_sensor, none, c.stream);
+  const std::vector<double> empty;
+  up(f.proj_z, empty, c.stream); up(f.calib, empty, c.stream); up(f.sensor, empty, c.stream); f.calib_baseline.free();
+  f.proj_J.alloc(std::max<size_t>((size_t)kPlanarRec * f.n_proj, 1));
+  hi.proj_pose = pose; hi.proj_point = pt;
+}
+
+void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, const std::vector<int32_t>& of_obs, const std::vector<uint8_t>& is_rig, const ShardFilter& own, bool planar) {
   auto& f = c.f;
   std::vector<int32_t> pose, pt, nz, cal, sen; std::vector<double> z;
   const int64_t n_stereo = p.n_stereo > 0 ? p.n_stereo : 0, n_sam = p.n_sam > 0 ? p.n_sam : 0;
+  if (planar) { upload_planar(c, hi, p); return; }
   f.form = n_sam > 0 ? ProjForm::Rows3Sam : n_stereo > 0 ? ProjForm::Rows3 : c.smart_pose ? ProjForm::Rows2Smart : ProjForm::Rows2;   // from the WHOLE graph (context.h; SmartView has refused smart_pose beside the other two)
   static_assert(proj_rec(ProjForm::Rows2) == kProjRec && proj_rec(ProjForm::Rows3) == kStereoRec, "context.h states the record lengths of factors.h");
   for (int64_t i = 0; i < p.n_proj; i++) {
@@ -489,7 +542,9 @@ void upload_priors(gtg_context& c, HostIndex& hi, const gtg_problem& p, const Sh
   std::vector<int32_t> var, nz; std::vector<int64_t> poff; std::vector<double> data;
   for (int64_t i = 0; i < p.n_prior; i++) {
     const int v = p.prior_var[i];
-    check_var(p, v); check_noise(p, p.prior_noise[i], tangent_dim(p.var_type[v]), "PriorFactor");
+    check_var(p, v);
+    if (p.var_type[v] == GTG_VAR_POINT2) throw std::invalid_argument("PriorFactor on a POINT2 variable is not supported");
+    check_noise(p, p.prior_noise[i], tangent_dim(p.var_type[v]), "PriorFactor");
     if (own.n_shards > 1 && !own.owns_prior(v, i)) continue;
     var.push_back(v); nz.push_back(p.prior_noise[i]); poff.push_back((int64_t)data.size());
     const double* d = p.prior_data + p.prior_off[i];
@@ -547,7 +602,8 @@ void upload_problem(gtg_context& c, const gtg_problem& user, int shard, int n_sh
   // GeneralSFM records recomputed where they are needed instead of stored (fused.h) -- not with smart factors, whose measurements'
   // records depend on the factor's triangulation status, and not beside stereo or bearing / range factors, whose three-row records
   // only the stored-record kernels read
-  c.fused_sfm = GTG_FUSED_SFM != 0 && c.n_smart == 0 && !(user.n_stereo > 0) && !(user.n_sam > 0);
+  const bool planar = check_planar(user, n_shards);   // (its own records and kernels: context.h ProjForm::Planar)
+  c.fused_sfm = GTG_FUSED_SFM != 0 && c.n_smart == 0 && !(user.n_stereo > 0) && !(user.n_sam > 0) && !planar;
   const SmartView view(user);
   const gtg_problem& p = view.problem();
   c.smart_pose = view.pose; c.smart_repeats = view.repeats; c.smart_obs0 = view.pose ? user.n_proj : user.n_sfm;
@@ -559,7 +615,7 @@ void upload_problem(gtg_context& c, const gtg_problem& user, int shard, int n_sh
   keep_whole_graph_keys(hi, p, n_shards);
   SideUpload side;   // started by upload_sfm for a whole, non-empty table
   upload_sfm(c, hi, p, view.of_obs, own, side);
-  upload_projection(c, hi, p, view.of_obs, view.is_rig, own);
+  upload_projection(c, hi, p, view.of_obs, view.is_rig, own, planar);
   upload_between(c, hi, p, own);
   upload_priors(c, hi, p, own);
   clk.lap("factor tables (shard filter + upload)");

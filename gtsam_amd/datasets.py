@@ -1225,3 +1225,154 @@ def pose_partial_graph2d(n_poses=83, n_closures=9, seed=0):
         graph.add(A.PoseRotationPrior2D(X(i), pose_z, model))
         k += 1
     return graph, initial, info
+
+
+# ---- planar landmark SLAM: BearingRangeFactor / RangeFactor / BearingFactor <Pose2, Point2> ----------------------------------------
+def _pose2_between(a, b):
+    """(x, y, theta) of a^-1 b for two (x, y, theta) rows."""
+    c, s = np.cos(a[2]), np.sin(a[2])
+    d = b[:2] - a[:2]
+    dth = b[2] - a[2]
+    return np.array([c * d[0] + s * d[1], -s * d[0] + c * d[1], np.arctan2(np.sin(dth), np.cos(dth))])
+
+
+def _add_sam2(graph, rng, kind, pose_key, point_key, q, model, bearing_sigma, range_sigma):
+    """One planar bearing / range factor of `kind` (0 bearing-range, 1 range, 2 bearing) with a noisy measurement of the local point q."""
+    from . import api as A
+    b = A.Rot2.fromAngle(float(np.arctan2(q[1], q[0])) + bearing_sigma * rng.normal())
+    r = float(np.hypot(q[0], q[1])) + range_sigma * rng.normal()
+    if kind == 0:
+        graph.add(A.BearingRangeFactor2D(pose_key, point_key, b, r, model))
+    elif kind == 1:
+        graph.add(A.RangeFactor2D(pose_key, point_key, r, model))
+    else:
+        graph.add(A.BearingFactor2D(pose_key, point_key, b, model))
+
+
+def planar_mixed_graph(n_poses=11, n_points=30, seed=5, views=8, bearing_sigma=0.01, range_sigma=0.03):
+    """A small planar graph that enters every branch of BearingRangeFactor / RangeFactor / BearingFactor <Pose2, Point2> on the device,
+    built through the API mirror: a robot on an arc sees its `views` nearest landmarks by a factor of every kind in turn; dim-2 and dim-1
+    Unit, Isotropic, Diagonal and full Gaussian noise, one Robust(Huber) and one Robust(Cauchy); a BetweenFactorPose2 chain, one
+    PriorFactorPose2 and two 2-D partial priors.  One more pose, X(n_poses), starts with theta = 0 and a translation of binary fractions,
+    so that what it predicts for three more landmarks is exact in floating point:
+      L(n_points)      at t + (3, 4): the predicted Rot2 is (3/5, 4/5) and the measured one holds the same two doubles ("same");
+      L(n_points + 1)  starts ON the pose: a BearingFactor2D (relativeBearing below 1e-5: a zero Jacobian, "bearing_zero") and a
+                       RangeFactor2D (norm2 at 0: the Jacobian (1, 1), "range_zero") see it there; the landmark itself lies elsewhere and two
+                       other poses see it;
+      L(n_points + 2)  behind the pose, a little to the left (predicted bearing just below pi) with a measured bearing just above -pi:
+                       the residual crosses the cut ("wrap").
+    Graph order: planar factors, between, prior, partial priors.  Returns (graph, initial values, {branch name: index among the planar
+    factors})."""
+    from . import api as A
+    rng = np.random.default_rng(seed)
+    X, L = A.symbol_shorthand.X, A.symbol_shorthand.L
+    nm = A.noiseModel
+    ang = np.linspace(0.3, 2.4, n_poses)
+    poses = np.stack([7 * np.cos(ang), 7 * np.sin(ang), ang + np.pi / 2 + 0.05 * rng.normal(size=n_poses)], 1)
+    t_id = np.array([0.5, -0.25])
+    poses = np.concatenate([poses, [[t_id[0], t_id[1], 0.0]]])
+    rad = rng.uniform(3.0, 11.0, n_points); phi = rng.uniform(0.0, 2.7, n_points)
+    pts = np.stack([rad * np.cos(phi), rad * np.sin(phi)], 1)
+    special = t_id + np.array([[3.0, 4.0], [1.5, 1.0], [-3.0, 0.015625]])       # where the three branch landmarks are
+    special0 = np.array([special[0], t_id, special[2]])                         # ... and where they start
+    pts = np.concatenate([pts, special])
+    R2 = np.array([[80.0, 9.0], [0.0, 30.0]])
+    models = {0: [nm.Unit.Create(2), nm.Isotropic.Sigma(2, 0.05), nm.Diagonal.Sigmas([bearing_sigma, range_sigma]), nm.Gaussian.SqrtInformation(R2),
+                  nm.Robust.Create(nm.mEstimator.Huber.Create(1.345), nm.Diagonal.Sigmas([0.012, 0.04]))],
+              1: [nm.Unit.Create(1), nm.Isotropic.Sigma(1, range_sigma), nm.Diagonal.Sigmas([0.05], False), nm.Gaussian.SqrtInformation([[25.0]], False),
+                  nm.Robust.Create(nm.mEstimator.Cauchy.Create(0.8), nm.Isotropic.Sigma(1, 0.04))],
+              2: [nm.Unit.Create(1), nm.Isotropic.Sigma(1, bearing_sigma), nm.Diagonal.Sigmas([0.02], False), nm.Gaussian.SqrtInformation([[70.0]], False)]}
+
+    def local(i, j):
+        c, s = np.cos(poses[i, 2]), np.sin(poses[i, 2])
+        d = pts[j] - poses[i, :2]
+        return np.array([c * d[0] + s * d[1], -s * d[0] + c * d[1]])
+
+    graph, initial = A.NonlinearFactorGraph(), A.Values()
+    k, count = 0, {0: 0, 1: 0, 2: 0}
+    for i in range(n_poses):
+        near = np.argsort(np.linalg.norm(pts[:n_points] - poses[i, :2], axis=1))[:views]
+        for j in sorted(int(j) for j in near):
+            kind = k % 3
+            _add_sam2(graph, rng, kind, X(i), L(j), local(i, j), models[kind][count[kind] % len(models[kind])], bearing_sigma, range_sigma)
+            count[kind] += 1; k += 1
+    for j in range(n_points):                                  # every landmark is seen at least twice with a bearing and a range
+        for i in (j % n_poses, (j + 5) % n_poses):
+            _add_sam2(graph, rng, 0, X(i), L(j), local(i, j), models[0][2], bearing_sigma, range_sigma); k += 1
+    for j in range(3):                                         # the branch landmarks from two poses of the arc
+        for i in (1, n_poses - 2):
+            _add_sam2(graph, rng, 0, X(i), L(n_points + j), local(i, n_points + j), models[0][2], bearing_sigma, range_sigma); k += 1
+    branch = {"same": k, "bearing_zero": k + 1, "range_zero": k + 2, "wrap": k + 3}
+    graph.add(A.BearingRangeFactor2D(X(n_poses), L(n_points), A.Rot2.fromCosSin(3.0 / 5.0, 4.0 / 5.0), 5.0 + range_sigma * rng.normal(), models[0][2]))
+    q1 = special[1] - t_id
+    graph.add(A.BearingFactor2D(X(n_poses), L(n_points + 1), A.Rot2.fromAngle(float(np.arctan2(q1[1], q1[0])) + bearing_sigma * rng.normal()), nm.Isotropic.Sigma(1, 0.2)))
+    graph.add(A.RangeFactor2D(X(n_poses), L(n_points + 1), float(np.hypot(q1[0], q1[1])) + range_sigma * rng.normal(), nm.Isotropic.Sigma(1, 0.5)))
+    graph.add(A.BearingFactor2D(X(n_poses), L(n_points + 2), A.Rot2.fromAngle(-(np.pi - 0.015)), nm.Isotropic.Sigma(1, 0.05)))
+    n_odo = nm.Diagonal.Sigmas([0.05, 0.05, 0.02]); n_odo_g = nm.Gaussian.SqrtInformation(np.array([[20.0, 2.0, -1.0], [0.0, 18.0, 3.0], [0.0, 0.0, 45.0]]))
+    for i in range(n_poses):
+        z = _pose2_between(poses[i], poses[i + 1]) + rng.normal(0, [0.03, 0.03, 0.01])
+        graph.add(A.BetweenFactorPose2(X(i), X(i + 1), A.Pose2(*z), n_odo_g if i % 3 == 1 else n_odo))
+    graph.addPriorPose2(X(0), A.Pose2(*poses[0]), nm.Diagonal.Sigmas([0.02, 0.02, 0.01]))
+    graph.add(A.PoseTranslationPrior2D(X(n_poses), A.Point2(*t_id), nm.Isotropic.Sigma(2, 0.02)))
+    graph.add(A.PoseRotationPrior2D(X(n_poses), A.Rot2.fromAngle(0.0), nm.Isotropic.Sigma(1, 0.01)))
+    for i in range(n_poses):
+        initial.insert(X(i), A.Pose2(*(poses[i] + rng.normal(0, [0.08, 0.08, 0.02]))))
+    initial.insert(X(n_poses), A.Pose2(t_id[0], t_id[1], 0.0))
+    for j in range(n_points):
+        initial.insert(L(j), A.Point2(*(pts[j] + rng.normal(0, 0.1, 2))))
+    for j in range(3):
+        initial.insert(L(n_points + j), A.Point2(*special0[j]))
+    return graph, initial, branch
+
+
+def planar_slam_graph(n_poses=40, n_points=120, seed=11, views=9, bearing_sigma=0.01, range_sigma=0.05):
+    """Planar landmark SLAM: a robot once round a circle with odometry (BetweenFactorPose2) and a prior on its first pose; every
+    landmark is seen from its `views` nearest poses by a BearingRangeFactor2D, a RangeFactor2D or a BearingFactor2D in turn (the first
+    view of every landmark is a bearing-range one).  The graph of a 2-D lidar front end.  Returns (graph, initial values)."""
+    from . import api as A
+    rng = np.random.default_rng(seed)
+    X, L = A.symbol_shorthand.X, A.symbol_shorthand.L
+    nm = A.noiseModel
+    th = np.linspace(0.0, 1.8 * np.pi, n_poses)
+    poses = np.stack([12 * np.cos(th), 12 * np.sin(th), th + np.pi / 2 + 0.03 * rng.normal(size=n_poses)], 1)
+    poses[:, 2] = np.arctan2(np.sin(poses[:, 2]), np.cos(poses[:, 2]))
+    rad = rng.uniform(5.0, 19.0, n_points); phi = rng.uniform(0.0, 1.8 * np.pi, n_points)
+    pts = np.stack([rad * np.cos(phi), rad * np.sin(phi)], 1)
+    models = {0: nm.Diagonal.Sigmas([bearing_sigma, range_sigma]), 1: nm.Isotropic.Sigma(1, range_sigma), 2: nm.Isotropic.Sigma(1, bearing_sigma)}
+    odo = nm.Diagonal.Sigmas([0.05, 0.05, 0.01])
+    graph, initial = A.NonlinearFactorGraph(), A.Values()
+    for j in range(n_points):
+        near = np.argsort(np.linalg.norm(poses[:, :2] - pts[j], axis=1))[:views]
+        for k, i in enumerate(sorted(int(i) for i in near)):
+            c, s = np.cos(poses[i, 2]), np.sin(poses[i, 2])
+            d = pts[j] - poses[i, :2]
+            _add_sam2(graph, rng, k % 3, X(i), L(j), np.array([c * d[0] + s * d[1], -s * d[0] + c * d[1]]), models[k % 3], bearing_sigma, range_sigma)
+    for i in range(n_poses - 1):
+        graph.add(A.BetweenFactorPose2(X(i), X(i + 1), A.Pose2(*(_pose2_between(poses[i], poses[i + 1]) + rng.normal(0, [0.04, 0.04, 0.01]))), odo))
+    graph.addPriorPose2(X(0), A.Pose2(*poses[0]), nm.Diagonal.Sigmas([0.02, 0.02, 0.01]))
+    for i in range(n_poses):
+        v = poses[i] + rng.normal(0, [0.1, 0.1, 0.03])
+        initial.insert(X(i), A.Pose2(v[0], v[1], float(np.arctan2(np.sin(v[2]), np.cos(v[2])))))
+    for j in range(n_points):
+        initial.insert(L(j), A.Point2(*(pts[j] + rng.normal(0, 0.2, 2))))
+    return graph, initial
+
+
+def planar_slam_example():
+    """The graph of the reference's examples/PlanarSLAMExample.cpp: three poses with a prior and two odometry factors, two landmarks
+    seen by three BearingRangeFactor2D.  Returns (graph, initial values)."""
+    from . import api as A
+    X, L = A.symbol_shorthand.X, A.symbol_shorthand.L
+    nm = A.noiseModel
+    graph, initial = A.NonlinearFactorGraph(), A.Values()
+    graph.addPriorPose2(X(1), A.Pose2(0.0, 0.0, 0.0), nm.Diagonal.Sigmas([0.3, 0.3, 0.1]))
+    odo = nm.Diagonal.Sigmas([0.2, 0.2, 0.1])
+    graph.add(A.BetweenFactorPose2(X(1), X(2), A.Pose2(2.0, 0.0, 0.0), odo))
+    graph.add(A.BetweenFactorPose2(X(2), X(3), A.Pose2(2.0, 0.0, 0.0), odo))
+    meas = nm.Diagonal.Sigmas([0.1, 0.2])
+    graph.add(A.BearingRangeFactor2D(X(1), L(1), A.Rot2.fromAngle(np.pi * 45 / 180), np.sqrt(4.0 + 4.0), meas))
+    graph.add(A.BearingRangeFactor2D(X(2), L(1), A.Rot2.fromAngle(np.pi * 90 / 180), 2.0, meas))
+    graph.add(A.BearingRangeFactor2D(X(3), L(2), A.Rot2.fromAngle(np.pi * 90 / 180), 2.0, meas))
+    initial.insert(X(1), A.Pose2(0.5, 0.0, 0.2)); initial.insert(X(2), A.Pose2(2.3, 0.1, -0.2)); initial.insert(X(3), A.Pose2(4.1, 0.1, 0.1))
+    initial.insert(L(1), A.Point2(1.8, 2.1)); initial.insert(L(2), A.Point2(4.1, 1.8))
+    return graph, initial

@@ -81,6 +81,9 @@ typedef GenericStereoFactor<Pose3, Point3> StereoFactor;
 typedef BearingRangeFactor<Pose3, Point3> SamBearingRangeFactor;   // gtsam/sam: wrapped as BearingRangeFactor3D, RangeFactor3D, BearingFactor3D
 typedef RangeFactor<Pose3, Point3> SamRangeFactor;
 typedef BearingFactor<Pose3, Point3> SamBearingFactor;
+typedef BearingRangeFactor<Pose2, Point2> Sam2BearingRangeFactor;   // planar: wrapped as BearingRangeFactor2D, RangeFactor2D, BearingFactor2D
+typedef RangeFactor<Pose2, Point2> Sam2RangeFactor;
+typedef BearingFactor<Pose2, Point2> Sam2BearingFactor;
 // partial pose priors (gtsam/slam): wrapped as PoseTranslationPrior3D / 2D and PoseRotationPrior3D / 2D
 typedef PoseTranslationPrior<Pose3> TranslationPrior3;
 typedef PoseRotationPrior<Pose3> RotationPrior3;
@@ -158,7 +161,8 @@ void packCamera(const SfmCamera& c, double* p) {
 // ---- variable types (GTG_VAR_*), each fact once: which Values are of one, its storage size and tangent dimension, to doubles and back
 int32_t classify(const Value* v) {   // -1: a type outside the GPU path
   return dynamic_cast<const GenericValue<Point3>*>(v) ? GTG_VAR_POINT3 : dynamic_cast<const GenericValue<SfmCamera>*>(v) ? GTG_VAR_SFM_CAMERA :
-         dynamic_cast<const GenericValue<Pose3>*>(v) ? GTG_VAR_POSE3 : dynamic_cast<const GenericValue<Pose2>*>(v) ? GTG_VAR_POSE2 : -1;
+         dynamic_cast<const GenericValue<Pose3>*>(v) ? GTG_VAR_POSE3 : dynamic_cast<const GenericValue<Pose2>*>(v) ? GTG_VAR_POSE2 :
+         dynamic_cast<const GenericValue<Point2>*>(v) ? GTG_VAR_POINT2 : -1;
 }
 template <class T> struct VarTypeOf;
 template <> struct VarTypeOf<Pose3> { static constexpr int32_t value = GTG_VAR_POSE3; };
@@ -167,6 +171,9 @@ template <> struct VarTypeOf<Point3> { static constexpr int32_t value = GTG_VAR_
 template <> struct VarTypeOf<Pose2> { static constexpr int32_t value = GTG_VAR_POSE2; };
 constexpr int storageSize(int32_t t) { return t == GTG_VAR_POSE3 ? 12 : t == GTG_VAR_SFM_CAMERA ? 17 : 3; }
 constexpr int tangentDim(int32_t t) { return t == GTG_VAR_POSE3 ? 6 : t == GTG_VAR_SFM_CAMERA ? 9 : 3; }
+// A Point2 is padded to the landmark slot at the C ABI: (x, y, 0) and (dx, dy, 0).  The padding never leaves this file: the caller's
+// Values hold a Point2, a VectorValues entry of it two numbers, a Jacobian block on it two columns.
+constexpr int userDim(int32_t t) { return t == GTG_VAR_POINT2 ? 2 : tangentDim(t); }
 // an object of a variable's type (a value, a prior, a measurement) as storageSize() doubles; payload(): of a Value whose type the caller knows, no check
 void packAs(const Point3& q, double* p) { p[0] = q.x(); p[1] = q.y(); p[2] = q.z(); }
 void packAs(const Pose2& q, double* p) { p[0] = q.x(); p[1] = q.y(); p[2] = q.theta(); }
@@ -178,25 +185,32 @@ void pack(int32_t t, const Value& v, double* p) {
   if (t == GTG_VAR_POINT3) packAs(payload<Point3>(v), p);
   else if (t == GTG_VAR_SFM_CAMERA) packAs(payload<SfmCamera>(v), p);
   else if (t == GTG_VAR_POSE3) packAs(payload<Pose3>(v), p);
+  else if (t == GTG_VAR_POINT2) { const Point2& q = payload<Point2>(v); p[0] = q.x(); p[1] = q.y(); p[2] = 0.0; }
   else packAs(payload<Pose2>(v), p);
 }
 void unpack(int32_t t, const double* p, Value& v) {
   if (t == GTG_VAR_POINT3) payload<Point3>(v) = Point3(p[0], p[1], p[2]);
   else if (t == GTG_VAR_SFM_CAMERA) payload<SfmCamera>(v) = SfmCamera(unpackPose(p), Cal3Bundler(p[12], p[13], p[14], p[15], p[16]));
   else if (t == GTG_VAR_POSE3) payload<Pose3>(v) = unpackPose(p);
+  else if (t == GTG_VAR_POINT2) payload<Point2>(v) = Point2(p[0], p[1]);
   else payload<Pose2>(v) = Pose2(p[0], p[1], p[2]);
 }
 // ---- Jacobian records (gtg_get_jacobians): one whitened [A1 | A2 | b] per factor, row-major blocks at fixed offsets; the record's width follows
 // the factor type, the block sizes the factor's first variable (Pose2: 3x3 blocks inside the record of the Pose3 factor)
-constexpr int kFacTypes = 7;
-const int64_t kRecordWidth[kFacTypes] = {26, 20, 78, 90, 30, 30, 90};   // by GTG_FAC_*
-struct RecordLayout { int rows, nblk, boff[2], bcols[2], rhs; int64_t width; };
+constexpr int kFacTypes = 8;
+const int64_t kRecordWidth[kFacTypes] = {26, 20, 78, 90, 30, 30, 90, 21};   // by GTG_FAC_*
+struct RecordLayout {
+  int rows, nblk, boff[2], bcols[2], rhs; int64_t width;
+  int bpitch[2] = {0, 0};   // doubles from one row of a block to the next where that is not bcols (the padded landmark block of a planar record)
+  int pitch(int k) const { return bpitch[k] ? bpitch[k] : bcols[k]; }
+};
 template <class F> RecordLayout recordLayout(int32_t fac, F&& firstVarType) {   // firstVarType(): GTG_VAR_* of the factor's first variable, asked only where the layout depends on it
   const int64_t w = kRecordWidth[fac];
   if (fac == GTG_FAC_GENERAL_SFM) return {2, 2, {0, 18}, {tangentDim(GTG_VAR_SFM_CAMERA), 3}, 24, w};
   if (fac == GTG_FAC_PROJECTION) return {2, 2, {0, 12}, {tangentDim(GTG_VAR_POSE3), 3}, 18, w};
   if (fac == GTG_FAC_STEREO) return {3, 2, {0, 18}, {tangentDim(GTG_VAR_POSE3), 3}, 27, w};
   if (fac == GTG_FAC_SAM) return {3, 2, {0, 18}, {tangentDim(GTG_VAR_POSE3), 3}, 27, w};   // (rows: the caller puts the kind's 3, 1 or 2 -- Impl::layoutOf)
+  if (fac == GTG_FAC_SAM2) return {2, 2, {0, 9}, {tangentDim(GTG_VAR_POSE2), userDim(GTG_VAR_POINT2)}, 18, w, {0, 3}};   // (rows: the kind's 2 or 1)
   const int d = tangentDim(firstVarType());
   if (fac == GTG_FAC_BETWEEN_POSE3) return {d, 2, {0, 36}, {d, d}, 72, w};
   return {d, 1, {0, 0}, {d, 0}, 81, w};   // PRIOR, and POSE_PARTIAL (rows: the caller puts the factor's 3, 2 or 1 -- Impl::layoutOf)
@@ -281,9 +295,11 @@ struct GpuLevenbergMarquardtOptimizer::Impl {
   void takeScalars(const State& s) { error = s.error; lambda = s.lambda; factor = s.currentFactor; iterations = s.iterations; inner = s.totalNumberInnerIterations; }
   std::vector<int32_t> sam_kind;         // GTG_SAM_* by row of the sam table: a bearing / range record has its kind's 3, 1 or 2 rows
   std::vector<int32_t> pp_kind;          // GTG_POSE_PARTIAL_* by row of the partial pose prior table: 3 rows on a Pose3, 2 or 1 on a Pose2
+  std::vector<int32_t> sam2_kind;        // GTG_SAM_* by row of the planar sam table: 2 rows for a bearing-range record, else 1
   RecordLayout layoutOf(const std::pair<int32_t, int64_t>& tf, Key first) const {
     RecordLayout lay = recordLayout(tf.first, [&] { return var_type[idOf(keys, first)]; });
     if (tf.first == GTG_FAC_SAM) lay.rows = sam_kind[(size_t)tf.second] == GTG_SAM_BEARING_RANGE ? 3 : sam_kind[(size_t)tf.second] == GTG_SAM_RANGE ? 1 : 2;
+    if (tf.first == GTG_FAC_SAM2) lay.rows = sam2_kind[(size_t)tf.second] == GTG_SAM_BEARING_RANGE ? 2 : 1;
     if (tf.first == GTG_FAC_POSE_PARTIAL) lay.rows = lay.bcols[0] == 6 ? 3 : pp_kind[(size_t)tf.second] == GTG_POSE_PARTIAL_TRANSLATION ? 2 : 1;
     return lay;
   }
@@ -387,13 +403,13 @@ namespace {
 // calibrations as (run length, object) -- rows of the shared tables are handed out afterwards, sequentially, in first-occurrence
 // order, so that the tables are those of a single-threaded pass whatever the thread count.
 struct Extract {
-  std::vector<int32_t> sfm_cam, sfm_pt, pj_pose, pj_pt, pj_sen, st_pose, st_pt, st_sen, sam_kind, sam_pose, sam_pt, bt_1, bt_2, pr_var, sm_cam, pp_kind, pp_var;
-  std::vector<double> sfm_z, pj_z, st_z, sam_z, sensor, bt_z, pr_data, sm_z, sm_prm, pp_z;
+  std::vector<int32_t> sfm_cam, sfm_pt, pj_pose, pj_pt, pj_sen, st_pose, st_pt, st_sen, sam_kind, sam_pose, sam_pt, bt_1, bt_2, pr_var, sm_cam, pp_kind, pp_var, s2_kind, s2_pose, s2_pt;
+  std::vector<double> sfm_z, pj_z, st_z, sam_z, sensor, bt_z, pr_data, sm_z, sm_prm, pp_z, s2_z;
   std::vector<int64_t> pr_off, sm_ptr;
   FactorMap fac_map;                                                        // (type, index in THIS chunk's table of that type)
   typedef std::vector<std::pair<int64_t, SharedNoiseModel>> Runs;
-  Runs sfm_nz, pj_nz, st_nz, sam_nz, bt_nz, pr_nz, sm_nz, pp_nz;
-  std::vector<int32_t> bt_dim, pr_dim, sam_dim, pp_dim;                     // expected noise dimension per between / prior / sam / partial prior factor
+  Runs sfm_nz, pj_nz, st_nz, sam_nz, bt_nz, pr_nz, sm_nz, pp_nz, s2_nz;
+  std::vector<int32_t> bt_dim, pr_dim, sam_dim, pp_dim, s2_dim;             // expected noise dimension per between / prior / sam / partial prior / planar sam factor
   std::vector<std::pair<const void*, int>> pj_cal;                          // calibration object per projection factor, 1 = Cal3DS2
   std::vector<const Cal3_S2Stereo*> st_cal;                                 // calibration object per stereo factor
   std::vector<const Cal3_S2*> sm_cal;                                       // per smart factor: the shared K of a pose-type factor, null for a camera-type one
@@ -447,6 +463,16 @@ void addSam(Extract& x, int32_t kind, Key pose, Key point, const Unit3* bearing,
   if (bearing) { const Vector3 u = bearing->unitVector(); z[0] = u(0); z[1] = u(1); z[2] = u(2); }
   if (range) z[3] = *range;
   Extract::run(x.sam_nz, nm); x.sam_dim.push_back(kind == GTG_SAM_BEARING_RANGE ? 3 : kind == GTG_SAM_RANGE ? 1 : 2);
+}
+// BearingRangeFactor / RangeFactor / BearingFactor <Pose2, Point2> (gtsam/sam, planar): one row of the sam2 table; bearing: the measured
+// Rot2 or null -- its (c, s) as the reference holds them --, range: the measured range or null
+void addSam2(Extract& x, int32_t kind, Key pose, Key point, const Rot2* bearing, const double* range, const SharedNoiseModel& nm, const std::vector<Key>& keys) {
+  x.fac_map.emplace_back(GTG_FAC_SAM2, (int64_t)x.s2_pose.size());
+  x.s2_kind.push_back(kind); x.s2_pose.push_back(idOf(keys, pose)); x.s2_pt.push_back(idOf(keys, point));
+  double* z = Extract::grow(x.s2_z, 3);
+  if (bearing) { z[0] = bearing->c(); z[1] = bearing->s(); }
+  if (range) z[2] = *range;
+  Extract::run(x.s2_nz, nm); x.s2_dim.push_back(kind == GTG_SAM_BEARING_RANGE ? 2 : 1);
 }
 // the rows every smart factor has, whatever its camera type: parameters, noise model, keys and measurements
 template <class FACTOR>
@@ -529,6 +555,9 @@ void addFactor(Extract& x, const NonlinearFactor* f, const std::vector<Key>& key
   else if (auto br = dynamic_cast<const SamBearingRangeFactor*>(f)) { const Unit3 u = br->measured().bearing(); const double r = br->measured().range(); addSam(x, GTG_SAM_BEARING_RANGE, br->keys()[0], br->keys()[1], &u, &r, br->noiseModel(), keys); }
   else if (auto rf = dynamic_cast<const SamRangeFactor*>(f)) { const double r = rf->measured(); addSam(x, GTG_SAM_RANGE, rf->keys()[0], rf->keys()[1], nullptr, &r, rf->noiseModel(), keys); }
   else if (auto bf = dynamic_cast<const SamBearingFactor*>(f)) addSam(x, GTG_SAM_BEARING, bf->keys()[0], bf->keys()[1], &bf->measured(), nullptr, bf->noiseModel(), keys);
+  else if (auto br2 = dynamic_cast<const Sam2BearingRangeFactor*>(f)) { const Rot2 u = br2->measured().bearing(); const double r = br2->measured().range(); addSam2(x, GTG_SAM_BEARING_RANGE, br2->keys()[0], br2->keys()[1], &u, &r, br2->noiseModel(), keys); }
+  else if (auto rf2 = dynamic_cast<const Sam2RangeFactor*>(f)) { const double r = rf2->measured(); addSam2(x, GTG_SAM_RANGE, rf2->keys()[0], rf2->keys()[1], nullptr, &r, rf2->noiseModel(), keys); }
+  else if (auto bf2 = dynamic_cast<const Sam2BearingFactor*>(f)) addSam2(x, GTG_SAM_BEARING, bf2->keys()[0], bf2->keys()[1], &bf2->measured(), nullptr, bf2->noiseModel(), keys);
   else if (auto sf = dynamic_cast<const SmartFactor*>(f)) addSmart(x, *sf, keys);
   else if (auto sp = dynamic_cast<const SmartPoseFactor*>(f)) addSmartPose(x, *sp, keys);
   else if (auto sr = dynamic_cast<const SmartRigFactor*>(f)) addSmartRig(x, *sr, keys);
@@ -544,7 +573,7 @@ void addFactor(Extract& x, const NonlinearFactor* f, const std::vector<Key>& key
   else if (auto p3 = dynamic_cast<const PriorFactor<Point3>*>(f)) addPrior(x, *p3, keys);
   else throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: factor type outside the GPU hot path "   // (anything else is a hard error)
                                    "(supported: GeneralSFMFactor<SfmCamera,Point3>, GenericProjectionFactor<Pose3,Point3,Cal3_S2|Cal3DS2>, "
-                                   "GenericStereoFactor<Pose3,Point3>, BearingRangeFactor|RangeFactor|BearingFactor<Pose3,Point3>, SmartProjectionFactor<SfmCamera>, SmartProjectionPoseFactor<Cal3_S2>, SmartProjectionRigFactor<PinholePose<Cal3_S2>>, BetweenFactor<Pose3|Pose2>, PriorFactor<Pose3|Pose2|SfmCamera|Point3>, PoseTranslationPrior|PoseRotationPrior<Pose3|Pose2>)");
+                                   "GenericStereoFactor<Pose3,Point3>, BearingRangeFactor|RangeFactor|BearingFactor<Pose3,Point3> and <Pose2,Point2>, SmartProjectionFactor<SfmCamera>, SmartProjectionPoseFactor<Cal3_S2>, SmartProjectionRigFactor<PinholePose<Cal3_S2>>, BetweenFactor<Pose3|Pose2>, PriorFactor<Pose3|Pose2|SfmCamera|Point3>, PoseTranslationPrior|PoseRotationPrior<Pose3|Pose2>)");
 }
 // The factors [b, e) of `graph` into x, each pointer also copied into `graphCopy`; the chunk stops at its first offending factor and keeps what that threw.
 void extractChunk(Extract& x, const NonlinearFactorGraph& graph, NonlinearFactorGraph& graphCopy, const std::vector<Key>& keys, size_t b, size_t e) {
@@ -573,13 +602,13 @@ template <class T> struct Raw {
   T* data() const { return p.get(); } size_t size() const { return n; }
 };
 typedef Raw<int32_t> RawI; typedef Raw<double> RawD;
-struct Place { int64_t o_sfm, o_pj, o_st, o_sam, o_bt, o_pr, o_sm, o_pp; std::vector<std::pair<int64_t, int32_t>> sfm_rows; };   // per chunk: offsets of its tables, (count, noise row) of its GeneralSFM runs
+struct Place { int64_t o_sfm, o_pj, o_st, o_sam, o_bt, o_pr, o_sm, o_pp, o_s2; std::vector<std::pair<int64_t, int32_t>> sfm_rows; };   // per chunk: offsets of its tables, (count, noise row) of its GeneralSFM runs
 struct HostProblem {
   NoiseTable nt;
   RawI sfm_cam, sfm_pt, sfm_nz;
   RawD sfm_z;
-  std::vector<int32_t> pj_pose, pj_pt, pj_nz, pj_cal, pj_sen, st_pose, st_pt, st_nz, st_cal, st_sen, sam_kind, sam_pose, sam_pt, sam_nz, bt_1, bt_2, bt_nz, pr_var, pr_nz, sm_cam, sm_nz, sm_cal, sm_sen, sm_mcal, sm_msen, pp_kind, pp_var, pp_nz;
-  std::vector<double> pj_z, st_z, sam_z, calib, sensor, rig_sensor, bt_z, pr_data, sm_z, sm_prm, pp_z;   // (rig_sensor: the rigs' extrinsics, appended to `sensor` behind every chunk's rows)
+  std::vector<int32_t> pj_pose, pj_pt, pj_nz, pj_cal, pj_sen, st_pose, st_pt, st_nz, st_cal, st_sen, sam_kind, sam_pose, sam_pt, sam_nz, bt_1, bt_2, bt_nz, pr_var, pr_nz, sm_cam, sm_nz, sm_cal, sm_sen, sm_mcal, sm_msen, pp_kind, pp_var, pp_nz, s2_kind, s2_pose, s2_pt, s2_nz;
+  std::vector<double> pj_z, st_z, sam_z, calib, sensor, rig_sensor, bt_z, pr_data, sm_z, sm_prm, pp_z, s2_z;   // (rig_sensor: the rigs' extrinsics, appended to `sensor` behind every chunk's rows)
   std::vector<int64_t> pr_off, sm_ptr{0};    // (smart factors: one track each)
   bool any_smart_pose = false;               // a SmartProjectionPoseFactor: the smart_calib / smart_sensor tables go to the library
   bool any_smart_rig = false;                // a SmartProjectionRigFactor: sm_mcal / sm_msen (per smart measurement) go to the library too
@@ -642,6 +671,8 @@ struct HostProblem {
     pb.n_prior = (int64_t)pr_var.size(); pb.prior_var = pr_var.data(); pb.prior_off = pr_off.data(); pb.prior_data = pr_data.data(); pb.prior_noise = pr_nz.data();
     pb.n_pose_partial = (int64_t)pp_var.size();
     if (pb.n_pose_partial) { pb.pose_partial_kind = pp_kind.data(); pb.pose_partial_var = pp_var.data(); pb.pose_partial_z = pp_z.data(); pb.pose_partial_noise = pp_nz.data(); }
+    pb.planar.n_sam2 = (int64_t)s2_pose.size();
+    if (pb.planar.n_sam2) { pb.planar.sam2_kind = s2_kind.data(); pb.planar.sam2_pose = s2_pose.data(); pb.planar.sam2_point = s2_pt.data(); pb.planar.sam2_z = s2_z.data(); pb.planar.sam2_noise = s2_nz.data(); }
     return pb;
   }
 };
@@ -751,7 +782,7 @@ HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap
     }
     for (const auto& kc : x.cal_order) { if (kc.second == 2) hp.stereoCalibRow(static_cast<const Cal3_S2Stereo*>(kc.first)); else hp.calibRow(kc.first, kc.second); }
     place[pi].o_sfm = o_sfm_next; place[pi].o_pj = (int64_t)hp.pj_pose.size(); place[pi].o_st = (int64_t)hp.st_pose.size(); place[pi].o_sam = (int64_t)hp.sam_pose.size(); place[pi].o_bt = (int64_t)hp.bt_1.size();
-    place[pi].o_pr = (int64_t)hp.pr_var.size(); place[pi].o_sm = (int64_t)hp.sm_nz.size(); place[pi].o_pp = (int64_t)hp.pp_var.size();
+    place[pi].o_pr = (int64_t)hp.pr_var.size(); place[pi].o_sm = (int64_t)hp.sm_nz.size(); place[pi].o_pp = (int64_t)hp.pp_var.size(); place[pi].o_s2 = (int64_t)hp.s2_pose.size();
     o_sfm_next += (int64_t)x.sfm_cam.size();
     for (const auto& r : x.sfm_nz) place[pi].sfm_rows.emplace_back(r.first, hp.nt.add(r.second, 2));
     cat(hp.pj_pose, x.pj_pose); cat(hp.pj_pt, x.pj_pt); cat(hp.pj_z, x.pj_z);
@@ -764,6 +795,8 @@ HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap
     for (const Cal3_S2Stereo* K : x.st_cal) hp.st_cal.push_back(hp.stereoCalibRow(K));
     cat(hp.sam_kind, x.sam_kind); cat(hp.sam_pose, x.sam_pose); cat(hp.sam_pt, x.sam_pt); cat(hp.sam_z, x.sam_z);
     rows(hp.sam_nz, x.sam_nz, &x.sam_dim);
+    cat(hp.s2_kind, x.s2_kind); cat(hp.s2_pose, x.s2_pose); cat(hp.s2_pt, x.s2_pt); cat(hp.s2_z, x.s2_z);
+    rows(hp.s2_nz, x.s2_nz, &x.s2_dim);
     cat(hp.bt_1, x.bt_1); cat(hp.bt_2, x.bt_2); cat(hp.bt_z, x.bt_z);
     rows(hp.bt_nz, x.bt_nz, &x.bt_dim);
     cat(hp.pr_var, x.pr_var); cat(hp.pr_data, x.pr_data);
@@ -803,7 +836,7 @@ HostProblem mergeTables(const std::vector<Extract>& part, size_t nfac, FactorMap
     auto* fm_out = fac_map->data() + cut(nfac, part.size(), pi);     // (the chunk's factors: the range extractFactors gave it)
     for (const auto& fm : x.fac_map)
       *fm_out++ = {fm.first, fm.second + (fm.first == GTG_FAC_GENERAL_SFM ? pl.o_sfm : fm.first == GTG_FAC_PROJECTION ? pl.o_pj : fm.first == GTG_FAC_STEREO ? pl.o_st : fm.first == GTG_FAC_SAM ? pl.o_sam :
-                                           fm.first == GTG_FAC_BETWEEN_POSE3 ? pl.o_bt : fm.first == GTG_FAC_PRIOR ? pl.o_pr : fm.first == GTG_FAC_POSE_PARTIAL ? pl.o_pp : fm.first == -2 ? pl.o_sm : 0)};
+                                           fm.first == GTG_FAC_BETWEEN_POSE3 ? pl.o_bt : fm.first == GTG_FAC_PRIOR ? pl.o_pr : fm.first == GTG_FAC_POSE_PARTIAL ? pl.o_pp : fm.first == GTG_FAC_SAM2 ? pl.o_s2 : fm.first == -2 ? pl.o_sm : 0)};
   });
   return hp;
 }
@@ -858,7 +891,7 @@ void GpuLevenbergMarquardtOptimizer::init(const NonlinearFactorGraph& graph, con
   const HostProblem hp = mergeTables(part, graph.size(), &m.fac_map);
   lap("factors: merge, noise / calibration tables");
   const gtg_problem pb = hp.view(m.var_type);
-  m.sam_kind = hp.sam_kind; m.pp_kind = hp.pp_kind;
+  m.sam_kind = hp.sam_kind; m.pp_kind = hp.pp_kind; m.sam2_kind = hp.s2_kind;
   if (shards.n_shards < 1 || shards.shard < 0 || shards.shard >= shards.n_shards) throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: bad ShardSpec");
   if (shards.n_shards > 1 && !shards.allreduce) throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: n_shards > 1 needs an all-reduce callback");
   for (auto& t : packers) t.join();
@@ -1087,7 +1120,7 @@ GaussianFactorGraph::shared_ptr GpuLevenbergMarquardtOptimizer::downloadLineariz
     const double* r = records.of(tf);
     const KeyVector& keys = graph_[i]->keys();
     const RecordLayout lay = m.layoutOf(tf, keys[0]);
-    auto block = [&](int k) { return Matrix(Eigen::Map<const RowMat>(r + lay.boff[k], lay.rows, lay.bcols[k])); };
+    auto block = [&](int k) { return Matrix(Eigen::Map<const RowMat, 0, Eigen::OuterStride<>>(r + lay.boff[k], lay.rows, lay.bcols[k], Eigen::OuterStride<>(lay.pitch(k)))); };
     const Vector b = Eigen::Map<const Vector>(r + lay.rhs, lay.rows);
     if (lay.nblk == 2) out->emplace_shared<JacobianFactor>(keys[0], block(0), keys[1], block(1), b);
     else out->emplace_shared<JacobianFactor>(keys[0], block(0), b);
@@ -1145,7 +1178,7 @@ VectorValues GpuLevenbergMarquardtOptimizer::solve(const GaussianFactorGraph& gf
           const auto A = theirs->getA(theirs->begin() + k);
           if ((int)A.cols() != lay.bcols[k]) { same = false; return; }
           for (int a = 0; a < lay.rows; a++)
-            for (int cc = 0; cc < lay.bcols[k]; cc++) { const double x = A(a, cc); scale = std::max(scale, std::abs(x)); worst = std::max(worst, std::abs(x - r[lay.boff[k] + a * lay.bcols[k] + cc])); }
+            for (int cc = 0; cc < lay.bcols[k]; cc++) { const double x = A(a, cc); scale = std::max(scale, std::abs(x)); worst = std::max(worst, std::abs(x - r[lay.boff[k] + a * lay.pitch(k) + cc])); }
         }
         const auto bb = theirs->getb();
         for (int a = 0; a < lay.rows; a++) { scale = std::max(scale, std::abs(bb(a))); worst = std::max(worst, std::abs(bb(a) - r[lay.rhs + a])); }
@@ -1169,7 +1202,7 @@ VectorValues GpuLevenbergMarquardtOptimizer::solve(const GaussianFactorGraph& gf
   check(gtg_get_delta(m.h, delta.data(), (int64_t)delta.size()), "gtg_get_delta");
   VectorValues x;
   for (size_t v = 0; v < nv; v++)
-    x.insert(m.keys[v], Vector(Eigen::Map<const Vector>(delta.data() + m.dim_off[v], m.dim_off[v + 1] - m.dim_off[v])));
+    x.insert(m.keys[v], Vector(Eigen::Map<const Vector>(delta.data() + m.dim_off[v], userDim(m.var_type[v]))));
   return x;
 }
 

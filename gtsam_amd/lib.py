@@ -127,7 +127,7 @@ def _check(rc, what):
 class DeviceGraph:
     """One factor graph resident on one MI355X (one handle of the C ABI)."""
 
-    JAC_ROW = {0: 26, 1: 20, 2: 78, 3: 90, 4: 30, 5: 30, 6: 90}
+    JAC_ROW = {0: 26, 1: 20, 2: 78, 3: 90, 4: 30, 5: 30, 6: 90, 7: 21}
 
     def __init__(self, problem: Problem, device: int = 0, shard: int = 0, n_shards: int = 1,
                  reduced_ordering=None, allreduce=None):
@@ -146,7 +146,7 @@ class DeviceGraph:
         self.val_size = self.lib.gtg_values_size(self.h)
         self.dim_size = self.lib.gtg_tangent_size(self.h)
         self.reduced_dim = self.lib.gtg_reduced_dim(self.h)
-        self.reduced_vars = int((np.asarray(problem.var_type) != 2).sum())        # everything but the POINT3 variables
+        self.reduced_vars = int((~np.isin(np.asarray(problem.var_type), (2, 4))).sum())        # everything but the POINT3 / POINT2 variables
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h.value:
@@ -196,7 +196,7 @@ class DeviceGraph:
 
     def jacobians(self, ftype):
         n = {0: self.problem.n_sfm, 1: self.problem.n_proj, 2: self.problem.n_between, 3: self.problem.n_prior, 4: self.problem.n_stereo, 5: self.problem.n_sam,
-             6: self.problem.n_pose_partial}[ftype]
+             6: self.problem.n_pose_partial, 7: self.problem.n_sam2}[ftype]
         out = np.empty((n, self.JAC_ROW[ftype]), np.float64)
         _check(self.lib.gtg_get_jacobians(self.h, ftype, out.ctypes.data, out.size), "gtg_get_jacobians")
         return out

@@ -13,16 +13,17 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-VAR_POSE3, VAR_SFM_CAMERA, VAR_POINT3, VAR_POSE2 = 0, 1, 2, 3
-FAC_GENERAL_SFM, FAC_PROJECTION, FAC_BETWEEN_POSE3, FAC_PRIOR, FAC_STEREO, FAC_SAM, FAC_POSE_PARTIAL = 0, 1, 2, 3, 4, 5, 6
+VAR_POSE3, VAR_SFM_CAMERA, VAR_POINT3, VAR_POSE2, VAR_POINT2 = 0, 1, 2, 3, 4
+FAC_GENERAL_SFM, FAC_PROJECTION, FAC_BETWEEN_POSE3, FAC_PRIOR, FAC_STEREO, FAC_SAM, FAC_POSE_PARTIAL, FAC_SAM2 = 0, 1, 2, 3, 4, 5, 6, 7
 SAM_BEARING_RANGE, SAM_RANGE, SAM_BEARING = 0, 1, 2
 POSE_PARTIAL_TRANSLATION, POSE_PARTIAL_ROTATION = 0, 1
 NOISE_UNIT, NOISE_ISOTROPIC, NOISE_DIAGONAL, NOISE_GAUSSIAN = 0, 1, 2, 3
 SMART_RIG = -2     # smart_calib of a SmartProjectionRigFactor (GTG_SMART_RIG): calib / sensor per measurement
 ROBUST_NONE, ROBUST_FAIR, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY, ROBUST_WELSCH, ROBUST_GEMANMCCLURE, ROBUST_DCS, ROBUST_L2WITHDEADZONE = range(9)
 
-STORAGE = {VAR_POSE3: 12, VAR_SFM_CAMERA: 17, VAR_POINT3: 3, VAR_POSE2: 3}    # Pose2 = (x, y, theta)
-TANGENT = {VAR_POSE3: 6, VAR_SFM_CAMERA: 9, VAR_POINT3: 3, VAR_POSE2: 3}
+# Pose2 = (x, y, theta); a Point2 is padded to the landmark slot at the C ABI: (x, y, 0) and (dx, dy, 0)
+STORAGE = {VAR_POSE3: 12, VAR_SFM_CAMERA: 17, VAR_POINT3: 3, VAR_POSE2: 3, VAR_POINT2: 3}
+TANGENT = {VAR_POSE3: 6, VAR_SFM_CAMERA: 9, VAR_POINT3: 3, VAR_POSE2: 3, VAR_POINT2: 3}
 
 
 class gtg_problem(C.Structure):
@@ -51,6 +52,18 @@ class gtg_problem(C.Structure):
         ("n_pose_partial", C.c_int64), ("pose_partial_kind", _i32p), ("pose_partial_var", _i32p), ("pose_partial_z", _f64p),
         ("pose_partial_noise", _i32p),
     ]
+
+
+class gtg_planar_table(C.Structure):
+    """The planar bearing / range factors (include/gtsam_amd.h: gtg_planar_table), the member `planar` of the C struct."""
+    _i32p, _f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    _fields_ = [("n_sam2", C.c_int64), ("sam2_kind", _i32p), ("sam2_pose", _i32p), ("sam2_point", _i32p), ("sam2_z", _f64p), ("sam2_noise", _i32p)]
+
+
+class gtg_problem_full(gtg_problem):
+    """The C struct gtg_problem as the library reads it: gtg_problem's own fields (above, field for field those of the header) and,
+    behind them, the tables it holds by value as member structs."""
+    _fields_ = [("planar", gtg_planar_table)]
 
 
 def _a(x, dt):
@@ -123,6 +136,13 @@ class Problem:
     pose_partial_var: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     pose_partial_z: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float64))
     pose_partial_noise: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    # BearingRangeFactor / RangeFactor / BearingFactor <Pose2, Point2> (gtsam/sam, planar): sam2_kind SAM_*, sam2_z 3 per factor = (c, s)
+    # of the measured Rot2 as the reference holds it, then the range (the entries a kind does not use are 0)
+    sam2_kind: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    sam2_pose: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    sam2_point: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    sam2_z: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float64))
+    sam2_noise: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
 
     def __post_init__(self):
         for name, dt in (("var_type", np.int32), ("noise_kind", np.int32), ("noise_dim", np.int32),
@@ -143,7 +163,9 @@ class Problem:
                          ("sam_kind", np.int32), ("sam_pose", np.int32), ("sam_point", np.int32), ("sam_z", np.float64),
                          ("sam_noise", np.int32),
                          ("pose_partial_kind", np.int32), ("pose_partial_var", np.int32), ("pose_partial_z", np.float64),
-                         ("pose_partial_noise", np.int32)):
+                         ("pose_partial_noise", np.int32),
+                         ("sam2_kind", np.int32), ("sam2_pose", np.int32), ("sam2_point", np.int32), ("sam2_z", np.float64),
+                         ("sam2_noise", np.int32)):
             setattr(self, name, _a(getattr(self, name), dt))
 
     # ---- sizes -------------------------------------------------------------------------------
@@ -157,6 +179,8 @@ class Problem:
     def n_stereo(self): return int(self.stereo_pose.size)
     @property
     def n_sam(self): return int(self.sam_pose.size)
+    @property
+    def n_sam2(self): return int(self.sam2_pose.size)
     @property
     def n_between(self): return int(self.between_v1.size)
     @property
@@ -195,8 +219,8 @@ class Problem:
         return idx
 
     # ---- ctypes view (keeps the arrays alive through the returned object) ---------------------
-    def to_ctypes(self) -> gtg_problem:
-        p = gtg_problem()
+    def to_ctypes(self) -> gtg_problem_full:
+        p = gtg_problem_full()
         keep = []
 
         def ptr(arr, ct):
@@ -296,6 +320,14 @@ class Problem:
         p.pose_partial_var = ptr(self.pose_partial_var, C.c_int32)
         p.pose_partial_z = ptr(self.pose_partial_z, C.c_double)
         p.pose_partial_noise = ptr(self.pose_partial_noise, C.c_int32)
+        p.planar.n_sam2 = self.n_sam2
+        if self.sam2_z.size != 3 * self.n_sam2 or any(a.size != self.n_sam2 for a in (self.sam2_kind, self.sam2_point, self.sam2_noise)):
+            raise ValueError("inconsistent planar bearing / range factor tables (sam2_z holds 3 doubles per factor)")
+        p.planar.sam2_kind = ptr(self.sam2_kind, C.c_int32)
+        p.planar.sam2_pose = ptr(self.sam2_pose, C.c_int32)
+        p.planar.sam2_point = ptr(self.sam2_point, C.c_int32)
+        p.planar.sam2_z = ptr(self.sam2_z, C.c_double)
+        p.planar.sam2_noise = ptr(self.sam2_noise, C.c_int32)
         p._keep = keep
         return p
 
@@ -365,6 +397,22 @@ class Problem:
         self.sam_kind = np.append(self.sam_kind, np.int32(kind)); self.sam_pose = np.append(self.sam_pose, np.int32(pose))
         self.sam_point = np.append(self.sam_point, np.int32(point)); self.sam_noise = np.append(self.sam_noise, np.int32(noise_idx))
         self.sam_z = np.concatenate([self.sam_z, z])
+
+    def add_sam2(self, kind: int, pose: int, point: int, noise_idx: int, bearing=None, range_=None):
+        """One BearingRangeFactor (SAM_BEARING_RANGE: bearing and range_), RangeFactor (SAM_RANGE: range_) or BearingFactor
+        (SAM_BEARING: bearing) <Pose2, Point2>.  bearing: (c, s) of the measured Rot2, stored as given."""
+        if kind not in (SAM_BEARING_RANGE, SAM_RANGE, SAM_BEARING):
+            raise ValueError("unknown sam kind")
+        if (bearing is None) != (kind == SAM_RANGE) or (range_ is None) != (kind == SAM_BEARING):
+            raise ValueError("a bearing-range factor takes a bearing and a range, a range factor a range, a bearing factor a bearing")
+        z = np.zeros(3)
+        if bearing is not None:
+            z[:2] = _a(bearing, np.float64)
+        if range_ is not None:
+            z[2] = float(range_)
+        self.sam2_kind = np.append(self.sam2_kind, np.int32(kind)); self.sam2_pose = np.append(self.sam2_pose, np.int32(pose))
+        self.sam2_point = np.append(self.sam2_point, np.int32(point)); self.sam2_noise = np.append(self.sam2_noise, np.int32(noise_idx))
+        self.sam2_z = np.concatenate([self.sam2_z, z])
 
     # ---- partial pose priors -------------------------------------------------------------------
     def add_pose_partial(self, kind: int, var: int, z, noise_idx: int):

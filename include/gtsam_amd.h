@@ -37,8 +37,11 @@ enum { GTG_OK = 0, GTG_INDETERMINATE = 1, GTG_ERR_USAGE = -1, GTG_ERR_HIP = -2,
  *              17 doubles = pose (12) then f,k1,k2,u0,v0; tangent 9 = [pose(6); f,k1,k2]
  *   POINT3     gtsam::Point3: 3 doubles; tangent 3
  *   POSE2      gtsam::Pose2 (geometry/Pose2.h): 3 doubles = x, y, theta (theta() = atan2(s, c), wrapped); tangent 3,
- *              retract = compose with Pose2(v0, v1, v2) (Pose2.cpp:99-109, GTSAM_SLOW_BUT_CORRECT_EXPMAP off)    */
-enum { GTG_VAR_POSE3 = 0, GTG_VAR_SFM_CAMERA = 1, GTG_VAR_POINT3 = 2, GTG_VAR_POSE2 = 3 };
+ *              retract = compose with Pose2(v0, v1, v2) (Pose2.cpp:99-109, GTSAM_SLOW_BUT_CORRECT_EXPMAP off)
+ *   POINT2     gtsam::Point2, the landmark of a planar graph, padded to the POINT3 slot: 3 doubles = x, y, 0; tangent 3 =
+ *              dx, dy, 0.  Given a third storage entry of 0, every third entry the library returns (delta, gradients, Hessian
+ *              diagonal, trial and accepted values) is exactly 0.0.  Only in a graph of POSE2 / POINT2 variables.             */
+enum { GTG_VAR_POSE3 = 0, GTG_VAR_SFM_CAMERA = 1, GTG_VAR_POINT3 = 2, GTG_VAR_POSE2 = 3, GTG_VAR_POINT2 = 4 };
 
 /* Factor types on the path. */
 enum { GTG_FAC_GENERAL_SFM = 0,   /* GeneralSFMFactor<PinholeCamera<Cal3Bundler>,Point3>  slam/GeneralSFMFactor.h:127-177 */
@@ -84,6 +87,29 @@ enum { GTG_ROBUST_NONE = 0, GTG_ROBUST_FAIR = 1, GTG_ROBUST_HUBER = 2, GTG_ROBUS
 /* The factor graph in structure-of-arrays form: what the extractor produces by walking a
  * gtsam::NonlinearFactorGraph once (FactorGraph.h:92 factors_, Factor.h keys_). Variable ids are
  * dense 0..n_vars-1 (the shim maps gtsam::Key -> id in Values order, Values.h:74-79). */
+/* GTG_FAC_SAM2: BearingRangeFactor<Pose2, Point2>, RangeFactor<Pose2, Point2> and BearingFactor<Pose2, Point2> (gtsam/sam), the
+ * landmark factors of planar SLAM.  The same ExpressionFactorN as GTG_FAC_SAM with h = Pose2::bearing (geometry/Pose2.cpp:245-256:
+ * Rot2::relativeBearing of transformTo, a ZERO Jacobian and the identity rotation at a distance <= 1e-5) and Pose2::range
+ * (Pose2.cpp:270-284: norm2, Jacobian (1, 1) at r <= 1e-10); b = [theta(h^-1 z) ; z_range - h_range].  Rows: bearing-range 2
+ * (bearing 0, range 1), range 1, bearing 1.  A POINT2 is a landmark and is eliminated like a POINT3; a graph with a POINT2 variable is
+ * a PLANAR graph: beside these factors it may hold BetweenFactor<Pose2>, PriorFactor<Pose2> and the 2-D partial pose priors.
+ * NULL / 0: no such factors.  Refused by gtg_upload_problem, each with its own message: keys that are not (POSE2, POINT2); an unknown
+ * kind; a noise dimension that does not match the kind (2, 1, 1); n_sam2 > 0 with a table missing; a POINT2 variable or a planar
+ * factor in a graph that also has POSE3, SFM_CAMERA or POINT3 variables or camera, stereo, 3-D bearing / range or smart factors; a
+ * PriorFactor on a POINT2; n_shards > 1.  gtg_try_lambda_pcg refuses a planar graph at the call.
+ * The table is a struct of its own, held by value as `planar`, the LAST member of gtg_problem: in memory its six fields stand where six
+ * more fields of gtg_problem would, behind the partial pose priors, and gtg_problem's own field list is what it was (a caller built
+ * against the older struct must be recompiled all the same). */
+typedef struct gtg_planar_table {
+  int64_t n_sam2;
+  const int32_t* sam2_kind;       /* [n_sam2] GTG_SAM_* */
+  const int32_t* sam2_pose;       /* [n_sam2] variable id of the POSE2 */
+  const int32_t* sam2_point;      /* [n_sam2] variable id of the POINT2 */
+  const double* sam2_z;           /* [n_sam2*3] c_z, s_z of the measured Rot2 as the reference holds it, then the measured range; the
+                                     entries a kind does not use are 0 */
+  const int32_t* sam2_noise;      /* [n_sam2] index into the noise table (dim 2, 1 or 1 by kind) */
+} gtg_planar_table;
+
 typedef struct gtg_problem {
   int32_t n_vars;
   const int32_t* var_type;       /* [n_vars] GTG_VAR_* */
@@ -235,11 +261,15 @@ typedef struct gtg_problem {
   const int32_t* pose_partial_var;    /* [n_pose_partial] variable id of the POSE3 or POSE2 */
   const double* pose_partial_z;       /* [n_pose_partial*9] the measurement, see above */
   const int32_t* pose_partial_noise;  /* [n_pose_partial] index into the noise table (dim 3, 3, 2 or 1 by kind and variable type) */
+
+  gtg_planar_table planar;        /* the planar bearing / range factors (GTG_FAC_SAM2): see gtg_planar_table above */
 } gtg_problem;
 /* pose_partial_kind */
 enum { GTG_POSE_PARTIAL_TRANSLATION = 0, GTG_POSE_PARTIAL_ROTATION = 1 };
 /* the factor type of the partial pose priors for gtg_get_jacobians (the enum of the factor types above, continued) */
 enum { GTG_FAC_POSE_PARTIAL = 6 };
+/* ... and of the planar bearing / range factors */
+enum { GTG_FAC_SAM2 = 7 };
 /* smart_calib[i] of a rig-type smart factor */
 enum { GTG_SMART_RIG = -2 };
 
@@ -307,7 +337,7 @@ int gtg_try_lambda(gtg_handle h, double lambda, int diagonal_damping, double min
  * PCGSolverParameters, NonlinearOptimizer.cpp:154-172) with a block-Jacobi preconditioner, applied to the IMPLICIT Schur
  * complement of the landmarks (never formed).  cg = {maxIterations, minIterations, epsilon_rel, epsilon_abs}
  * (ConjugateGradientParameters defaults: 500, 1, 1e-3, 1e-3); *iterations receives the CG iteration count.
- * Single-shard graphs only. */
+ * Single-shard graphs only; not for a planar graph (GTG_VAR_POINT2). */
 int gtg_try_lambda_pcg(gtg_handle h, double lambda, int diagonal_damping, double min_diagonal, double max_diagonal,
                        const double cg[4], double out[4], int32_t* iterations);
 
@@ -342,7 +372,9 @@ int gtg_get_graph_gradient(gtg_handle h, double* g, int64_t n);
  * 30-double record (the caller's bearing / range factors in the caller's order: bearing rows 0-1 and range row 2 of a bearing-range
  * factor, a range-only factor in row 0, a bearing-only factor in rows 0-1; the rows a kind does not use are exactly 0), POSE_PARTIAL the 90-double PRIOR
  * record of the pose's tangent dimension d (the caller's partial pose priors in the caller's order: the factor's 3, 2 or 1 rows first,
- * the rows it does not have exactly 0; PRIOR keeps returning the caller's PriorFactor records alone).
+ * the rows it does not have exactly 0; PRIOR keeps returning the caller's PriorFactor records alone), SAM2 [A1 3x3 | A2 3x3 | b 3]
+ * (21 doubles, the caller's planar bearing / range factors in the caller's order: bearing row 0 and range row 1 of a bearing-range
+ * factor, a bearing-only or range-only factor in row 0; A2's third column and the rows a kind does not use are exactly 0).
  * n = doubles available in out. */
 int gtg_get_jacobians(gtg_handle h, int factor_type, double* out, int64_t n);
 int64_t gtg_reduced_dim(gtg_handle h);
