@@ -18,7 +18,7 @@ import numpy as np
 
 from .optimizer import DeviceLevenbergMarquardt
 from .params import LevenbergMarquardtParams
-from .problem import (NOISE_DIAGONAL, NOISE_GAUSSIAN, NOISE_ISOTROPIC, NOISE_UNIT, POSE_PARTIAL_ROTATION, POSE_PARTIAL_TRANSLATION, SAM_BEARING,
+from .problem import (CALIB_FISHEYE, CALIB_PINHOLE, NOISE_DIAGONAL, NOISE_GAUSSIAN, NOISE_ISOTROPIC, NOISE_UNIT, POSE_PARTIAL_ROTATION, POSE_PARTIAL_TRANSLATION, SAM_BEARING,
                       SAM_BEARING_RANGE, SAM_RANGE, STORAGE, TANGENT, VAR_POINT2, VAR_POINT3, VAR_POSE2, VAR_POSE3, VAR_SFM_CAMERA, Problem)
 
 
@@ -158,6 +158,29 @@ class Cal3DS2:
 
     def __init__(self, fx=1.0, fy=1.0, s=0.0, u0=0.0, v0=0.0, k1=0.0, k2=0.0, p1=0.0, p2=0.0):
         self.v = np.array([fx, fy, s, u0, v0, k1, k2, p1, p2], np.float64)
+
+
+class Cal3Fisheye:
+    """fx, fy, s, u0, v0 + the coefficients k1..k4 of the equidistant fisheye model (OpenCV fisheye / Kannala-Brandt,
+    geometry/Cal3Fisheye.h:52-77)."""
+
+    def __init__(self, fx=1.0, fy=1.0, s=0.0, u0=0.0, v0=0.0, k1=0.0, k2=0.0, k3=0.0, k4=0.0):
+        self.v = np.array([fx, fy, s, u0, v0, k1, k2, k3, k4], np.float64)
+
+    def uncalibrate(self, p):
+        """Intrinsic point -> pixel (geometry/Cal3Fisheye.cpp:35-59); for building scenes."""
+        fx, fy, sk, u0, v0, k1, k2, k3, k4 = self.v
+        xi, yi = float(p[0]), float(p[1])
+        r = np.sqrt(xi * xi + yi * yi)
+        t = np.arctan2(r, 1.0)
+        t2 = t * t; t4 = t2 * t2; t6 = t2 * t4; t8 = t4 * t4
+        if r > 1e-8 or r < -1e-8:
+            scaling = np.arctan(r) / r
+        else:
+            r2 = r * r; scaling = 1.0 - r2 / 3 + r2 * r2 / 5
+        s = scaling * (1 + k1 * t2 + k2 * t4 + k3 * t6 + k4 * t8)
+        xd, yd = s * xi, s * yi
+        return np.array([fx * xd + sk * yd + u0, fy * yd + v0])
 
 
 class Cal3_S2Stereo:
@@ -326,6 +349,10 @@ class GenericProjectionFactorCal3_S2:
 
 class GenericProjectionFactorCal3DS2(GenericProjectionFactorCal3_S2):
     """GenericProjectionFactor<Pose3, Point3, Cal3DS2> (wrapped name of slam/slam.i's instantiation): same factor, K a Cal3DS2."""
+
+
+class GenericProjectionFactorCal3Fisheye(GenericProjectionFactorCal3_S2):
+    """GenericProjectionFactor<Pose3, Point3, Cal3Fisheye> (wrapped name of slam/slam.i's instantiation): same factor, K a Cal3Fisheye."""
 
 
 class GenericStereoFactor3D:
@@ -644,6 +671,7 @@ def extract(graph: NonlinearFactorGraph, values: Values):
 
     sfm, proj, btw, stereo = [], [], [], []
     calibs, sensors = {}, []
+    ckey = lambda K: (type(K).__name__, K.v.tobytes())     # by class: a Cal3DS2 and a Cal3Fisheye hold nine numbers each
     smart_sensors = {}      # pose-type smart factors share their sensor rows (one body_P_sensor for a whole front end)
     # rig-type smart factors: (rig object, camera id) -> (calib row, row of rig_sensors or -1), shared by every factor of the rig; the
     # extrinsics stand BEHIND the sensor rows of the other factors (as the C++ shim, which merges its extraction chunks, places them)
@@ -652,17 +680,17 @@ def extract(graph: NonlinearFactorGraph, values: Values):
         if isinstance(f, GeneralSFMFactorCal3Bundler):
             sfm.append((vid(f.keys_[0]), vid(f.keys_[1]), f.z, nid(f.model, 2)))
         elif isinstance(f, GenericProjectionFactorCal3_S2):
-            ck = f.K.v.tobytes()
+            ck = ckey(f.K)
             if ck not in calibs:
-                calibs[ck] = (len(calibs), f.K.v)
+                calibs[ck] = (len(calibs), f.K.v, f.K)
             si = -1
             if f.sensor is not None:
                 si = len(sensors); sensors.append(f.sensor.packed())
             proj.append((vid(f.keys_[0]), vid(f.keys_[1]), f.z, nid(f.model, 2), calibs[ck][0], si))
         elif isinstance(f, GenericStereoFactor3D):   # same calib / sensor tables; the baseline goes to calib_baseline
-            ck = f.K.v.tobytes()
+            ck = ckey(f.K)
             if ck not in calibs:
-                calibs[ck] = (len(calibs), f.K.v)
+                calibs[ck] = (len(calibs), f.K.v, f.K)
             si = -1
             if f.sensor is not None:
                 si = len(sensors); sensors.append(f.sensor.packed())
@@ -679,9 +707,9 @@ def extract(graph: NonlinearFactorGraph, values: Values):
                         sp.dynamicOutlierRejectionThreshold, sp.retriangulationThreshold, sp.degeneracyMode, sp.linearizationMode, sp.enableEPI,
                         use_lost=sp.useLOST, lost_sigma=sp.lostSigma() if sp.useLOST else 1e-4)
         elif isinstance(f, SmartProjectionPose3Factor):
-            ck = f.K.v.tobytes()
+            ck = ckey(f.K)
             if ck not in calibs:
-                calibs[ck] = (len(calibs), f.K.v)
+                calibs[ck] = (len(calibs), f.K.v, f.K)
             si = -1
             if f.sensor is not None:
                 sk = f.sensor.packed().tobytes()
@@ -699,9 +727,9 @@ def extract(graph: NonlinearFactorGraph, values: Values):
                     raise IndexError(f"SmartProjectionRigFactor: camera id {cid} outside the rig")
                 if (id(f.rig), cid) not in rig_rows:
                     cam = f.rig[cid]
-                    ck = cam.calibration().v.tobytes()
+                    ck = ckey(cam.calibration())
                     if ck not in calibs:
-                        calibs[ck] = (len(calibs), cam.calibration().v)
+                        calibs[ck] = (len(calibs), cam.calibration().v, cam.calibration())
                     si = -1                       # an identity extrinsic is no extrinsic (the composition returns the body pose's own numbers)
                     if not np.array_equal(cam.pose().packed(), Pose3().packed()):
                         si = len(rig_sensors); rig_sensors.append(cam.pose().packed())
@@ -750,8 +778,12 @@ def extract(graph: NonlinearFactorGraph, values: Values):
     if proj or stereo or calibs:
         rows = [c[1] for c in sorted(calibs.values(), key=lambda c: c[0])]
         p.calib = np.concatenate([r[:5] for r in rows])
-        if any(r.size == 9 for r in rows):      # Cal3DS2 entries: k1, k2, p1, p2 per calibration (zero rows for a Cal3_S2)
-            p.calib_distortion = np.concatenate([r[5:] if r.size == 9 else np.zeros(4) for r in rows])
+        kinds = [c[2] for c in sorted(calibs.values(), key=lambda c: c[0])]
+        nine = [isinstance(K, (Cal3DS2, Cal3Fisheye)) for K in kinds]
+        if any(nine):      # Cal3DS2 entries: k1, k2, p1, p2 per calibration, Cal3Fisheye entries: k1, k2, k3, k4 (zero rows for a Cal3_S2)
+            p.calib_distortion = np.concatenate([r[5:] if n else np.zeros(4) for r, n in zip(rows, nine)])
+        if any(isinstance(K, Cal3Fisheye) for K in kinds):      # the model of every row (empty: every row a pinhole)
+            p.calib_model = np.array([CALIB_FISHEYE if isinstance(K, Cal3Fisheye) else CALIB_PINHOLE for K in kinds], np.int32)
         if stereo:                              # Cal3_S2Stereo entries: their baseline (zero for the monocular calibrations)
             p.calib_baseline = np.array([r[5] if r.size == 6 else 0.0 for r in rows], np.float64)
         p.sensor = np.concatenate(sensors) if sensors else np.zeros(0)

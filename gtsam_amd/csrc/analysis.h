@@ -17,6 +17,7 @@ static inline int tangent_dim(int t) { return t == GTG_VAR_POSE3 ? 6 : t == GTG_
 struct HostIndex {
   std::vector<int32_t> sfm_cam, sfm_point, proj_pose, proj_point, between_v1, between_v2, prior_var;
   std::vector<int32_t> user_order;  // optional reduced ordering (variable ids)
+  std::vector<int32_t> calib_model; // gtg_set_calibration_models: GTG_CALIB_* per calib row of the NEXT upload, which clears it (empty: every row a pinhole)
   // n_shards > 1: the keys of EVERY observation and between factor of the whole graph (all shards).  The structure of
   // the reduced system -- ordering, offsets, tile schedule, exchange list -- must be identical on every shard, so it is
   // derived from the whole graph; only the numeric lists (terms, incidence) are the shard's own.

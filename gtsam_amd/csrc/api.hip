@@ -222,6 +222,19 @@ int gtg_set_reduced_ordering(gtg_handle c, const int32_t* order, int32_t n) {
   GTG_CATCH
 }
 
+// The camera model of every calib row of the NEXT upload (upload.hip::take_calibration_models checks it against that problem, uses it
+// and clears it): kept in the host index like the reduced ordering, because gtg_problem has no field for it.
+int gtg_set_calibration_models(gtg_handle c, const int32_t* model, int32_t n_calib) {
+  GTG_TRY
+  if (!c) throw std::invalid_argument("null handle");
+  if (n_calib < 0) throw std::invalid_argument("gtg_set_calibration_models: n_calib is negative");
+  HostIndex& hi = host_index(c);
+  if (!model || n_calib == 0) hi.calib_model.clear();
+  else hi.calib_model.assign(model, model + n_calib);
+  return GTG_OK;
+  GTG_CATCH
+}
+
 int64_t gtg_values_size(gtg_handle c) { return c ? c->user_val_size : -1; }
 int64_t gtg_tangent_size(gtg_handle c) { return c ? c->user_dim_size : -1; }
 int64_t gtg_reduced_dim(gtg_handle c) { return c ? c->n_red : -1; }

@@ -107,8 +107,9 @@ struct DfPlan : DfLists {                       // + the device copies (tile_pla
 
 // The form of the projection range: what its records look like and which kernels linearise and evaluate it.  Decided once per
 // upload (upload.hip::upload_projection) from facts of the WHOLE graph -- a shard may own none of the factors that define the form.
-// These five are the only states: pose-type smart factors beside stereo or bearing / range factors are refused by SmartView
-// (upload.hip), bearing / range factors alone already make a three-row graph, and a planar graph has no other observation.
+// These six are the only states: pose-type smart factors beside stereo or bearing / range factors are refused by SmartView
+// (upload.hip), bearing / range factors alone already make a three-row graph, a planar graph has no other observation, and a fisheye
+// calibration is refused wherever the form would not be Rows2 without it.
 enum class ProjForm {
   Rows2,        // GenericProjectionFactors only: records [A1 2x6 | A2 2x3 | b 2], two measurement entries
   Rows2Smart,   // ... and the measurements of pose-type smart factors behind them (gtg_context::smart_pose, which this state is derived from)
@@ -116,8 +117,10 @@ enum class ProjForm {
   Rows3Sam,     // the graph has bearing / range factors (with or without stereo factors): the same records, the sam factors in [n_cam, n_proj)
   Planar,       // a POSE2 / POINT2 graph: the range is its bearing / range factors alone, the POSE2 as the "camera" (reduced dimension 3):
                 // records [A1 3x3 | A2 3x3 | b 3] with a zero third landmark column (the POINT2 padded to the landmark slot)
+  Rows2Fisheye, // GenericProjectionFactors only, some calib row a Cal3Fisheye (FactorTables::calib_model): the records and measurement
+                // entries of Rows2, so every reader of the records runs what it runs for Rows2; kernels of its own linearise and evaluate the range
 };
-constexpr int proj_rows(ProjForm f) { return f == ProjForm::Rows2 || f == ProjForm::Rows2Smart ? 2 : 3; }
+constexpr int proj_rows(ProjForm f) { return f == ProjForm::Rows2 || f == ProjForm::Rows2Smart || f == ProjForm::Rows2Fisheye ? 2 : 3; }
 constexpr int proj_dc(ProjForm f) { return f == ProjForm::Planar ? 3 : 6; }   // tangent dimension of the range's "camera"
 constexpr int proj_rec(ProjForm f) { return proj_rows(f) * (proj_dc(f) + 4); }   // doubles per record [A1 R x DC | A2 R x 3 | b R]: kProjRec / kStereoRec / kPlanarRec (factors.h)
 constexpr bool has_sam(ProjForm f) { return f == ProjForm::Rows3Sam; }
@@ -133,6 +136,9 @@ struct FactorTables {
   DevBuf<int32_t> proj_pose, proj_point, proj_noise, proj_calib, proj_sensor;
   DevBuf<double> proj_z, proj_J, calib, sensor;
   ProjForm form = ProjForm::Rows2;
+  // ProjForm::Rows2Fisheye: the camera model of every calib row (GTG_CALIB_*), a buffer of its own beside the calib table, whose
+  // fisheye rows hold fx fy s u0 v0 k1 k2 k3 k4.  Empty in every other form.
+  DevBuf<int32_t> calib_model;
   // GenericStereoFactor<Pose3, Point3>: the stereo factors are the observations [n_mono, n_cam) of the projection range.  A three-row
   // graph keeps three-row records (kStereoRec) and three measurement entries for every observation of the range, the monocular ones
   // with a zero third row.

@@ -183,6 +183,60 @@ GT_HD double proj_error(const double* pose, const double* K, const double* senso
   return factor_loss(n, r[0] * r[0] + r[1] * r[1]);
 }
 
+// ---- GenericProjectionFactor<Pose3,Point3,Cal3Fisheye> -----------------------------------------
+// The same factor (slam/ProjectionFactor.h:138-166) through PinholeCamera<Cal3Fisheye>: K = fx, fy, s, u0, v0, k1, k2, k3, k4.  The contract
+// of proj_linearize / proj_error, written out beside them so that the two-row kernels of the pinhole models keep their instruction
+// streams (factors.hip, above k_lin_proj): the record [A1 2x6 | A2 2x3 | b 2] of kProjRec doubles.
+GT_HD void proj_linearize_fisheye(const double* pose, const double* K, const double* sensor, const double* pt,
+                                  const double* z, const NoiseRef& n, double* J) {
+  const int nkind = n.kind; const double* nd = n.data;
+  double pi[2];
+  bool ok;
+  if (sensor) {  // pose.compose(body_P_sensor, H0); H1 = H1 * H0, H0 = sensor^-1 AdjointMap (Lie.h:56-61)
+    double T[12], Dp[12], Si[12], H0[36];
+    pose_compose(pose, sensor, T);
+    ok = fisheye_project(T, K, pt, pi, Dp, J + 12);
+    if (ok) {
+      pose_inverse(sensor, Si);
+      pose_adjoint(Si, H0);
+      for (int r = 0; r < 2; r++)
+        for (int c = 0; c < 6; c++) {
+          double acc = 0.0;
+          for (int k = 0; k < 6; k++) acc += Dp[6 * r + k] * H0[6 * k + c];
+          J[6 * r + c] = acc;
+        }
+    }
+  } else {
+    ok = fisheye_project(pose, K, pt, pi, J, J + 12);
+  }
+  if (!ok) {  // H = 0 and residual 2*fx (ProjectionFactor.h:157-165, throwCheirality_ = false)
+    for (int i = 0; i < 18; i++) J[i] = 0.0;
+    J[18] = -2.0 * K[0]; J[19] = -2.0 * K[0];
+  } else {
+    J[18] = -(pi[0] - z[0]); J[19] = -(pi[1] - z[1]);
+  }
+  whiten_cols<2>(nkind, nd, J, 6);
+  whiten_cols<2>(nkind, nd, J + 12, 3);
+  whiten_cols<2>(nkind, nd, J + 18, 1);
+  if (n.rkind) { const double w = reweight_factor(n, J + 18, 2); for (int i = 0; i < kProjRec; i++) J[i] *= w; }
+}
+GT_HD double proj_error_fisheye(const double* pose, const double* K, const double* sensor, const double* pt,
+                                const double* z, const NoiseRef& n) {
+  double pi[2], r[2];
+  bool ok;
+  if (sensor) {
+    double T[12];
+    pose_compose(pose, sensor, T);
+    ok = fisheye_project(T, K, pt, pi, nullptr, nullptr);
+  } else {
+    ok = fisheye_project(pose, K, pt, pi, nullptr, nullptr);
+  }
+  if (ok) { r[0] = pi[0] - z[0]; r[1] = pi[1] - z[1]; }
+  else { r[0] = 2.0 * K[0]; r[1] = 2.0 * K[0]; }
+  whiten_cols<2>(n.kind, n.data, r, 1);
+  return factor_loss(n, r[0] * r[0] + r[1] * r[1]);
+}
+
 // One measurement of a SmartProjectionPoseFactor<Cal3_S2> whose landmark is a point at infinity (SmartFactorBase::computeJacobians<Unit3>,
 // slam/SmartFactorBase.h:203-239, whitened by the isotropic model): the projection record with F = Dpose (rotation part only) times
 // the H of world_P_body.compose(body_P_sensor) when there is a sensor (:216-233), the landmark block 2 x 2 padded with a zero column.

@@ -194,6 +194,42 @@ __global__ __launch_bounds__(kBlock) void k_lin_planar(int64_t n, const int32_t*
   }
 }
 
+// The projection range of a two-row graph with a Cal3Fisheye calibration (ProjForm::Rows2Fisheye): the shape of k_lin_proj, a kernel of
+// its own so that k_lin_proj keeps its instruction stream (above).  Every observation dispatches on the model of its calib row
+// (model[calib_idx[i]], GTG_CALIB_*): a pinhole row goes through proj_linearize as in k_lin_proj, a fisheye row through
+// proj_linearize_fisheye -- a rig with a pinhole and a fisheye camera is one graph.  The record (kProjRec, the layout of Rows2) in place in
+// the LDS image and stored as above.
+__global__ __launch_bounds__(kBlock) void k_lin_proj_fisheye(int64_t n, const int32_t* __restrict__ pose,
+    const int32_t* __restrict__ pt, const double* __restrict__ z, const int32_t* __restrict__ nz,
+    const int32_t* __restrict__ calib_idx, const int32_t* __restrict__ sensor_idx,
+    const double* __restrict__ calib, const int32_t* __restrict__ model, const double* __restrict__ sensor,
+    const double* __restrict__ values, const int64_t* __restrict__ val_off, NoiseTab nt, double* __restrict__ J) {
+  typedef RecIO<kProjRec> IO;
+  __shared__ double img[kBlock / 64][IO::LDS_DOUBLES];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double* my = img[wave];
+  const int64_t nchunks = (n + 63) / 64, stride = (int64_t)gridDim.x * (kBlock / 64);
+  for (int64_t ch = blockIdx.x * (int64_t)(kBlock / 64) + wave; ch < nchunks; ch += stride) {
+    const int64_t i = ch * 64 + lane;
+    if (i < n) {
+      double T[12], p[3], zz[2], K[kCalibStride], S[12];
+      const double* tp = values + val_off[pose[i]];
+      const double* pp = values + val_off[pt[i]];
+      for (int k = 0; k < 12; k++) T[k] = tp[k];
+      for (int k = 0; k < 3; k++) p[k] = pp[k];
+      const int ci = calib_idx[i];
+      for (int k = 0; k < kCalibStride; k++) K[k] = calib[kCalibStride * ci + k];
+      const int si = sensor_idx[i];
+      if (si >= 0) for (int k = 0; k < 12; k++) S[k] = sensor[12 * si + k];
+      zz[0] = z[2 * i]; zz[1] = z[2 * i + 1];
+      if (model[ci] == GTG_CALIB_FISHEYE) proj_linearize_fisheye(T, K, si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]), my + lane * IO::PITCH);
+      else proj_linearize(T, K, si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]), my + lane * IO::PITCH);
+    }
+    const int64_t left = n - ch * 64;
+    IO::store(my, J + (int64_t)kProjRec * ch * 64, left < 64 ? (int)left : 64, lane);
+  }
+}
+
 // BetweenFactor<Pose3> or BetweenFactor<Pose2>: decided by the type of the factor's variables (both of one type)
 __global__ __launch_bounds__(kBlock) void k_lin_between(int64_t n, const int32_t* __restrict__ v1,
     const int32_t* __restrict__ v2, const double* __restrict__ z, const int32_t* __restrict__ nz,
@@ -369,6 +405,32 @@ __global__ __launch_bounds__(kBlock) void k_error_planar(int64_t n, const int32_
     const double* pp = values + val_off[pt[i]];
     for (int k = 0; k < 3; k++) { x[k] = xp[k]; p[k] = pp[k]; zz[k] = z[3 * i + k]; }
     acc += sam2_error(kind[i], x, p, zz, nt.ref(nz[i]));
+  }
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// The projection range of a two-row graph with a Cal3Fisheye calibration (the range of k_lin_proj_fisheye), in the place of
+// k_error_rows3: k_error<kErrRest> is then launched without that range.  Fixed slices per block as above.
+__global__ __launch_bounds__(kBlock) void k_error_proj_fisheye(int64_t n, const int32_t* __restrict__ pose, const int32_t* __restrict__ pt,
+    const double* __restrict__ z, const int32_t* __restrict__ nz, const int32_t* __restrict__ calib_idx, const int32_t* __restrict__ sensor_idx,
+    const double* __restrict__ calib, const int32_t* __restrict__ model, const double* __restrict__ sensor,
+    const double* __restrict__ values, const int64_t* __restrict__ val_off, NoiseTab nt, double* __restrict__ partials) {
+  double acc = 0.0;
+  const int64_t tid = blockIdx.x * (int64_t)kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = tid; i < n; i += stride) {
+    double T[12], p[3], zz[2], K[kCalibStride], S[12];
+    const double* tp = values + val_off[pose[i]];
+    const double* pp = values + val_off[pt[i]];
+    for (int k = 0; k < 12; k++) T[k] = tp[k];
+    for (int k = 0; k < 3; k++) p[k] = pp[k];
+    const int ci = calib_idx[i];
+    for (int k = 0; k < kCalibStride; k++) K[k] = calib[kCalibStride * ci + k];
+    const int si = sensor_idx[i];
+    if (si >= 0) for (int k = 0; k < 12; k++) S[k] = sensor[12 * si + k];
+    zz[0] = z[2 * i]; zz[1] = z[2 * i + 1];
+    if (model[ci] == GTG_CALIB_FISHEYE) acc += proj_error_fisheye(T, K, si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]));
+    else acc += proj_error(T, K, si >= 0 ? S : nullptr, p, zz, nt.ref(nz[i]));
   }
   const double s = block_sum(acc);
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
@@ -766,6 +828,11 @@ void launch_linearize(gtg_context& c) {
       hipLaunchKernelGGL(k_lin_planar, dim3(grid_for(f.n_proj)), dim3(kBlock), 0, c.stream, f.n_proj, f.proj_pose.p, f.proj_point.p,
                          f.proj_noise.p, f.sam_kind.p, f.sam_z.p, c.values.p, c.val_off.p, nt, f.proj_J.p);
       break;
+    case ProjForm::Rows2Fisheye:
+      hipLaunchKernelGGL(k_lin_proj_fisheye, dim3(grid_for(f.n_proj)), dim3(kBlock), 0, c.stream, f.n_proj, f.proj_pose.p, f.proj_point.p,
+                         f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_model.p, f.sensor.p, c.values.p,
+                         c.val_off.p, nt, f.proj_J.p);
+      break;
   }
   if (f.n_between)
     hipLaunchKernelGGL(k_lin_between, dim3(grid_for(f.n_between)), dim3(kBlock), 0, c.stream, f.n_between,
@@ -810,7 +877,8 @@ void launch_sfm_records(gtg_context& c, double* dst) {
 
 void launch_error(gtg_context& c, const double* values, int slot, const double* gate) {
   auto& f = c.f;
-  const bool three = proj_rows(f.form) == 3;   // (its projection range goes to k_error_rows3 -- k_error_planar --, the third group of block partials)
+  // (its projection range goes to k_error_rows3 -- k_error_planar, k_error_proj_fisheye --, the third group of block partials)
+  const bool three = proj_rows(f.form) == 3 || f.form == ProjForm::Rows2Fisheye;
   const int64_t n_partial = f.n_prior - f.n_user_prior;   // (the partial pose priors go to k_error_pose_partial, the last group of block partials)
   ErrArgs a{f.n_sfm, three ? 0 : f.n_proj, f.n_between, f.n_user_prior,
             f.sfm_cam.p, f.sfm_point.p, f.sfm_noise.p, f.sfm_z.p,
@@ -832,6 +900,10 @@ void launch_error(gtg_context& c, const double* values, int slot, const double* 
   if (g3 && f.form == ProjForm::Planar)
     hipLaunchKernelGGL(k_error_planar, dim3(g3), dim3(kBlock), 0, c.stream, f.n_proj, f.proj_pose.p, f.proj_point.p, f.proj_noise.p,
                        f.sam_kind.p, f.sam_z.p, values, c.val_off.p, noise_tab(c), c.partials.p + g1 + g2);
+  else if (g3 && f.form == ProjForm::Rows2Fisheye)
+    hipLaunchKernelGGL(k_error_proj_fisheye, dim3(g3), dim3(kBlock), 0, c.stream, f.n_proj, f.proj_pose.p, f.proj_point.p, f.proj_z.p,
+                       f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_model.p, f.sensor.p, values, c.val_off.p,
+                       noise_tab(c), c.partials.p + g1 + g2);
   else if (g3) hipLaunchKernelGGL(k_three, dim3(g3), dim3(kBlock), 0, c.stream, f.n_proj, f.n_mono, f.n_cam, f.proj_pose.p, f.proj_point.p,
                              f.proj_z.p, f.proj_noise.p, f.proj_calib.p, f.proj_sensor.p, f.calib.p, f.calib_baseline.p, f.sensor.p,
                              f.sam_kind.p, f.sam_z.p, values, c.val_off.p, noise_tab(c), c.partials.p + g1 + g2);
@@ -883,7 +955,8 @@ void prewarm_factors(int) {
                    (const void*)k_lin_between, (const void*)k_lin_prior, (const void*)k_lin_pose_partial, (const void*)k_error_pose_partial, (const void*)k_error<kErrSfm>, (const void*)k_error<kErrRest>,
                    (const void*)k_error<kErrRest | kErrSmartProj>, (const void*)k_error_rows3<false>, (const void*)k_error_rows3<true>, (const void*)k_final_sum,
                    (const void*)k_linear_error<true, 2>, (const void*)k_linear_error<false, 2>, (const void*)k_linear_error<false, 3>, (const void*)k_linear_error<false, 3, 3>,
-                   (const void*)k_lin_planar, (const void*)k_error_planar, (const void*)k_retract,
+                   (const void*)k_lin_planar, (const void*)k_error_planar, (const void*)k_lin_proj_fisheye, (const void*)k_error_proj_fisheye,
+                   (const void*)k_retract,
                    (const void*)k_sumsq, (const void*)k_smart_triangulate<false, false>, (const void*)k_smart_triangulate<true, false>,
                    (const void*)k_smart_triangulate<false, true>, (const void*)k_smart_triangulate<true, true>, (const void*)k_lin_smart_at_infinity,
                    (const void*)k_error_smart_at_infinity, (const void*)k_sfm_value_offsets, (const void*)k_lin_smart_pose_at_infinity,

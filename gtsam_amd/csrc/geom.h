@@ -786,6 +786,67 @@ GT_HD bool s2_project(const double* T, const double* K, const double* pw, double
   return true;
 }
 
+// ---- Cal3Fisheye: the equidistant (OpenCV fisheye / Kannala-Brandt) model ---------------------------------------------------------
+// Cal3Fisheye::Scaling (geometry/Cal3Fisheye.cpp:35-44): atan(r) / r, by its Taylor series 1 - r^2/3 + r^4/5 for |r| <= 1e-8.
+GT_HD double fisheye_scaling(double r) {
+  if (r > 1e-8 || r < -1e-8) return atan(r) / r;
+  const double r2 = r * r, r4 = r2 * r2;
+  return 1.0 - r2 / 3 + r4 / 5;
+}
+// Cal3Fisheye::uncalibrate (geometry/Cal3Fisheye.cpp:47-108).  K = fx, fy, s, u0, v0, k1, k2, k3, k4 (kCalibStride); pn the intrinsic
+// point.  D (or nullptr): d(pixel)/d(intrinsic point) 2x2 row-major -- DK alone when r^2 == 0 exactly (:79-80), else DK * DR (:82-103).
+GT_HD void fisheye_uncalibrate(const double* K, const double* pn, double* pi, double* D) {
+  const double fx = K[0], fy = K[1], sk = K[2], u0 = K[3], v0 = K[4];
+  const double k1 = K[5], k2 = K[6], k3 = K[7], k4 = K[8];
+  const double xi = pn[0], yi = pn[1], zi = 1;
+  const double r2 = xi * xi + yi * yi, r = sqrt(r2);
+  const double t = atan2(r, zi);
+  const double t2 = t * t, t4 = t2 * t2, t6 = t2 * t4, t8 = t4 * t4;
+  const double scaling = fisheye_scaling(r);
+  const double s = scaling * (1 + k1 * t2 + k2 * t4 + k3 * t6 + k4 * t8);   // K.dot(T) (:53-57), summed left to right as Eigen's 5-vector dot does
+  const double xd = s * xi, yd = s * yi;
+  pi[0] = fx * xd + sk * yd + u0;
+  pi[1] = fy * yd + v0;
+  if (!D) return;
+  if (r2 == 0) {
+    D[0] = fx; D[1] = sk; D[2] = 0.0; D[3] = fy;
+    return;
+  }
+  const double dtd_dt = 1 + 3 * k1 * t2 + 5 * k2 * t4 + 7 * k3 * t6 + 9 * k4 * t8;
+  const double R2 = r2 + zi * zi;
+  const double dt_dr = zi / R2;
+  const double rinv = 1 / r;
+  const double dr_dxi = xi * rinv, dr_dyi = yi * rinv;
+  const double dtd_dr = dtd_dt * dt_dr;
+  const double c2 = dr_dxi * dr_dxi, s2 = dr_dyi * dr_dyi, cs = dr_dxi * dr_dyi;
+  const double dxd_dxi = dtd_dr * c2 + s * (1 - c2);
+  const double dxd_dyi = (dtd_dr - s) * cs;
+  const double dyd_dxi = dxd_dyi;
+  const double dyd_dyi = dtd_dr * s2 + s * (1 - s2);
+  D[0] = fx * dxd_dxi + sk * dyd_dxi; D[1] = fx * dxd_dyi + sk * dyd_dyi;   // DK * DR, DK = [fx s; 0 fy] (the zero entry's products included, as Eigen forms them)
+  D[2] = 0.0 * dxd_dxi + fy * dyd_dxi; D[3] = 0.0 * dxd_dyi + fy * dyd_dyi;
+}
+// PinholePose<Cal3Fisheye>(pose, K).project (PinholePose.h:89-109): project2 as it is, then the above, chained into Dpose 2x6 and
+// Dpoint 2x3 (both or none).  false on a CheiralityException.
+GT_HD bool fisheye_project(const double* T, const double* K, const double* pw, double* pi, double* Dpose, double* Dpoint) {
+  double pn[2], Dps[12], Dpt[6], D[4];
+  const bool want = Dpose || Dpoint;
+  if (!(want ? project2(T, pw, pn, Dps, Dpt) : project2(T, pw, pn, nullptr, nullptr))) return false;
+  if (!want) { fisheye_uncalibrate(K, pn, pi, nullptr); return true; }
+  fisheye_uncalibrate(K, pn, pi, D);
+  if (Dpose)
+    _Pragma("unroll") for (int j = 0; j < 6; j++) {
+      Dpose[j] = D[0] * Dps[j] + D[1] * Dps[6 + j];
+      Dpose[6 + j] = D[2] * Dps[j] + D[3] * Dps[6 + j];
+    }
+  if (Dpoint)
+    _Pragma("unroll") for (int j = 0; j < 3; j++) {
+      Dpoint[j] = D[0] * Dpt[j] + D[1] * Dpt[3 + j];
+      Dpoint[3 + j] = D[2] * Dpt[j] + D[3] * Dpt[3 + j];
+    }
+  return true;
+}
+
 // ---- SmartProjectionPoseFactor<Cal3_S2>: cameras PinholePose<Cal3_S2>(pose * body_P_sensor, K) (slam/SmartProjectionPoseFactor.h:138-147) ----
 // Cal3_S2::calibrate (geometry/Cal3_S2.cpp:53-69) and ::uncalibrate (:44-50); K = fx, fy, s, u0, v0
 GT_HD void s2_calibrate(const double* K, const double* pi, double* pn) {

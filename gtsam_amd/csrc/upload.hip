@@ -236,6 +236,42 @@ bool check_planar(const gtg_problem& p, int n_shards) {
   return true;
 }
 
+// The list gtg_set_calibration_models left in the host index (upload_problem has taken it out), checked against the problem it is consumed by.  Returns the model of
+// every calib row when some row is a Cal3Fisheye, and an empty list otherwise: a list of pinhole rows is no list.  A fisheye row is
+// allowed only where the projection range would be ProjForm::Rows2 without it (context.h).
+std::vector<int32_t> check_calibration_models(std::vector<int32_t> model, const gtg_problem& p, bool planar) {
+  if (model.empty()) return model;
+  if ((int64_t)model.size() != (int64_t)(p.n_calib > 0 ? p.n_calib : 0))
+    throw std::invalid_argument("gtg_set_calibration_models: n_calib differs from the n_calib of the uploaded problem");
+  bool fisheye = false;
+  for (int32_t m : model) {
+    if (m != GTG_CALIB_PINHOLE && m != GTG_CALIB_FISHEYE)
+      throw std::invalid_argument("gtg_set_calibration_models: unknown calibration model (GTG_CALIB_PINHOLE or GTG_CALIB_FISHEYE)");
+    fisheye = fisheye || m == GTG_CALIB_FISHEYE;
+  }
+  if (!fisheye) return {};
+  if (planar) throw std::invalid_argument("Cal3Fisheye: a fisheye calibration row in a planar graph is not supported");
+  if (!p.calib_distortion)
+    throw std::invalid_argument("Cal3Fisheye: a fisheye calibration row needs calib_distortion (k1, k2, k3, k4), which is NULL");
+  const auto is_fisheye = [&](int32_t ci) { return ci >= 0 && ci < p.n_calib && model[(size_t)ci] == GTG_CALIB_FISHEYE; };
+  const int64_t n_stereo = p.n_stereo > 0 && p.stereo_calib ? p.n_stereo : 0, n_smart = p.n_smart > 0 ? p.n_smart : 0;
+  for (int64_t i = 0; i < n_stereo; i++)
+    if (is_fisheye(p.stereo_calib[i]))
+      throw std::invalid_argument("Cal3Fisheye: a GenericStereoFactor names a fisheye calibration row (Cal3_S2Stereo only)");
+  if (n_smart && p.smart_calib)
+    for (int64_t i = 0; i < n_smart; i++)
+      if (is_fisheye(p.smart_calib[i]))
+        throw std::invalid_argument("Cal3Fisheye: a smart factor names a fisheye calibration row through smart_calib (Cal3_S2 only)");
+  if (n_smart && p.smart_meas_calib && p.smart_ptr)
+    for (int64_t k = 0; k < p.smart_ptr[n_smart]; k++)
+      if (is_fisheye(p.smart_meas_calib[k]))
+        throw std::invalid_argument("Cal3Fisheye: a smart factor names a fisheye calibration row through smart_meas_calib (Cal3_S2 only)");
+  if (p.n_stereo > 0 || p.n_sam > 0 || n_smart)
+    throw std::invalid_argument("Cal3Fisheye: a fisheye calibration row in a graph with stereo, 3-D bearing / range or smart factors is not supported "
+                                "(two-row projection graphs only)");
+  return model;
+}
+
 // noise table: derive the inverse sigmas like the reference constructors (NoiseModel.cpp:275-281, Isotropic ctor)
 void upload_noise_table(gtg_context& c, const gtg_problem& p) {
   std::vector<int32_t> kind(p.noise_kind, p.noise_kind + p.n_noise);
@@ -438,18 +474,24 @@ void upload_planar(gtg_context& c, HostIndex& hi, const gtg_problem& p) {
   up(f.proj_pose, pose, c.stream); up(f.proj_point, pt, c.stream); up(f.proj_noise, nz, c.stream); up(f.proj_calib, none, c.stream);
   up(f.proj_sensor, none, c.stream);
   const std::vector<double> empty;
-  up(f.proj_z, empty, c.stream); up(f.calib, empty, c.stream); up(f.sensor, empty, c.stream); f.calib_baseline.free();
+  up(f.proj_z, empty, c.stream); up(f.calib, empty, c.stream); up(f.sensor, empty, c.stream); f.calib_baseline.free(); f.calib_model.free();
   f.proj_J.alloc(std::max<size_t>((size_t)kPlanarRec * f.n_proj, 1));
   hi.proj_pose = pose; hi.proj_point = pt;
 }
 
-void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, const std::vector<int32_t>& of_obs, const std::vector<uint8_t>& is_rig, const ShardFilter& own, bool planar) {
+void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, const std::vector<int32_t>& of_obs, const std::vector<uint8_t>& is_rig, const ShardFilter& own, bool planar,
+                       const std::vector<int32_t>& calib_model) {
   auto& f = c.f;
   std::vector<int32_t> pose, pt, nz, cal, sen; std::vector<double> z;
   const int64_t n_stereo = p.n_stereo > 0 ? p.n_stereo : 0, n_sam = p.n_sam > 0 ? p.n_sam : 0;
   if (planar) { upload_planar(c, hi, p); return; }
   f.form = n_sam > 0 ? ProjForm::Rows3Sam : n_stereo > 0 ? ProjForm::Rows3 : c.smart_pose ? ProjForm::Rows2Smart : ProjForm::Rows2;   // from the WHOLE graph (context.h; SmartView has refused smart_pose beside the other two)
   static_assert(proj_rec(ProjForm::Rows2) == kProjRec && proj_rec(ProjForm::Rows3) == kStereoRec, "context.h states the record lengths of factors.h");
+  if (!calib_model.empty()) {   // some calib row is a Cal3Fisheye (take_calibration_models has refused it beside everything but Rows2)
+    if (f.form != ProjForm::Rows2) throw std::logic_error("Cal3Fisheye: the projection range is not two-row");
+    f.form = ProjForm::Rows2Fisheye;
+    static_assert(proj_rec(ProjForm::Rows2Fisheye) == kProjRec, "the fisheye form keeps the records of Rows2");
+  }
   for (int64_t i = 0; i < p.n_proj; i++) {
     check_var(p, p.proj_pose[i]); check_var(p, p.proj_point[i]); check_noise(p, p.proj_noise[i], 2, "GenericProjectionFactor");
     if (p.proj_calib[i] < 0 || p.proj_calib[i] >= p.n_calib) throw std::invalid_argument("bad calibration index");
@@ -513,6 +555,7 @@ void upload_projection(gtg_context& c, HostIndex& hi, const gtg_problem& p, cons
     if (p.calib_distortion) for (int j = 0; j < 4; j++) calib[kCalibStride * (size_t)k + 5 + j] = p.calib_distortion[4 * (size_t)k + j];
   }
   up(f.calib, calib, c.stream); up(f.sensor, sensor, c.stream);
+  if (f.form == ProjForm::Rows2Fisheye) up(f.calib_model, calib_model, c.stream); else f.calib_model.free();   // (a fisheye row: fx fy s u0 v0 k1 k2 k3 k4)
   if (n_stereo) {   // the baselines beside the table, so that the table and the kernels of a graph without stereo factors stay as they are
     std::vector<double> bl(p.calib_baseline, p.calib_baseline + p.n_calib);
     up(f.calib_baseline, bl, c.stream);
@@ -602,8 +645,11 @@ void upload_problem(gtg_context& c, const gtg_problem& user, int shard, int n_sh
   // GeneralSFM records recomputed where they are needed instead of stored (fused.h) -- not with smart factors, whose measurements'
   // records depend on the factor's triangulation status, and not beside stereo or bearing / range factors, whose three-row records
   // only the stored-record kernels read
+  std::vector<int32_t> pending_models;
+  pending_models.swap(host_index(&c).calib_model);   // consumed by this upload, whatever becomes of it
   const bool planar = check_planar(user, n_shards);   // (its own records and kernels: context.h ProjForm::Planar)
   c.fused_sfm = GTG_FUSED_SFM != 0 && c.n_smart == 0 && !(user.n_stereo > 0) && !(user.n_sam > 0) && !planar;
+  const std::vector<int32_t> calib_model = check_calibration_models(std::move(pending_models), user, planar);   // (empty: every calib row a pinhole)
   const SmartView view(user);
   const gtg_problem& p = view.problem();
   c.smart_pose = view.pose; c.smart_repeats = view.repeats; c.smart_obs0 = view.pose ? user.n_proj : user.n_sfm;
@@ -615,7 +661,7 @@ void upload_problem(gtg_context& c, const gtg_problem& user, int shard, int n_sh
   keep_whole_graph_keys(hi, p, n_shards);
   SideUpload side;   // started by upload_sfm for a whole, non-empty table
   upload_sfm(c, hi, p, view.of_obs, own, side);
-  upload_projection(c, hi, p, view.of_obs, view.is_rig, own, planar);
+  upload_projection(c, hi, p, view.of_obs, view.is_rig, own, planar, calib_model);
   upload_between(c, hi, p, own);
   upload_priors(c, hi, p, own);
   clk.lap("factor tables (shard filter + upload)");

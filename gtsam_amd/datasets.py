@@ -1376,3 +1376,133 @@ def planar_slam_example():
     initial.insert(X(1), A.Pose2(0.5, 0.0, 0.2)); initial.insert(X(2), A.Pose2(2.3, 0.1, -0.2)); initial.insert(X(3), A.Pose2(4.1, 0.1, 0.1))
     initial.insert(L(1), A.Point2(1.8, 2.1)); initial.insert(L(2), A.Point2(4.1, 1.8))
     return graph, initial
+
+
+def _project_pixel(K, Rw, tw, pt):
+    """The pixel of a world point through the calibration object K (Cal3_S2, Cal3DS2 or Cal3Fisheye of the API mirror) of a camera at
+    (Rw, tw), or None behind the camera; for building scenes."""
+    q = Rw.T @ (pt - tw)
+    if q[2] <= 0:
+        return None
+    u, v = q[0] / q[2], q[1] / q[2]
+    if hasattr(K, "uncalibrate"):
+        return K.uncalibrate((u, v))
+    fx, fy, s, u0, v0 = K.v[:5]
+    if K.v.size == 9:       # Cal3DS2: radial and tangential distortion of the intrinsic point
+        k1, k2, p1, p2 = K.v[5:]
+        rr = u * u + v * v; g = 1 + k1 * rr + k2 * rr * rr
+        u, v = g * u + 2 * p1 * u * v + p2 * (rr + 2 * u * u), g * v + 2 * p2 * u * v + p1 * (rr + 2 * v * v)
+    return np.array([fx * u + s * v + u0, fy * v + v0])
+
+
+def fisheye_example_graph():
+    """The graph of the reference's examples/FisheyeExample.cpp: the eight corners of the cube of examples/SFMdata.h seen from its eight
+    poses on a circle of radius 30, every (pose, corner) pair a GenericProjectionFactor<Pose3, Point3, Cal3Fisheye> with the exact
+    projection as its measurement and the example's calibration literal; a prior on the first pose and on the first corner; the
+    example's perturbed initial values.  Graph order as in the example: the two priors, then the projection factors pose by pose.
+    Returns (graph, initial values)."""
+    from . import api as A
+    from .io import _ypr
+    X, L = A.symbol_shorthand.X, A.symbol_shorthand.L
+    nm = A.noiseModel
+    K = A.Cal3Fisheye(278.66, 278.48, 0.0, 319.75, 241.96, -0.013721808247486035, 0.020727425669427896, -0.012786476702685545,
+                      0.0025242267320687625)
+    points = np.array([[10.0, 10.0, 10.0], [-10.0, 10.0, 10.0], [-10.0, -10.0, 10.0], [10.0, -10.0, 10.0],
+                       [10.0, 10.0, -10.0], [-10.0, 10.0, -10.0], [-10.0, -10.0, -10.0], [10.0, -10.0, -10.0]])
+    Rd, td = _ypr(0.0, -np.pi / 4, 0.0), np.array([np.sin(np.pi / 4) * 30, 0.0, 30 * (1 - np.sin(np.pi / 4))])
+    poses = [(_ypr(np.pi / 2, 0.0, -np.pi / 2), np.array([30.0, 0.0, 0.0]))]
+    for _ in range(7):
+        Rp, tp = poses[-1]
+        poses.append((Rp @ Rd, tp + Rp @ td))
+    graph, initial = A.NonlinearFactorGraph(), A.Values()
+    graph.addPriorPose3(X(0), A.Pose3(A.Rot3(poses[0][0]), poses[0][1]), nm.Diagonal.Sigmas([0.1] * 3 + [0.3] * 3))
+    graph.addPriorPoint3(L(0), points[0], nm.Isotropic.Sigma(3, 0.1))
+    noise = nm.Isotropic.Sigma(2, 1.0)
+    for j, pt in enumerate(points):
+        initial.insert(L(j), pt + np.array([-0.25, 0.20, 0.15]))
+    Rk, tk = _rodrigues(np.array([[-0.1, 0.2, 0.25]]))[0], np.array([0.05, -0.10, 0.20])
+    for i, (Rp, tp) in enumerate(poses):
+        for j, pt in enumerate(points):
+            graph.add(A.GenericProjectionFactorCal3Fisheye(_project_pixel(K, Rp, tp, pt), noise, X(i), L(j), K))
+        initial.insert(X(i), A.Pose3(A.Rot3(Rp @ Rk), tp + Rp @ tk))
+    return graph, initial
+
+
+def fisheye_mixed_graph(n_poses=11, n_points=36, seed=0):
+    """A small rig graph that enters every branch of GenericProjectionFactor<Pose3, Point3, Cal3Fisheye> on the device, built through the
+    API mirror the way user code would: poses on an arc looking at a point cloud, every (pose, landmark) pair a projection factor whose
+    calibration cycles through two Cal3Fisheye (the second with a NON-ZERO skew), a Cal3_S2 and a Cal3DS2; every third factor is
+    mounted through one of two body_P_sensor; dim-2 Unit / Isotropic / Diagonal / Gaussian noise, Robust(Huber) and Robust(Cauchy);
+    BetweenFactor<Pose3> along the arc, a prior on the first pose and on one landmark.  The middle pose starts with the identity
+    rotation, and three factors are in a branch of their own AT THE INITIAL VALUES:
+      on_axis  a landmark exactly on the optical axis of the middle pose (r^2 == 0), through the skewed fisheye calibration, Unit noise;
+      taylor   a landmark with 0 < r = 1e-9 from the same pose (the Taylor branch of Cal3Fisheye::Scaling);
+      behind   the last landmark, 0.5 behind pose 0 (cheirality), which only the last two poses see from the front, Isotropic(1.5).
+    Graph order: projection, between, prior.  Returns (graph, initial values, {branch name: index among the projection factors})."""
+    from . import api as A
+    rng = np.random.default_rng(seed)
+    mid = n_poses // 2
+    ang = np.linspace(-0.5, 0.5, n_poses)
+    centers = np.stack([8 * np.sin(ang), 0.25 + 0.1 * rng.normal(size=n_poses), -8 * np.cos(ang)], 1)
+    R = _rodrigues(np.stack([0.02 * rng.normal(size=n_poses), -ang, 0.02 * rng.normal(size=n_poses)], 1))   # looks at the origin (+z)
+    pts = np.stack([rng.uniform(-2, 2, n_points), rng.uniform(-1.5, 1.5, n_points), rng.uniform(-2, 2, n_points)], 1)
+    t_mid = np.array([0.0, 0.25, -8.0])                                        # where the middle pose starts, with the identity rotation
+    pts[0] = t_mid + np.array([0.0, 0.0, 8.0]) + rng.normal(0, 0.03, 3)       # starts on its optical axis
+    pts[1] = t_mid + np.array([0.0, 0.0, 7.0]) + rng.normal(0, 0.03, 3)       # starts 1e-9 off it
+    pts[-1] = centers[0] - 0.5 * R[0][:, 2] + np.array([0.2, -0.1, 0.0])       # 0.5 behind pose 0 along its optical axis
+    X, L = A.symbol_shorthand.X, A.symbol_shorthand.L
+    Kf = A.Cal3Fisheye(278.66, 278.48, 0.0, 319.75, 241.96, -0.013721808247486035, 0.020727425669427896, -0.012786476702685545,
+                       0.0025242267320687625)
+    Ks = A.Cal3Fisheye(300.0, 295.0, 0.8, 320.0, 240.0, -0.02, 0.01, -0.005, 0.001)      # skew 0.8: DK's off-diagonal entry
+    Km = A.Cal3_S2(520.0, 515.0, 0.3, 320.0, 240.0)
+    Kd = A.Cal3DS2(400.0, 400.0, 0.0, 300.0, 200.0, 0.05, -0.01, 0.001, -0.002)
+    cals = [Kf, Km, Ks, Kd]
+    sensors = []
+    for w, t in (([0.02, -0.03, 0.01], [0.1, -0.05, 0.2]), ([-0.01, 0.04, 0.02], [-0.08, 0.03, 0.1])):
+        sensors.append((_rodrigues(np.array([w]))[0], np.array(t)))
+    Rg = np.array([[1.1, 0.2], [0.0, 0.9]])
+    nm = A.noiseModel
+    models = [nm.Unit.Create(2), nm.Isotropic.Sigma(2, 1.5), nm.Diagonal.Sigmas([1.0, 1.3]), nm.Gaussian.SqrtInformation(Rg),
+              nm.Robust.Create(nm.mEstimator.Huber.Create(1.345), nm.Isotropic.Sigma(2, 1.2)),
+              nm.Robust.Create(nm.mEstimator.Cauchy.Create(2.0), nm.Diagonal.Sigmas([1.1, 0.9]))]
+    graph, initial = A.NonlinearFactorGraph(), A.Values()
+    branch, k = {}, 0
+    for i in range(n_poses):
+        for j in range(n_points):
+            if j == n_points - 1 and 0 < i < n_poses - 2:
+                continue                                  # (the last landmark: seen from behind by pose 0, from the front by the last two poses only)
+            K, sen, model = cals[k % 4], sensors[(k // 3) % 2] if k % 3 == 0 else None, models[(k + k // 4) % 6]      # (every noise kind under every calibration)
+            if i == mid and j == 0:
+                branch["on_axis"] = k; K, sen, model = Ks, None, models[0]      # (Unit: the record is the factor's own Jacobian)
+            elif i == mid and j == 1:
+                branch["taylor"] = k; K, sen = Kf, None
+            elif i == 0 and j == n_points - 1:
+                branch["behind"] = k; K, sen, model = Kf, None, models[1]       # (Isotropic 1.5: the residual is 2 fx / 1.5 in both rows)
+            Rw, tw = (R[i], centers[i]) if sen is None else (R[i] @ sen[0], centers[i] + R[i] @ sen[1])
+            z = _project_pixel(K, Rw, tw, pts[j])
+            z = rng.normal(300.0, 50.0, 2) if z is None else z + rng.normal(0, 0.7, 2)
+            graph.add(type_of_projection(A, K)(z, model, X(i), L(j), K, None if sen is None else A.Pose3(A.Rot3(sen[0]), sen[1])))
+            k += 1
+    n6 = nm.Diagonal.Sigmas([0.01] * 3 + [0.05] * 3); n6b = nm.Diagonal.Sigmas([0.02, 0.02, 0.03, 0.1, 0.1, 0.15])
+    for i in range(n_poses - 1):
+        Rz = R[i].T @ R[i + 1]; tz = R[i].T @ (centers[i + 1] - centers[i])
+        graph.add(A.BetweenFactorPose3(X(i), X(i + 1), A.Pose3(A.Rot3(Rz @ _rodrigues(rng.normal(0, 0.005, (1, 3)))[0]), tz + rng.normal(0, 0.02, 3)), n6b))
+    graph.addPriorPose3(X(0), A.Pose3(A.Rot3(R[0]), centers[0]), n6)
+    graph.addPriorPoint3(L(2), pts[2], nm.Isotropic.Sigma(3, 0.1))
+    dR = _rodrigues(rng.normal(0, 0.01, (n_poses, 3)))
+    for i in range(n_poses):
+        if i == mid:
+            initial.insert(X(i), A.Pose3(A.Rot3(np.eye(3)), t_mid))
+        else:
+            initial.insert(X(i), A.Pose3(A.Rot3(R[i] @ dR[i]), centers[i] + rng.normal(0, 0.05, 3)))
+    for j in range(n_points):
+        initial.insert(L(j), pts[j] + rng.normal(0, 0.05, 3))
+    initial.update(L(0), t_mid + np.array([0.0, 0.0, 8.0]))
+    initial.update(L(1), t_mid + np.array([7e-9, 0.0, 7.0]))
+    return graph, initial, branch
+
+
+def type_of_projection(A, K):
+    """The GenericProjectionFactor instantiation of the API mirror for a calibration object."""
+    return {A.Cal3_S2: A.GenericProjectionFactorCal3_S2, A.Cal3DS2: A.GenericProjectionFactorCal3DS2,
+            A.Cal3Fisheye: A.GenericProjectionFactorCal3Fisheye}[type(K)]

@@ -4,6 +4,7 @@
 
 #include <gtsam/geometry/Cal3Bundler.h>
 #include <gtsam/geometry/Cal3DS2.h>
+#include <gtsam/geometry/Cal3Fisheye.h>
 #include <gtsam/geometry/Cal3_S2.h>
 #include <gtsam/geometry/PinholeCamera.h>
 #include <gtsam/geometry/Pose2.h>
@@ -77,6 +78,7 @@ typedef PinholeCamera<Cal3Bundler> SfmCamera;
 typedef GeneralSFMFactor<SfmCamera, Point3> SfmFactor;
 typedef GenericProjectionFactor<Pose3, Point3, Cal3_S2> ProjFactor;
 typedef GenericProjectionFactor<Pose3, Point3, Cal3DS2> ProjFactorDS2;
+typedef GenericProjectionFactor<Pose3, Point3, Cal3Fisheye> ProjFactorFisheye;
 typedef GenericStereoFactor<Pose3, Point3> StereoFactor;
 typedef BearingRangeFactor<Pose3, Point3> SamBearingRangeFactor;   // gtsam/sam: wrapped as BearingRangeFactor3D, RangeFactor3D, BearingFactor3D
 typedef RangeFactor<Pose3, Point3> SamRangeFactor;
@@ -410,14 +412,14 @@ struct Extract {
   typedef std::vector<std::pair<int64_t, SharedNoiseModel>> Runs;
   Runs sfm_nz, pj_nz, st_nz, sam_nz, bt_nz, pr_nz, sm_nz, pp_nz, s2_nz;
   std::vector<int32_t> bt_dim, pr_dim, sam_dim, pp_dim, s2_dim;             // expected noise dimension per between / prior / sam / partial prior / planar sam factor
-  std::vector<std::pair<const void*, int>> pj_cal;                          // calibration object per projection factor, 1 = Cal3DS2
+  std::vector<std::pair<const void*, int>> pj_cal;                          // calibration object per projection factor, 1 = Cal3DS2, 3 = Cal3Fisheye
   std::vector<const Cal3_S2Stereo*> st_cal;                                 // calibration object per stereo factor
   std::vector<const Cal3_S2*> sm_cal;                                       // per smart factor: the shared K of a pose-type factor, null for a camera-type one
   std::vector<int32_t> sm_sen;                                              // per smart factor: row of `sensor` (this chunk's) or -1
   std::vector<const SmartRigFactor::Cameras*> sm_rig;                       // per smart factor: the rig of a rig-type factor, else null
   std::vector<int32_t> sm_cid;                                              // per smart measurement: camera id in that rig (0 for other factors)
   std::vector<uint8_t> sensor_shared;                                       // per row of `sensor`: 1 = a smart factor's body_P_sensor, shared by value (mergeTables)
-  std::vector<std::pair<const void*, int>> cal_order;                       // the calibration objects the chunk's factors name, in the order they are first met (0 Cal3_S2, 1 Cal3DS2, 2 Cal3_S2Stereo):
+  std::vector<std::pair<const void*, int>> cal_order;                       // the calibration objects the chunk's factors name, in the order they are first met (0 Cal3_S2, 1 Cal3DS2, 2 Cal3_S2Stereo, 3 Cal3Fisheye):
   std::set<const void*> cal_seen;                                           // the calib table gets its rows in GRAPH order, whichever factor type names an object first
   void calibration(const void* K, int kind) { if (cal_seen.insert(K).second) cal_order.emplace_back(K, kind); }
   std::exception_ptr err;                                                   // what the chunk's first offending factor threw
@@ -430,15 +432,16 @@ void addSfm(Extract& x, const SfmFactor& s, const std::vector<Key>& keys) {
   x.sfm_z.push_back(s.measured().x()); x.sfm_z.push_back(s.measured().y());
   Extract::run(x.sfm_nz, s.noiseModel());
 }
-// GenericProjectionFactor<Pose3, Point3, Cal3_S2>, or the same factor with a Cal3DS2 calibration (section 8(f) #3)
+// GenericProjectionFactor<Pose3, Point3, Cal3_S2>, or the same factor with a Cal3DS2 calibration (section 8(f) #3) or a Cal3Fisheye one
+template <class CAL> constexpr int calibrationKind() { return std::is_same<CAL, Cal3DS2>::value ? 1 : std::is_same<CAL, Cal3Fisheye>::value ? 3 : 0; }
 template <class CAL> void addProjection(Extract& x, const GenericProjectionFactor<Pose3, Point3, CAL>& p, const std::vector<Key>& keys) {
   x.fac_map.emplace_back(GTG_FAC_PROJECTION, (int64_t)x.pj_pose.size());
   if (p.throwCheirality()) throw std::invalid_argument("GenericProjectionFactor with throwCheirality is not supported");
   x.pj_pose.push_back(idOf(keys, p.key1())); x.pj_pt.push_back(idOf(keys, p.key2()));
   x.pj_z.push_back(p.measured().x()); x.pj_z.push_back(p.measured().y());
   Extract::run(x.pj_nz, p.noiseModel());
-  x.pj_cal.emplace_back(p.calibration().get(), std::is_same<CAL, Cal3DS2>::value ? 1 : 0);
-  x.calibration(p.calibration().get(), std::is_same<CAL, Cal3DS2>::value ? 1 : 0);
+  x.pj_cal.emplace_back(p.calibration().get(), calibrationKind<CAL>());
+  x.calibration(p.calibration().get(), calibrationKind<CAL>());
   if (p.body_P_sensor()) { x.pj_sen.push_back((int32_t)(x.sensor.size() / 12)); packPose(*p.body_P_sensor(), Extract::grow(x.sensor, 12)); x.sensor_shared.push_back(0); }
   else x.pj_sen.push_back(-1);
 }
@@ -551,6 +554,7 @@ void addFactor(Extract& x, const NonlinearFactor* f, const std::vector<Key>& key
   if (auto s = dynamic_cast<const SfmFactor*>(f)) addSfm(x, *s, keys);
   else if (auto p = dynamic_cast<const ProjFactor*>(f)) addProjection(x, *p, keys);
   else if (auto pd = dynamic_cast<const ProjFactorDS2*>(f)) addProjection(x, *pd, keys);
+  else if (auto pf = dynamic_cast<const ProjFactorFisheye*>(f)) addProjection(x, *pf, keys);
   else if (auto st = dynamic_cast<const StereoFactor*>(f)) addStereo(x, *st, keys);
   else if (auto br = dynamic_cast<const SamBearingRangeFactor*>(f)) { const Unit3 u = br->measured().bearing(); const double r = br->measured().range(); addSam(x, GTG_SAM_BEARING_RANGE, br->keys()[0], br->keys()[1], &u, &r, br->noiseModel(), keys); }
   else if (auto rf = dynamic_cast<const SamRangeFactor*>(f)) { const double r = rf->measured(); addSam(x, GTG_SAM_RANGE, rf->keys()[0], rf->keys()[1], nullptr, &r, rf->noiseModel(), keys); }
@@ -572,7 +576,7 @@ void addFactor(Extract& x, const NonlinearFactor* f, const std::vector<Key>& key
   else if (auto pc = dynamic_cast<const PriorFactor<SfmCamera>*>(f)) addPrior(x, *pc, keys);
   else if (auto p3 = dynamic_cast<const PriorFactor<Point3>*>(f)) addPrior(x, *p3, keys);
   else throw std::invalid_argument("GpuLevenbergMarquardtOptimizer: factor type outside the GPU hot path "   // (anything else is a hard error)
-                                   "(supported: GeneralSFMFactor<SfmCamera,Point3>, GenericProjectionFactor<Pose3,Point3,Cal3_S2|Cal3DS2>, "
+                                   "(supported: GeneralSFMFactor<SfmCamera,Point3>, GenericProjectionFactor<Pose3,Point3,Cal3_S2|Cal3DS2|Cal3Fisheye>, "
                                    "GenericStereoFactor<Pose3,Point3>, BearingRangeFactor|RangeFactor|BearingFactor<Pose3,Point3> and <Pose2,Point2>, SmartProjectionFactor<SfmCamera>, SmartProjectionPoseFactor<Cal3_S2>, SmartProjectionRigFactor<PinholePose<Cal3_S2>>, BetweenFactor<Pose3|Pose2>, PriorFactor<Pose3|Pose2|SfmCamera|Point3>, PoseTranslationPrior|PoseRotationPrior<Pose3|Pose2>)");
 }
 // The factors [b, e) of `graph` into x, each pointer also copied into `graphCopy`; the chunk stops at its first offending factor and keeps what that threw.
@@ -585,7 +589,7 @@ void extractChunk(Extract& x, const NonlinearFactorGraph& graph, NonlinearFactor
   if (b < e && graph.begin()[b]) {
     const NonlinearFactor* f0 = graph.begin()[b].get();
     if (dynamic_cast<const SfmFactor*>(f0)) { x.sfm_cam.reserve(e - b); x.sfm_pt.reserve(e - b); x.sfm_z.reserve(2 * (e - b)); }
-    else if (dynamic_cast<const ProjFactor*>(f0) || dynamic_cast<const ProjFactorDS2*>(f0)) { x.pj_pose.reserve(e - b); x.pj_pt.reserve(e - b); x.pj_sen.reserve(e - b); x.pj_z.reserve(2 * (e - b)); x.pj_cal.reserve(e - b); }
+    else if (dynamic_cast<const ProjFactor*>(f0) || dynamic_cast<const ProjFactorDS2*>(f0) || dynamic_cast<const ProjFactorFisheye*>(f0)) { x.pj_pose.reserve(e - b); x.pj_pt.reserve(e - b); x.pj_sen.reserve(e - b); x.pj_z.reserve(2 * (e - b)); x.pj_cal.reserve(e - b); }
     else if (dynamic_cast<const BetweenFactor<Pose3>*>(f0) || dynamic_cast<const BetweenFactor<Pose2>*>(f0)) { x.bt_1.reserve(e - b); x.bt_2.reserve(e - b); x.bt_z.reserve(12 * (e - b)); x.bt_dim.reserve(e - b); }
   }
   try {
@@ -615,16 +619,21 @@ struct HostProblem {
   std::map<std::pair<const void*, int32_t>, std::pair<int32_t, int32_t>> rig_rows;   // (rig object, camera id) -> (calib row, sensor row or -1)
   std::map<std::array<double, 12>, int32_t> shared_sensor;   // the body_P_sensor of smart factors -> row of the sensor table
   std::map<const void*, int32_t> calib_id;   // shared calibration objects (Cal3_S2 or Cal3DS2) -> row of the calibration table
-  std::vector<double> calib_dist;            // k1 k2 p1 p2 per row (zero for a Cal3_S2)
+  std::vector<double> calib_dist;            // k1 k2 p1 p2 per row (zero for a Cal3_S2), k1 k2 k3 k4 of a Cal3Fisheye
+  std::vector<int32_t> calib_model;          // GTG_CALIB_* per row: what gtg_set_calibration_models takes when some row is a Cal3Fisheye
+  bool any_fisheye = false;
   std::vector<double> calib_base;            // baseline per row (zero unless the row is a Cal3_S2Stereo)
   bool any_distortion = false;
   template <class CAL> void pinhole(const CAL* K) { calib.insert(calib.end(), {K->fx(), K->fy(), K->skew(), K->px(), K->py()}); }
-  int32_t calibRow(const void* object, int distorted) {
+  int32_t calibRow(const void* object, int kind) {   // kind: 0 Cal3_S2, 1 Cal3DS2, 3 Cal3Fisheye
     auto it = calib_id.find(object);
     if (it != calib_id.end()) return it->second;
     it = calib_id.emplace(object, (int32_t)(calib.size() / 5)).first;
-    const Cal3DS2* D = distorted ? static_cast<const Cal3DS2*>(object) : nullptr;
-    if (D) { pinhole(D); calib_dist.insert(calib_dist.end(), {D->k1(), D->k2(), D->p1(), D->p2()}); any_distortion = true; }
+    const Cal3DS2* D = kind == 1 ? static_cast<const Cal3DS2*>(object) : nullptr;
+    const Cal3Fisheye* F = kind == 3 ? static_cast<const Cal3Fisheye*>(object) : nullptr;
+    calib_model.push_back(F ? GTG_CALIB_FISHEYE : GTG_CALIB_PINHOLE);
+    if (F) { pinhole(F); calib_dist.insert(calib_dist.end(), {F->k1(), F->k2(), F->k3(), F->k4()}); any_distortion = true; any_fisheye = true; }
+    else if (D) { pinhole(D); calib_dist.insert(calib_dist.end(), {D->k1(), D->k2(), D->p1(), D->p2()}); any_distortion = true; }
     else { pinhole(static_cast<const Cal3_S2*>(object)); calib_dist.insert(calib_dist.end(), {0.0, 0.0, 0.0, 0.0}); }
     calib_base.push_back(0.0);
     return it->second;
@@ -644,7 +653,7 @@ struct HostProblem {
     auto it = calib_id.find(K);
     if (it != calib_id.end()) return it->second;
     it = calib_id.emplace(K, (int32_t)(calib.size() / 5)).first;
-    pinhole(K); calib_dist.insert(calib_dist.end(), {0.0, 0.0, 0.0, 0.0}); calib_base.push_back(K->baseline());
+    pinhole(K); calib_dist.insert(calib_dist.end(), {0.0, 0.0, 0.0, 0.0}); calib_base.push_back(K->baseline()); calib_model.push_back(GTG_CALIB_PINHOLE);
     return it->second;
   }
   gtg_problem view(const std::vector<int32_t>& var_type) const {   // (pointers into this object and into var_type: both outlive the upload)
@@ -900,6 +909,8 @@ void GpuLevenbergMarquardtOptimizer::init(const NonlinearFactorGraph& graph, con
   // launches either find their kernels loaded or load them themselves, while the helper goes on to the per-try kernels)
   check(gtg_create(&m.h, device), "gtg_create");
   if (shards.allreduce) check(gtg_set_allreduce(m.h, shards.allreduce, shards.user), "gtg_set_allreduce");   // before the upload: it verifies the layout across the shards
+  // (a Cal3Fisheye row: its model goes beside the problem, consumed by the upload that follows)
+  if (hp.any_fisheye) check(gtg_set_calibration_models(m.h, hp.calib_model.data(), (int32_t)hp.calib_model.size()), "gtg_set_calibration_models");
   check(gtg_upload_problem(m.h, &pb, shards.shard, shards.n_shards), "gtg_upload_problem");
   check(gtg_set_values(m.h, m.packed.data(), (int64_t)m.packed.size()), "gtg_set_values");
   lap("library: create + upload + set_values");

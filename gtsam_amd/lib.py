@@ -22,7 +22,7 @@ PHASES = ["linearize", "assemble", "point_eliminate", "schur", "cholesky", "solv
 
 # every symbol include/gtsam_amd.h declares (tests check the .so exports all of them)
 SYMBOLS = ["gtg_create", "gtg_destroy", "gtg_prewarm", "gtg_last_error", "gtg_version", "gtg_upload_problem",
-           "gtg_set_reduced_ordering", "gtg_values_size", "gtg_tangent_size", "gtg_set_values",
+           "gtg_set_reduced_ordering", "gtg_set_calibration_models", "gtg_values_size", "gtg_tangent_size", "gtg_set_values",
            "gtg_get_values", "gtg_get_trial_values", "gtg_error", "gtg_linearize", "gtg_try_lambda", "gtg_try_lambda_pcg",
            "gtg_accept", "gtg_get_delta", "gtg_get_gradient", "gtg_get_graph_gradient", "gtg_get_hessian_diagonal",
            "gtg_get_jacobians", "gtg_reduced_dim", "gtg_get_reduced_matrix", "gtg_set_allreduce",
@@ -77,6 +77,7 @@ def load():
     lib.gtg_destroy.argtypes = [C.c_void_p]
     lib.gtg_upload_problem.argtypes = [C.c_void_p, C.POINTER(gtg_problem), C.c_int, C.c_int]
     lib.gtg_set_reduced_ordering.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    lib.gtg_set_calibration_models.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     for name in ("gtg_set_values", "gtg_get_values", "gtg_get_trial_values", "gtg_get_delta",
                  "gtg_get_gradient", "gtg_get_graph_gradient", "gtg_get_hessian_diagonal", "gtg_get_reduced_matrix"):
         getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -142,6 +143,9 @@ class DeviceGraph:
             o = np.ascontiguousarray(reduced_ordering, np.int32)
             _check(self.lib.gtg_set_reduced_ordering(self.h, o.ctypes.data, o.size), "gtg_set_reduced_ordering")
         self._cp = problem.to_ctypes()
+        if np.any(problem.calib_model):     # a calib row that is no pinhole (Cal3Fisheye): the next upload consumes the list
+            m = np.ascontiguousarray(problem.calib_model, np.int32)
+            _check(self.lib.gtg_set_calibration_models(self.h, m.ctypes.data, m.size), "gtg_set_calibration_models")
         _check(self.lib.gtg_upload_problem(self.h, C.byref(self._cp), shard, n_shards), "gtg_upload_problem")
         self.val_size = self.lib.gtg_values_size(self.h)
         self.dim_size = self.lib.gtg_tangent_size(self.h)

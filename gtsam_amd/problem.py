@@ -19,6 +19,7 @@ SAM_BEARING_RANGE, SAM_RANGE, SAM_BEARING = 0, 1, 2
 POSE_PARTIAL_TRANSLATION, POSE_PARTIAL_ROTATION = 0, 1
 NOISE_UNIT, NOISE_ISOTROPIC, NOISE_DIAGONAL, NOISE_GAUSSIAN = 0, 1, 2, 3
 SMART_RIG = -2     # smart_calib of a SmartProjectionRigFactor (GTG_SMART_RIG): calib / sensor per measurement
+CALIB_PINHOLE, CALIB_FISHEYE = 0, 1     # GTG_CALIB_*: the camera model of a calib row (gtg_set_calibration_models)
 ROBUST_NONE, ROBUST_FAIR, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY, ROBUST_WELSCH, ROBUST_GEMANMCCLURE, ROBUST_DCS, ROBUST_L2WITHDEADZONE = range(9)
 
 # Pose2 = (x, y, theta); a Point2 is padded to the landmark slot at the C ABI: (x, y, 0) and (dx, dy, 0)
@@ -92,6 +93,9 @@ class Problem:
     proj_sensor: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     calib: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float64))
     calib_distortion: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float64))   # [n_calib*4] k1,k2,p1,p2 (Cal3DS2) or empty
+    # CALIB_* per calib row, or empty = every row a pinhole.  Not a field of gtg_problem: it travels through gtg_set_calibration_models
+    # (lib.DeviceGraph) when some entry is non-zero.  A CALIB_FISHEYE row (Cal3Fisheye) holds k1,k2,k3,k4 in its calib_distortion row.
+    calib_model: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     # SmartProjectionFactor<PinholeCamera<Cal3Bundler>>: one track per factor (include/gtsam_amd.h)
     smart_ptr: np.ndarray = field(default_factory=lambda: np.zeros(1, np.int64))
     smart_cam: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
@@ -151,7 +155,7 @@ class Problem:
                          ("sfm_cam", np.int32), ("sfm_point", np.int32), ("sfm_z", np.float64),
                          ("sfm_noise", np.int32), ("proj_pose", np.int32), ("proj_point", np.int32),
                          ("proj_z", np.float64), ("proj_noise", np.int32), ("proj_calib", np.int32),
-                         ("proj_sensor", np.int32), ("calib", np.float64), ("sensor", np.float64),
+                         ("proj_sensor", np.int32), ("calib", np.float64), ("calib_model", np.int32), ("sensor", np.float64),
                          ("between_v1", np.int32), ("between_v2", np.int32),
                          ("between_z", np.float64), ("between_noise", np.int32),
                          ("prior_var", np.int32), ("prior_off", np.int64),
@@ -258,6 +262,8 @@ class Problem:
         if self.calib_distortion.size not in (0, 4 * p.n_calib):
             raise ValueError("calib_distortion must be empty or hold k1, k2, p1, p2 for every calibration")
         p.calib_distortion = ptr(self.calib_distortion, C.c_double)
+        if self.calib_model.size not in (0, p.n_calib):
+            raise ValueError("calib_model must be empty or hold one CALIB_* entry for every calibration")
         p.n_sensor = int(self.sensor.size // 12)
         p.sensor = ptr(self.sensor, C.c_double)
         p.n_between = self.n_between

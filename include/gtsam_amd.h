@@ -299,6 +299,19 @@ int gtg_upload_problem(gtg_handle h, const gtg_problem* p, int shard, int n_shar
  * Cuthill-McKee ordering of the reduced graph computed at upload (band-limits the tile fill). */
 int gtg_set_reduced_ordering(gtg_handle h, const int32_t* order, int32_t n);
 
+/* Optional: the camera model of every row of the calib table.  The model does not travel in gtg_problem: a row is a pinhole
+ * calibration unless this call says otherwise.  model[k] is the model of calib row k, n_calib the problem's n_calib.  Must be called
+ * before gtg_upload_problem; the list is kept by the handle, consumed by the NEXT upload and cleared by it (also by an upload that
+ * fails).  NULL or n_calib == 0 clears it.  Without the call, or with every entry GTG_CALIB_PINHOLE, an upload does exactly what it
+ * does without it.
+ *   GTG_CALIB_FISHEYE: GenericProjectionFactor<Pose3, Point3, Cal3Fisheye> (the equidistant model of geometry/Cal3Fisheye.cpp:47-108):
+ *   calib row fx,fy,s,u0,v0 and calib_distortion row k1,k2,k3,k4.  Such a row may be named by monocular projection factors only, in a
+ *   graph without stereo, 3-D bearing / range, smart or planar factors; factors with pinhole rows may share the graph.  The upload
+ *   refuses everything else, each case with its own message. */
+enum { GTG_CALIB_PINHOLE = 0,   /* Cal3_S2, or Cal3DS2 by its calib_distortion row: what every row is without the call */
+       GTG_CALIB_FISHEYE = 1 }; /* Cal3Fisheye: calib row fx,fy,s,u0,v0; calib_distortion row k1,k2,k3,k4 */
+int gtg_set_calibration_models(gtg_handle h, const int32_t* model, int32_t n_calib);
+
 /* Values in packed storage, variable id order (see GTG_VAR_*).  Values.h:74-79. */
 int64_t gtg_values_size(gtg_handle h);   /* doubles in the packed Values (the caller's variables: the landmarks of smart factors are internal) */
 int64_t gtg_tangent_size(gtg_handle h);  /* dimension of delta (VectorValues) */
